@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the stereo hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--pairs B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--pairs B] [--dump-outputs DIR]
 
 One "step" = one pass of the pipeline's data-parallel path over one batch of
 synthetic uint8 stereo pairs already resident in HBM: edge detection of both
@@ -47,6 +47,10 @@ Prints ONE JSON line (rank 0).  Extra objects:
                 the reference does not implement: PARITY UNPINNED, the build's own definition --
                 at C3 (SAD 9x9) and C5 (SSD 11x11, ghost): ms per launch, Mpixel-disparities/s and
                 the VALU issue fraction.  Never part of `value`.
+  dumped_outputs (--dump-outputs DIR) what the last timed step computed, the int32 `web` maps of its pairs (and
+                `best` with --with-best), as DIR/web.npy (DIR/best.npy) in float32: the inputs are seeded, so two
+                builds run with the same arguments can be compared output for output.  Shape, dtype and, beyond
+                64 MB in all, how the stored sample of each output was drawn.
 """
 from __future__ import annotations
 
@@ -74,6 +78,7 @@ MFMA_I8_PEAK_TOPS = 5000.0                       # dense int8 on the matrix core
 VALU_SUSTAINED_GIPS = 806.0
 WARMUP_FLOOR_S = 0.025          # minimum duration of the warm-up (clock ramp), see main()
 WARMUP_BURST = 16         # untimed steps right in front of the timed region (see main)
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs: at most this much in all, else a seeded sample
 A_CV_BYTES = 10.0               # per pixel-disparity
 A_MIN_BYTES = 6.0               # per pixel          
 
@@ -130,7 +135,45 @@ def parse(argv=None):
                     help="skip the extra `e2e` object (N = 1 only): the PCIe-inclusive rate through the "
                          "C ABI alone (pinned buffers, async copies), measured after the timed region; "
                          "it is never part of `value`")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed -- the `web` maps of its pairs "
+                         "(and `best` with --with-best) -- as DIR/<name>.npy in float32 (float64 where float32 would not "
+                         "hold the values exactly); beyond %d MB in all, a fixed seeded sample of each output's elements "
+                         "(see dumped_outputs in the line).  N > 1: every rank writes its own, <name>_rank<r>.npy"
+                         % (DUMP_LIMIT_BYTES // 10**6))
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(out_dir: str, arrays: dict, limit_bytes: int, seed: int = 0) -> dict:
+    """Write each integer array of `arrays` as out_dir/<name>.npy in float32 (float64 where float32 would not hold
+    its values exactly).  If they come to more than `limit_bytes` in all, every array is cut to the same share of
+    its elements: a sample chosen by a generator seeded with `seed`, so that two runs of the same arguments sample
+    the same elements; the file then holds those elements, flattened, in index order.  -> what was written"""
+    import numpy as np
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        exact32 = a.size == 0 or int(np.abs(a.astype(np.int64)).max()) <= 1 << 24
+        conv[name] = a.astype(np.float32 if exact32 else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    share = min(1.0, limit_bytes / total) if total else 1.0
+    written = {}
+    for name, a in conv.items():
+        rec = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": share < 1.0}
+        if share < 1.0:
+            rng = np.random.default_rng([seed, a.size])
+            idx = np.sort(rng.choice(a.size, int(a.size * share), replace=False))
+            a = a.reshape(-1)[idx]
+            rec.update(elements=int(a.size), sample="flat indices: numpy.random.default_rng([%d, size]).choice(size, "
+                                                     "elements, replace=False), sorted" % seed)
+        np.save(out / f"{name}.npy", a)
+        written[name] = rec
+    return written
 
 
 # ---------------------------------------------------------------------------
@@ -723,6 +766,7 @@ def main():
     p_web = [C.c_void_p(web.data_ptr() + k * mp) for k in range(resident)]
     p_best = [C.c_void_p(best.data_ptr() + k * mp) if best is not None else C.c_void_p(0) for k in range(resident)]
     turn = [0]
+    last = [0]      # the resident batch the last step issued wrote (--dump-outputs)
 
     # Optional: the inputs are resident and complete, so consecutive steps may overlap
     # (step i on the plan's internal lane i & 1).  Every step still does all its work.
@@ -732,6 +776,7 @@ def main():
     def step(st=None, serial=False):
         k = turn[0]
         turn[0] = k + 1 if k + 1 < resident else 0
+        last[0] = k
         if serial or args.serial:
             check(lib.sm_run(plan._h, p_l[k], p_r[k], args.threshold, pairs, p_web[k], p_best[k], st or stream))
         else:       # inputs resident: no event to wait for; consecutive steps may overlap (include/stereo_hip.h)
@@ -768,6 +813,7 @@ def main():
             while n >= gsteps:
                 graph.replay()
                 n -= gsteps
+                last[0] = resident - 1      # (a graph is whole turns over the batches, captured from the first)
         for _ in range(n):
             step()
 
@@ -822,6 +868,15 @@ def main():
     shard.barrier()
     elapsed = shard.max_over_ranks(time.perf_counter() - t0, red_dev)
     web_timed = web.clone()     # the maps as the timed steps left them (checked below, outside the timed region)
+    # --dump-outputs: what the last timed step handed its caller, copied to the host before anything reuses the maps
+    last_outputs, dump_batch = None, last[0]
+    if args.dump_outputs:
+        sl = slice(dump_batch * pairs, (dump_batch + 1) * pairs)
+        last_outputs = {"web": web[sl].cpu().numpy()}
+        if best is not None:
+            last_outputs["best"] = best[sl].cpu().numpy()
+        if world > 1:
+            last_outputs = {f"{k}_rank{rank}": v for k, v in last_outputs.items()}
     if args.corrupt_map:
         web_timed[0, h // 2 + 3, 17] ^= 1
 
@@ -927,6 +982,11 @@ def main():
         del left, right, web, best
         torch.cuda.empty_cache()
         c4 = c4_leg(rank, world, dev, red_dev, args.steps, args.threshold, rehearsal, False)
+
+    dumped = None
+    if last_outputs is not None:
+        dumped = dump_outputs(args.dump_outputs, last_outputs, DUMP_LIMIT_BYTES // world)
+        del last_outputs
 
     if rank != 0:
         shard.finalize()
@@ -1040,6 +1100,9 @@ def main():
         out["e2e"] = e2e
     if c4 is not None:
         out["c4"] = c4
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "step": "the last timed step",
+                                 "resident_batch": dump_batch, "arrays": dumped}
     if c4 is None:
         plan.close()
         del left, right, web

@@ -79,7 +79,7 @@ def main():
         print(name, {k: v.shape for k, v in keep.items() if k in ("left", "web-1")})
 
 
-if __name__ == "__main__" and "--big" not in sys.argv:
+if __name__ == "__main__" and "--big" not in sys.argv and "--pinned" not in sys.argv:
     main()
 
 
@@ -118,3 +118,74 @@ def main_big():
 
 if __name__ == "__main__" and "--big" in sys.argv:
     main_big()
+
+
+# ---------------------------------------------------------------------------
+# what the compiled reference made of the cases tests/test_oracle.py and tests/test_cli_cpu.py pin
+# the checker and the command-line programs to, so that those tests need no reference at run time:
+#     python tests/golden/make_golden.py --pinned
+#   ref_pinned_cases.json    per case of test_oracle: SHA-256 / dtype / shape of every array the
+#                            reference dumps (all 30 shifts), or its exit status where it traps
+#   ref_240x135_{a,b}.png    the reference's own smallest test pair, the files as they are (data)
+#   ref_240x135_dumps.json   per debug program: the SHA-256 of each of the 96 PPMs its debug build
+#                            writes for that pair at (0.15, 7, 32, 10), and its stdout line
+# ---------------------------------------------------------------------------
+# (mode, w, h, square_width, kind, threshold): the parameters of test_oracle_matches_compiled_reference
+PINNED_CASES = [(mode, *c) for mode in ("toroidal", "ghost") for c in (
+    (72, 41, 7, "scene", 0.15), (41, 72, 11, "noise", 0.5), (30, 30, 30, "scene", 0.0),
+    (64, 32, 0, "scene", 1.0), (45, 52, 1, "scene", 0.15))]
+CLI_ARGS = ("a.png", "b.png", "0.15", "7", "32", "10")
+
+
+def pinned_key(mode, w, h, sw, kind, thr):
+    return f"{mode}:{w}x{h}:sw{sw}:{kind}:thr{thr}"
+
+
+def array_record(a):
+    import hashlib
+    a = np.ascontiguousarray(a)
+    return {"sha256": hashlib.sha256(a.tobytes()).hexdigest(), "dtype": str(a.dtype), "shape": list(a.shape)}
+
+
+def main_pinned():
+    import hashlib
+    import json
+    import os
+    import shutil
+    import subprocess
+    import tempfile
+    if not oracle.ref_available():
+        sys.exit("oracle/_ref is missing: run `make -C oracle ref` where /root/reference exists")
+    out_dir = Path(__file__).resolve().parent
+    cases = {}
+    for mode, w, h, sw, kind, thr in PINNED_CASES:
+        left, right = make_pair(w, h, 30, seed=w * 131 + h, kind=kind)
+        ref = oracle.run_reference(left, right, thr, sw, 6, 3, mode, allow_sigfpe=True)
+        arrays = {k: array_record(v) for k, v in ref.items() if isinstance(v, np.ndarray)} if ref["returncode"] == 0 else {}
+        cases[pinned_key(mode, w, h, sw, kind, thr)] = {"returncode": ref["returncode"], "arrays": arrays}
+    # all scores equal: the reference traps on the zero contour interval after writing web and score_best
+    left, right = make_pair(40, 30, 30, kind="constant")
+    ref = oracle.run_reference(left, right, 0.15, 5, 0, 10, "toroidal",
+                               keep=lambda s: s in ("web-1", "score_best-0"), allow_sigfpe=True)
+    cases["constant:40x30:sw5"] = {"returncode": ref["returncode"],
+                                   "arrays": {k: array_record(ref[k]) for k in ("web-1", "score_best-0")}}
+    (out_dir / "ref_pinned_cases.json").write_text(json.dumps(cases, indent=1, sort_keys=True) + "\n")
+
+    dumps = {}
+    for side in ("a", "b"):
+        shutil.copyfile(REF_PAIR / f"{side}.png", out_dir / f"ref_240x135_{side}.png")
+    for variant, subdir in (("stereomatch", "ser"), ("stereomatch-ghost", "sergh")):
+        with tempfile.TemporaryDirectory() as td:
+            for side in ("a", "b"):
+                shutil.copyfile(REF_PAIR / f"{side}.png", f"{td}/{side}.png")
+            os.mkdir(f"{td}/{subdir}")
+            p = subprocess.run([str(oracle.REF_DIR / f"{variant}-debug"), *CLI_ARGS], cwd=td,
+                               capture_output=True, text=True, check=True)
+            files = {f.name: hashlib.sha256(f.read_bytes()).hexdigest() for f in sorted(Path(td, subdir).iterdir())}
+        dumps[variant] = {"subdir": subdir, "args": list(CLI_ARGS), "stdout": p.stdout, "sha256": files}
+        print(variant, len(files), "files")
+    (out_dir / "ref_240x135_dumps.json").write_text(json.dumps(dumps, indent=1, sort_keys=True) + "\n")
+
+
+if __name__ == "__main__" and "--pinned" in sys.argv:
+    main_pinned()

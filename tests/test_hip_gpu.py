@@ -1752,3 +1752,32 @@ def test_bench_checks_what_it_timed(flags):
     assert p.returncode == 3, (p.returncode, p.stderr[-2000:])
     out = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][0]
     assert out["verified"] is False and "VERIFICATION FAILED" in p.stderr
+
+
+@pytest.mark.parametrize("steps", [7, 9])
+def test_bench_dumps_what_its_last_timed_step_computed(tmp_path, steps):
+    """--dump-outputs DIR: the `web` and `best` maps of the last timed step (7 steps: one graph of 4, then 3 host
+    launches; 9: one graph of 8, then 1), as float32 files holding exactly the CPU oracle's maps of that step's
+    seeded pair; the line says how many steps were timed and which resident batch the last one wrote."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, str(root / "bench.py"), "--config", "C1", "--steps", str(steps), "--warmup", "2",
+                        "--with-best", "--no-e2e", "--no-cost-modes", "--no-c2", "--no-cpu-baseline",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    out = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][0]
+    assert out["steps"] == steps and out["verified"] is True and out["graph_capture"] == "ok"
+    dumped = out["dumped_outputs"]
+    assert dumped["resident_batch"] == (steps - 1) % 4          # the default 4 resident batches, in turn
+    w, h, d, sw, mode = CONFIGS["C1"]
+    left, right = make_pair(w, h, d, seed=dumped["resident_batch"])
+    o = oracle.pipeline(left, right, 0.15, d, sw, mode=mode, step3=False)
+    for name, key in (("web", "web-1"), ("best", "score_best-0")):
+        a = np.load(tmp_path / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (1, h, w) and dumped["arrays"][name]["sampled"] is False
+        assert np.array_equal(a[0], o[key].astype(np.float32)), name

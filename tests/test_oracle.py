@@ -1,15 +1,32 @@
 """CPU tests of the checker itself: the C restatement against the golden
-vectors produced by the compiled reference, against the compiled reference
-directly (where oracle/_ref exists), and its two window-sum variants against
-each other."""
+vectors produced by the compiled reference, against everything the compiled
+reference dumped for further cases (SHA-256 digests, tests/golden/ref_pinned_cases.json),
+and its two window-sum variants against each other."""
+import json
+
 import numpy as np
 import pytest
 
 from stereomatching_amd.synth import make_pair
 from tests import oracle
-from tests.conftest import golden_cases, load_golden
+from tests.conftest import GOLDEN_DIR, golden_cases, load_golden, sha256_of
 
 PLANE_SHIFTS = (0, 1, 7, 29)
+
+
+def pinned_case(key):
+    """what the compiled reference made of one case (tests/golden/make_golden.py --pinned)"""
+    return json.loads((GOLDEN_DIR / "ref_pinned_cases.json").read_text())[key]
+
+
+def equals_record(a, rec):
+    """a holds exactly the values of the reference array the record describes (np.array_equal
+    against it: same shape, every value representable in its dtype, the same bytes in that dtype)"""
+    a = np.asarray(a)
+    if list(a.shape) != rec["shape"]:
+        return False
+    b = a.astype(rec["dtype"])
+    return bool(np.array_equal(b, a)) and sha256_of(b) == rec["sha256"]
 
 
 @pytest.mark.parametrize("name", golden_cases())
@@ -28,43 +45,39 @@ def test_oracle_matches_golden(name, faithful):
         assert np.array_equal(oracle.record_score(m, sa), z[f"scores-{d}"]), (name, d)
 
 
-@pytest.mark.skipif(not oracle.ref_available(), reason="oracle/_ref not built (no /root/reference)")
 @pytest.mark.parametrize("mode", ["toroidal", "ghost"])
 @pytest.mark.parametrize("w,h,sw,kind,thr", [
     (72, 41, 7, "scene", 0.15), (41, 72, 11, "noise", 0.5), (30, 30, 30, "scene", 0.0),
     (64, 32, 0, "scene", 1.0), (45, 52, 1, "scene", 0.15)])
 def test_oracle_matches_compiled_reference(mode, w, h, sw, kind, thr):
     left, right = make_pair(w, h, 30, seed=w * 131 + h, kind=kind)
-    try:
-        ref = oracle.run_reference(left, right, thr, sw, 6, 3, mode)
-    except RuntimeError as e:
+    ref = pinned_case(f"{mode}:{w}x{h}:sw{sw}:{kind}:thr{thr}")
+    if ref["returncode"] != 0:
         # SIGFPE: the reference divided by a zero contour interval; the
         # restatement must report the same condition
-        assert "exited -8" in str(e)
+        assert ref["returncode"] == -8
         with pytest.raises(ZeroDivisionError):
             oracle.pipeline(left, right, thr, 30, sw, 6, 3, mode, faithful=True)
         return
+    arrays = ref["arrays"]
     got = oracle.pipeline(left, right, thr, 30, sw, 6, 3, mode, faithful=True)
     for k, v in got.items():
-        assert np.array_equal(v, ref[k]), k
+        assert equals_record(v, arrays[k]), k
     for d in range(30):
         m = oracle.match_plane(got["edges-1"], got["edges-2"], d, mode)
-        assert np.array_equal(m, ref[f"matches-{d}"])
+        assert equals_record(m, arrays[f"matches-{d}"])
         sa = oracle.addup(m, sw, mode, True)
-        assert np.array_equal(sa, ref[f"score_all-{d}"])
-        assert np.array_equal(oracle.record_score(m, sa), ref[f"scores-{d}"])
+        assert equals_record(sa, arrays[f"score_all-{d}"])
+        assert equals_record(oracle.record_score(m, sa), arrays[f"scores-{d}"])
 
 
-@pytest.mark.skipif(not oracle.ref_available(), reason="oracle/_ref not built")
 def test_constant_image_ties_go_to_last_shift():
     # all scores equal -> the reference's second sweep leaves the LAST shift
-    left, right = make_pair(40, 30, 30, kind="constant")
-    ref = oracle.run_reference(left, right, 0.15, 5, 0, 10, "toroidal",
-                               keep=lambda s: s in ("web-1", "score_best-0"), allow_sigfpe=True)
+    ref = pinned_case("constant:40x30:sw5")
     assert ref["returncode"] == -8     # constant web -> zero contour interval -> SIGFPE
     best, web = oracle.hot_path(np.zeros((30, 40), np.uint8), np.zeros((30, 40), np.uint8), 30, 5)
-    assert np.array_equal(web, ref["web-1"]) and (web == 30).all()
-    assert np.array_equal(best, ref["score_best-0"]) and (best == 25).all()
+    assert equals_record(web, ref["arrays"]["web-1"]) and (web == 30).all()
+    assert equals_record(best, ref["arrays"]["score_best-0"]) and (best == 25).all()
 
 
 @pytest.mark.parametrize("mode", ["toroidal", "ghost"])
