@@ -318,6 +318,8 @@ int sm_run_after(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gra
  *     sm_plan_time_kernels(plan, 0) before the capture;
  *   - the first narrow result of a plan whose kernel needs the int32 staging map (an allocation):
  *     sm_plan_reserve_narrow before the capture.
+ * A bad argument (a NULL image or map, an unknown web_type, a narrow map too small for the shift count) is refused
+ * after those conditions, likewise before anything is captured, and leaves the capture valid.
  * A PIPELINED plan is captured with a protocol of its own: the lane of a call leaves `stream` at an event the
  * previous captured call recorded before it joined its own lane back, so consecutive calls still run side by side
  * inside the graph, every call joins at once (a capture may end after any call), and -- unlike outside a capture --

@@ -1366,6 +1366,22 @@ extern "C" int sm_run_typed(sm_plan *plan, const uint8_t *d_gray_left, const uin
     return run_on_lanes(plan, d_gray_left, d_gray_right, threshold, pairs, d_web, web_type, d_best, stream, nullptr);
 }
 
+// every argument sm_find_edges and sm_match_wta_typed would refuse, refused before a call that runs them on a lane (or
+// behind an event) waits for anything or moves the plan's state: a refusal after a lane's fork would leave a capture
+// unjoined (hipStreamEndCapture fails) and, outside a capture, the edges of a call that never matches queued on the lane
+static int check_run_args(const sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, double threshold,
+                          const void *d_web, int web_type, const char *me)
+{
+    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
+    if (!(threshold >= 0.0 && threshold <= 1.0)) return sm_fail(SM_ERR_ARG, "error: threshold must be between 0 and 1");
+    if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
+    if (web_type != SM_WEB_I32 && web_type != SM_WEB_U16 && web_type != SM_WEB_U8)
+        return sm_fail(SM_ERR_ARG, "%s: web_type %d is not SM_WEB_I32/U16/U8", me, web_type);
+    if ((web_type == SM_WEB_U8 && plan->num_shifts > 255) || (web_type == SM_WEB_U16 && plan->num_shifts > 65535))
+        return sm_fail(SM_ERR_ARG, "%s: %d shifts do not fit the requested web type", me, plan->num_shifts);
+    return SM_OK;
+}
+
 // sm_run whose ONLY input dependency is an event (DESIGN.md 9.4 of round 4; replaces the synchronous upload in front of
 // every call, src/stereo.cu:402-403): the call is free to overlap with the one before it, and the plan takes the two
 // lanes by itself where that pays -- a match launch that does not fill the chip twice over (fewer than 2 x 1024 waves:
@@ -1381,6 +1397,7 @@ extern "C" int sm_run_after(sm_plan *plan, const uint8_t *d_gray_left, const uin
     // C5: a 158 us match launch beside 15 us of edges -- two calls sharing the chip cost more than that: 0.1782 against 0.1755 ms
     // per step, where C3 gains 2.6 % and C1 / C2 9-19 %: profiles/r05/bench_all_configs.txt)
     if (!plan->pipelined && (waves >= 2 * 1024 || plan->num_shifts > 128)) {
+        SM_TRY(check_run_args(plan, d_gray_left, d_gray_right, threshold, d_web, web_type, "sm_run_after"));
         SM_TRY(use_device(plan->device));
         if (inputs_ready_event) SM_HIP(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)inputs_ready_event, 0));
         SM_TRY(sm_find_edges(plan, d_gray_left, d_gray_right, threshold, pairs, nullptr, nullptr, stream));
@@ -1407,8 +1424,25 @@ static int run_on_lanes(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t
     // waits for the call's release event: work the caller puts on it afterwards sees the results.
     SM_TRY(check_plan_pairs(plan, pairs, "sm_run"));
     SM_TRY(use_device(plan->device));
+    hipStream_t user = (hipStream_t)stream;
+    unsigned long long cap_id = 0;
+    const bool capturing = stream_capturing(user, &cap_id);
+    if (capturing) {
+        // what cannot be captured is refused first (and, as every bad argument below, before the lane leaves `stream`:
+        // an error must not leave the capture unjoined)
+        if (!(plan->tab_valid && memcmp(&plan->tab_threshold, &threshold, sizeof threshold) == 0))
+            return sm_fail(SM_ERR_ARG, "sm_run: the decision tables of threshold %g are not prepared and the stream is capturing: "
+                           "call sm_plan_prepare_threshold(plan, threshold, stream) before the capture begins", threshold);
+        if (plan->timing_n < plan->timing_cap)
+            return sm_fail(SM_ERR_ARG, "sm_run: kernel timing is armed (sm_plan_time_kernels) and the stream is capturing: "
+                           "disarm with sm_plan_time_kernels(plan, 0) before the capture begins");
+        if (web_type != SM_WEB_I32 && plan->kernel != SM_KERNEL_BS && !plan->d_web_tmp)
+            return sm_fail(SM_ERR_ARG, "sm_run: the int32 staging map of narrow results is not allocated and the stream is "
+                           "capturing: call sm_plan_reserve_narrow(plan) first");
+    }
+    SM_TRY(check_run_args(plan, d_gray_left, d_gray_right, threshold, d_web, web_type, "sm_run"));
     const int b = plan->cur ^ 1;
-    hipStream_t lane = plan->lane[b], user = (hipStream_t)stream;
+    hipStream_t lane = plan->lane[b];
     const unsigned q = plan->seq + 1;
     // what two calls in flight could share: the threshold tables (rebuilt when the threshold
     // changes), the one int32 staging map of the kernels without a narrow store path, and result
@@ -1423,8 +1457,7 @@ static int run_on_lanes(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t
         for (int j = 0; j < 2; j++)
             if (lo[i] < plan->out_hi[j] && plan->out_lo[j] < hi[i]) shared = true;
 
-    unsigned long long cap_id = 0;
-    if (stream_capturing(user, &cap_id)) {
+    if (capturing) {
         // INSIDE A STREAM CAPTURE every operation must descend from the capturing stream and join it again, and no
         // event recorded outside the capture may be waited for (hipErrorStreamCaptureIsolation -- what round 4's
         // attempt ran into: its lanes waited for the release events of calls made before the capture began;
@@ -1432,16 +1465,7 @@ static int run_on_lanes(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t
         // which the PREVIOUS captured call recorded before it joined its own lane back -- so call q depends on
         // everything up to call q - 2 and runs beside call q - 1 in the graph, as outside a capture -- and every
         // call joins its lane back at once (`stream` waits for its release event), so the capture can end anywhere.
-        // (what cannot be captured is refused BEFORE the lane leaves `stream`: an error must not leave the capture unjoined)
-        if (!(plan->tab_valid && memcmp(&plan->tab_threshold, &threshold, sizeof threshold) == 0))
-            return sm_fail(SM_ERR_ARG, "sm_run: the decision tables of threshold %g are not prepared and the stream is capturing: "
-                           "call sm_plan_prepare_threshold(plan, threshold, stream) before the capture begins", threshold);
-        if (plan->timing_n < plan->timing_cap)
-            return sm_fail(SM_ERR_ARG, "sm_run: kernel timing is armed (sm_plan_time_kernels) and the stream is capturing: "
-                           "disarm with sm_plan_time_kernels(plan, 0) before the capture begins");
-        if (web_type != SM_WEB_I32 && plan->kernel != SM_KERNEL_BS && !plan->d_web_tmp)
-            return sm_fail(SM_ERR_ARG, "sm_run: the int32 staging map of narrow results is not allocated and the stream is "
-                           "capturing: call sm_plan_reserve_narrow(plan) first");
+        // (what cannot be captured, and every bad argument, was refused above, before the lane leaves `stream`)
         const bool first = !plan->cap_live || plan->cap_id != cap_id;
         if (first) {
             plan->cap_live = 1;

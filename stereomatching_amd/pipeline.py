@@ -58,6 +58,8 @@ class StereoPlan:
                                     self.square_width, self.border, self.max_pairs,
                                     C.byref(opts) if opts is not None else None, C.byref(self._h)))
         self._dev = torch.device("cuda", self.device)
+        self._pipelined = 0
+        self._side = None           # where result maps of calls that take the lanes are allocated (_lane_out)
 
     def close(self):
         if self._h:
@@ -94,8 +96,10 @@ class StereoPlan:
         """Let consecutive run() calls overlap (two internal lanes: edges of call i+1 beside
         the match of call i, the head of match i+1 in the tail of match i; give consecutive
         calls their own result maps).  With True the inputs given to run() must be complete in
-        memory at call time; with 2 they may still be in flight on the current stream."""
+        memory at call time; with 2 they may still be in flight on the current stream.  Inside
+        a stream capture, run() on a pipelined plan needs web= (and best=) maps of your own."""
         check(lib.sm_plan_set_pipelined(self._h, int(enabled)))
+        self._pipelined = 2 if enabled == 2 else int(bool(enabled))
 
     def prepare_threshold(self, threshold: float = DEFAULT_THRESHOLD):
         """Threshold-only set-up of find_all_edges (it does this itself on first use)."""
@@ -146,6 +150,35 @@ class StereoPlan:
     def _new(self, pairs, dtype):
         return torch.empty((pairs, self.height, self.width), dtype=dtype, device=self._dev)
 
+    def _lane_out(self, t, pairs, name, dtype=torch.int32):
+        """_out() for a call that may run on the plan's lanes (run_after, run on a pipelined plan).  Such a call is
+        not ordered behind work already queued on the current stream, so a map from that stream's pool could be a
+        block freed while a consumer of an earlier map is still pending there, and the lane would overwrite it
+        first.  Maps of our own come from a private stream's pool instead, marked used by the current stream: the
+        allocator hands the block out again only once the current stream's work at the time of the free is done.
+        (Inside a capture there are none: _refuse_unowned_maps.)"""
+        if t is not None:
+            return self._out(t, pairs, name, dtype)
+        if self._side is None:
+            self._side = torch.cuda.Stream(self._dev)
+        user = torch.cuda.current_stream(self._dev)
+        with torch.cuda.stream(self._side):
+            t = self._new(pairs, dtype)
+        t.record_stream(user)
+        return t
+
+    def _refuse_unowned_maps(self, name, launch):
+        """A call that takes the lanes inside a stream capture, without a map of the caller's for `name`: the lanes
+        fork from the capturing stream where the PREVIOUS call ended, so nothing captured between two calls orders the
+        second one, and a block freed in the capture could be handed to it while a consumer of the block is pending.
+        `launch` makes the call with a NULL web map, which the library refuses before anything is captured -- after
+        what cannot be captured at all (its message names the remedy, and is the one raised).  Always raises."""
+        rc = launch()
+        if rc != capi.SM_OK and "d_web is NULL" not in lib.sm_last_error().decode(errors="replace"):
+            check(rc)
+        raise ValueError(f"{name}=None inside a stream capture: a call that takes the plan's lanes cannot be ordered "
+                         f"behind the consumers of a map allocated there -- pass {name}= a map of your own")
+
     # ---- step 1 ------------------------------------------------------------
     def find_all_edges(self, left, right, threshold=DEFAULT_THRESHOLD, want_edges=True):
         """find_all_edges x2 (src/stereo.cu:27-92,:312-313).  uint8 gray in; fills the
@@ -183,8 +216,14 @@ class StereoPlan:
         left = self._images(left, torch.uint8, "left")
         right = self._images(right, torch.uint8, "right")
         pairs = left.shape[0]
-        web = self._out(web, pairs, "web", web_dtype)
-        best = self._out(best, pairs, "best") if want_best else None
+        if self._pipelined and (web is None or (want_best and best is None)) and \
+                torch.cuda.is_current_stream_capturing():
+            self._refuse_unowned_maps("web" if web is None else "best", lambda: lib.sm_run_typed(
+                self._h, _ptr(left), _ptr(right), float(threshold), pairs, _ptr(None), WEB_TYPES[web_dtype], _ptr(None),
+                self._stream()))
+        out = self._lane_out if self._pipelined else self._out
+        web = out(web, pairs, "web", web_dtype)
+        best = out(best, pairs, "best") if want_best else None
         if web_dtype != torch.int32 and not getattr(self, "_narrow_ready", False) and \
                 not torch.cuda.is_current_stream_capturing():
             self.reserve_narrow()       # (inside a capture the library says what to call first)
@@ -194,17 +233,27 @@ class StereoPlan:
 
     def run_after(self, left, right, threshold=DEFAULT_THRESHOLD, inputs_ready=None, want_best=False, web=None,
                   best=None, web_dtype=torch.int32):
-        """run() whose only input dependency is `inputs_ready` (a torch.cuda.Event or None = complete now): consecutive
-        calls may overlap, and on launches that cannot fill the chip twice over the plan lets them (sm_run_after)."""
+        """run() whose only input dependency is `inputs_ready`: consecutive calls may overlap, and on launches that
+        cannot fill the chip twice over the plan lets them (sm_run_after).
+
+        inputs_ready is a torch.cuda.Event recorded behind whatever produces `left` and `right`, or None: the images
+        are complete in memory NOW.  None does not mean "queued on the current stream": the call is not ordered
+        behind that stream's earlier work (that order would also put it behind the previous call, and take away
+        the overlap this call exists for).  Inputs still in flight need an event here, or a plan run with
+        set_pipelined(2) instead.  Inside a stream capture pass web= (and best=) maps of your own."""
         left = self._images(left, torch.uint8, "left")
         right = self._images(right, torch.uint8, "right")
         pairs = left.shape[0]
-        web = self._out(web, pairs, "web", web_dtype)
-        best = self._out(best, pairs, "best") if want_best else None
+        ev = C.c_void_p(inputs_ready.cuda_event) if inputs_ready is not None else C.c_void_p(0)
+        if (web is None or (want_best and best is None)) and torch.cuda.is_current_stream_capturing():
+            self._refuse_unowned_maps("web" if web is None else "best", lambda: lib.sm_run_after(
+                self._h, _ptr(left), _ptr(right), float(threshold), pairs, _ptr(None), WEB_TYPES[web_dtype], _ptr(None),
+                self._stream(), ev))
+        web = self._lane_out(web, pairs, "web", web_dtype)
+        best = self._lane_out(best, pairs, "best") if want_best else None
         if web_dtype != torch.int32 and not getattr(self, "_narrow_ready", False) and \
                 not torch.cuda.is_current_stream_capturing():
             self.reserve_narrow()
-        ev = C.c_void_p(inputs_ready.cuda_event) if inputs_ready is not None else C.c_void_p(0)
         check(lib.sm_run_after(self._h, _ptr(left), _ptr(right), float(threshold), pairs, _ptr(web),
                                WEB_TYPES[web_dtype], _ptr(best if want_best else None), self._stream(), ev))
         return web, (best if want_best else None)
