@@ -371,6 +371,43 @@ int sm_debug_edge_table(int device, double threshold, uint8_t *d_table, void *st
 int sm_debug_edge_table_fast(sm_plan *plan, double threshold, uint8_t *d_table,
                              int *not_threshold_form, void *stream);
 
+/* ---- left-right consistency check ---------------------------------------- *
+ * New work (the reference matches one way only: each LEFT pixel's winning shift, src/stereo.cu:211-225).
+ * The check marks the left pixels whose match does not point back to them with 0 -- the value
+ * fill_web_holes (src/stereo.cu:235-256, sm_fill_web_holes, sm_step3's staged route) fills, and one the
+ * reference's matcher never produces.  Definition (oracle/stereo_oracle.c notation):
+ *   web_right = mirror(smo_hot_path(mirror(eR), mirror(eL))), mirror(a)(x) = a(W-1-x), and likewise
+ *   best_right: web_right(u,y) = s' means right pixel u matched left pixel u - (s'-1);
+ *   left pixel (x,y) with s = web(x,y) matched right pixel u = x + s - 1 (toroidal: mod W; ghost: u >= W
+ *   is the halo, and the pixel is rejected); it is kept iff |web_right(u,y) - s| <= max_diff, and the
+ *   checked map holds s where kept, 0 where rejected.
+ * The maps given to sm_lr_check come from the same plan and pairs (every value in 1..num_shifts); other
+ * values get what the formula gives (ghost: u outside 0..W-1 is rejected) and no read outside a row.
+ * Narrow maps and the SAD / SSD cost mode have no consistency check.  The workspace (mirrored packed
+ * images and one mirrored-order map per pair) is allocated by sm_plan_reserve_lr or, without it, by the
+ * first call that needs it (a hipMalloc, which synchronises the device).  All calls run in `stream`
+ * order; on a pipelined plan (sm_plan_set_pipelined, sm_run_after) `stream` first waits for every
+ * earlier call on the lanes, and the next call on the lanes waits for this one.  STREAM CAPTURE: as
+ * sm_run, once sm_plan_reserve_lr (and, for sm_run_lr, sm_plan_prepare_threshold) has been called;
+ * before, the call is refused with SM_ERR_ARG, a message naming the remedy, and the capture valid.     */
+/* adds: the right-reference map (and, d_best_right non-NULL, its winning scores) for the edges last given to
+ * sm_find_edges / sm_load_edges, in natural order -- the plan's match launch over mirrored packed images */
+int sm_match_wta_right(sm_plan *plan, int pairs, int32_t *d_web_right, int32_t *d_best_right, void *stream);
+/* adds: the check of d_web against d_web_right (both natural order) with tolerance max_diff >= 0 into
+ * d_web_out, which may equal d_web (in place) and must not overlap d_web_right; d_rejected: NULL or one
+ * int32 per pair, the number of rejected pixels                                                          */
+int sm_lr_check(sm_plan *plan, const int32_t *d_web, const int32_t *d_web_right, int max_diff,
+                int pairs, int32_t *d_web_out, int32_t *d_rejected, void *stream);
+/* adds: edges (as sm_find_edges: they stay loaded) + left match + right match + check in one call; d_web
+ * receives the checked map (0 = rejected), d_best the left match's scores; d_best / d_web_right (the
+ * right-reference map, natural order) / d_rejected may be NULL                                          */
+int sm_run_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, double threshold,
+              int pairs, int max_diff, int32_t *d_web, int32_t *d_best, int32_t *d_web_right,
+              int32_t *d_rejected, void *stream);
+/* adds: allocates the mirrored packed images and the mirrored-order map of the calls above (counted in
+ * sm_plan_workspace_bytes from then on); a plan that never calls them allocates neither.  Idempotent.  */
+int sm_plan_reserve_lr(sm_plan *plan);
+
 /* ---- step 3 -------------------------------------------------------------- *
  * fill_web_holes (src/stereo.cu:235-256): `times` Jacobi sweeps over pixels
  * that are 0, ping-ponging d_web and d_tmp exactly as the reference swaps

@@ -116,6 +116,10 @@ _SIGNATURES = {
     "sm_draw_contour_map": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp]),
     "sm_plan_status": (_int, [_vp, _vp]),
     "sm_step3": (_int, [_vp, _vp, _vp, _int, _int, _int, _vp, _vp, _intp, _vp]),
+    "sm_match_wta_right": (_int, [_vp, _int, _vp, _vp, _vp]),
+    "sm_lr_check": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "sm_run_lr": (_int, [_vp, _vp, _vp, _dbl, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    "sm_plan_reserve_lr": (_int, [_vp]),
 }
 
 

@@ -706,7 +706,7 @@ static int use_device(int device)
     SM_HIP(hipSetDevice(device));
     return SM_OK;
 }
-#define SM_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
+int sm_use_device(int device) { return use_device(device); }
 
 extern "C" int sm_device_count(int *count)
 {
@@ -979,6 +979,7 @@ extern "C" void sm_plan_destroy(sm_plan *plan)
     (void)hipEventDestroy(plan->ev_inputs);
     for (int b = 0; b < 2; b++) (void)hipEventDestroy(plan->ev_fork[b]);
     if (plan->d_web_tmp) (void)hipFree(plan->d_web_tmp);
+    sm_lr_free(plan);
     (void)hipFree(plan->d_flags);
     (void)hipFree(plan->d_edge_tab);
     (void)hipHostFree(plan->h_flags);
@@ -1026,7 +1027,7 @@ extern "C" size_t sm_plan_workspace_bytes(const sm_plan *plan)
 {
     if (!plan) return 0;
     const size_t staging = plan->d_web_tmp ? (size_t)plan->max_pairs * plan->width * plan->height * sizeof(i32) : 0;
-    return 2 * plan->ext_bytes + 4 * sizeof(i32) + 768 * sizeof(u32) + staging;
+    return 2 * plan->ext_bytes + 4 * sizeof(i32) + 768 * sizeof(u32) + staging + sm_lr_workspace_bytes(plan);
 }
 
 // synchronise `st` and return the plan's flags as they were at that point; flags in
@@ -1050,6 +1051,7 @@ static bool stream_capturing(hipStream_t st, unsigned long long *id = nullptr)
     if (id) *id = cid;
     return cs != hipStreamCaptureStatusNone;
 }
+bool sm_stream_capturing(hipStream_t st) { return stream_capturing(st); }
 
 static int check_plan_pairs(const sm_plan *plan, int pairs, const char *who)
 {

@@ -106,6 +106,10 @@ struct sm_plan {
     int tab_valid;
     int tab_ok;          // tables verified to be of threshold form
     int pairs_loaded;    // batch size of the edges currently in d_ext
+    // left-right consistency check (sm_lr.hip): NOT allocated with the plan, but by sm_plan_reserve_lr
+    // or the first call that needs them; part of the workspace from then on
+    u32 *d_ext_lr;       // mirrored packed images, d_ext's layout: side 0 = mirror(right), side 1 = mirror(left)
+    i32 *d_web_lr;       // right-reference map of sm_run_lr in mirrored order: max_pairs * W * H
     char describe[512];
 };
 
@@ -141,6 +145,7 @@ int sm_fail(int code, const char *fmt, ...);
                            "%s failed: %s (%s:%d)", #call,                    \
                            hipGetErrorString(e_), __FILE__, __LINE__);        \
     } while (0)
+#define SM_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 #define SM_LAUNCH_CHECK(name)                                                 \
     do {                                                                      \
         hipError_t e_ = hipGetLastError();                                    \
@@ -148,6 +153,12 @@ int sm_fail(int code, const char *fmt, ...);
             return sm_fail(SM_ERR_HIP, "launch of %s failed: %s", name,       \
                            hipGetErrorString(e_));                            \
     } while (0)
+
+// sm_api.hip
+int sm_use_device(int device);                    // hipSetDevice, failure as SM_ERR_HIP
+bool sm_stream_capturing(hipStream_t st);         // is `st` recording into a graph?
+size_t sm_lr_workspace_bytes(const sm_plan *plan);    // sm_lr.hip: 0 until sm_plan_reserve_lr
+void sm_lr_free(sm_plan *plan);                       // sm_lr.hip: sm_plan_destroy
 
 // sm_match_bs.hip (bit-sliced kernel; nullptr if not built for this window)
 const void *sm_bs_kernel_ptr(int n, int ds, bool fulld, bool ghost, bool cap2, bool duo = false);

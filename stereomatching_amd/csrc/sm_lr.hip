@@ -1,0 +1,380 @@
+// sm_lr.hip -- left-right consistency check: the right-reference map and the check that hands
+// the rejected pixels of the left map to hole filling (include/stereo_hip.h).
+//
+// The right-reference map is the plan's own match launch run over MIRRORED packed images:
+//     web_right = mirror(hot_path(mirror(eR), mirror(eL)))
+// (mirror(a)(x) = a(W-1-x)).  Both borders are symmetric under mirroring -- the ghost border's zero
+// halo and "no taps outside the image", the centre-match mask, last-shift-wins ties -- so every
+// kernel variant the plan can choose gets a right-reference mode without a new instantiation.
+// The new kernels: k_mirror_ext (packed images -> mirrored packed images, a row of words in
+// reverse order, each bit-reversed) and k_lr_check (one pass over the left map, bandwidth bound).
+
+#include "sm_internal.h"
+
+#include <string.h>
+
+#include <algorithm>
+
+// ---------------------------------------------------------------------------
+// kernels
+// ---------------------------------------------------------------------------
+
+__device__ __forceinline__ int lr_pos_mod(int v, int m)
+{
+    int r = v % m;
+    return r < 0 ? r + m : r;
+}
+
+// Mirrored packed images from the plan's packed images (layout in sm_internal.h), one lane per
+// output word.  Output side 0 (the reference image of the right-reference pass) is mirror(right),
+// side 1 is mirror(left); each keeps the row extents the edge kernels give the side it stands in
+// for (edge_words_l / _r: the words beyond stay zero, as in the plan's own images).
+//
+// Output bit b of word k is image column x = 32k + b - pad_l and takes source column W-1-x.  Where
+// all 32 columns of the word lie inside the image, those are 32 consecutive source bits, read from
+// two neighbouring words (realigned by W mod 32 -- pad_l is a multiple of 32 -- with v_alignbit_b32)
+// and reversed with v_bfrev_b32.  The few words that reach into the halo apply the border bit by
+// bit: the toroidal halo wraps (mod W), the ghost halo is zero.  Rows need nothing: the halo rows
+// of the source are already the border's, and mirroring is horizontal.  Every source read is of a
+// column in [0, W), i.e. bit pad_l .. pad_l + W - 1 of the row, inside edge_words_l words.
+__global__ __launch_bounds__(64) void k_mirror_ext(const u32 *__restrict__ src, u32 *__restrict__ dst,
+                                                    MatchGeom g, int ghost)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    const int e = blockIdx.y;
+    const int side = blockIdx.z & 1, pair = blockIdx.z >> 1;
+    if (k >= (side ? g.edge_words_r : g.edge_words_l)) return;
+    const u32 *s = src + ((long long)(2 * pair + (side ^ 1)) * g.ext_rows + e) * g.ext_words;
+    u32 *d = dst + ((long long)(2 * pair + side) * g.ext_rows + e) * g.ext_words;
+    const int W = g.w;
+    const int x0 = 32 * k - g.pad_l;
+    u32 v = 0;
+    if (x0 >= 0 && x0 + 31 < W) {
+        const int p = W - 32 - x0 + g.pad_l;           // source bit of output bit 31
+        const int lo = p >> 5, sh = p & 31;
+        const u32 a = s[lo];
+        const u32 b = sh ? s[lo + 1] : 0u;             // (p + 31 <= pad_l + W - 1: inside the row)
+        v = __builtin_bitreverse32(__builtin_amdgcn_alignbit(b, a, sh));
+    } else {
+        // source column of bit 0, then one column to the left per bit (toroidal: wrapping round; ghost: columns
+        // outside the image are 0): no division per bit, and 32 independent loads
+        int xs = ghost ? W - 1 - x0 : lr_pos_mod(W - 1 - x0, W);
+#pragma unroll
+        for (int b = 0; b < 32; b++) {
+            const bool in = !ghost || (xs >= 0 && xs < W);
+            const int q = (in ? xs : 0) + g.pad_l;
+            v |= (in ? (s[q >> 5] >> (q & 31)) & 1u : 0u) << b;
+            xs = (!ghost && xs == 0) ? W - 1 : xs - 1;
+        }
+    }
+    d[k] = v;
+}
+
+// Is left pixel x of a row, whose map value is s, consistent with the right-reference row `rrow`?
+// u = x + s - 1 is the right pixel it matched: toroidal u mod W; ghost: past the row (the halo, or
+// before column 0 for values no match produces) = rejected.  MIRRORED: rrow is in mirrored order.
+template <bool MIRRORED>
+__device__ __forceinline__ bool lr_keep(const i32 *rrow, int x, i32 s, int W, int ghost, int max_diff)
+{
+    long long u = (long long)x + s - 1;
+    if (u < 0 || u >= W) {
+        if (ghost) return false;
+        u %= W;
+        if (u < 0) u += W;
+    }
+    const int ui = (int)u;
+    const long long diff = (long long)rrow[MIRRORED ? W - 1 - ui : ui] - s;
+    return (diff < 0 ? -diff : diff) <= max_diff;
+}
+
+// The workgroup's rejections, added to the pair's count with ONE atomic: a sum across each wave (DPP / shuffles),
+// then across the four waves in LDS.  All atomics of a pair go to one address, where they serialise: one per
+// wave of four pixels per lane cost ~11 ns each, 0.35 ms at 4K (32 K waves) -- hence workgroups that stride
+// over the map (SM_LR_BLOCKS per pair) and one atomic per workgroup.
+#define SM_LR_BLOCKS 1024
+__device__ __forceinline__ void lr_count(i32 *rejected, int cnt)
+{
+    __shared__ int part[4];
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int total = part[0] + part[1] + part[2] + part[3];
+        if (total) atomicAdd(rejected, total);
+    }
+}
+
+// The check, one pass over the left map: web (in place allowed: out == web, so neither is
+// __restrict__), the gather from the right-reference row, out, and -- MIRRORED, right_out
+// non-NULL -- the right-reference map in natural order.  Grid: x strides over the pixels of one
+// pair, four per lane (VEC: W % 4 == 0 and 16-byte aligned maps: one int4 per map) or one; y = pair.
+template <bool MIRRORED, bool VEC>
+__global__ __launch_bounds__(256) void k_lr_check(const i32 *web, const i32 *right, i32 *out, i32 *right_out,
+                                                  i32 *rejected, int W, unsigned npx, int max_diff, int ghost)
+{
+    const size_t base = (size_t)blockIdx.y * npx;
+    constexpr int P = VEC ? 4 : 1;
+    const unsigned lanes = npx / P;
+    int cnt = 0;
+    for (unsigned t = blockIdx.x * 256u + threadIdx.x; t < lanes; t += gridDim.x * 256u) {
+        const unsigned p = t * P;
+        const unsigned row = p / (unsigned)W;
+        const int x = (int)(p - row * (unsigned)W);
+        const i32 *rrow = right + base + (size_t)row * W;
+        if (VEC) {
+            const int4 s = *(const int4 *)(web + base + p);
+            const bool k0 = lr_keep<MIRRORED>(rrow, x, s.x, W, ghost, max_diff);
+            const bool k1 = lr_keep<MIRRORED>(rrow, x + 1, s.y, W, ghost, max_diff);
+            const bool k2 = lr_keep<MIRRORED>(rrow, x + 2, s.z, W, ghost, max_diff);
+            const bool k3 = lr_keep<MIRRORED>(rrow, x + 3, s.w, W, ghost, max_diff);
+            *(int4 *)(out + base + p) = make_int4(k0 ? s.x : 0, k1 ? s.y : 0, k2 ? s.z : 0, k3 ? s.w : 0);
+            cnt += 4 - (int)k0 - (int)k1 - (int)k2 - (int)k3;
+            if (MIRRORED && right_out) {
+                const int4 r = *(const int4 *)(rrow + (W - 4 - x));
+                *(int4 *)(right_out + base + p) = make_int4(r.w, r.z, r.y, r.x);
+            }
+        } else {
+            const i32 s = web[base + p];
+            const bool keep = lr_keep<MIRRORED>(rrow, x, s, W, ghost, max_diff);
+            out[base + p] = keep ? s : 0;
+            cnt += !keep;
+            if (MIRRORED && right_out) right_out[base + p] = rrow[W - 1 - x];
+        }
+    }
+    if (rejected) lr_count(rejected + blockIdx.y, cnt);
+}
+
+// sm_match_wta_right: the match launch wrote both maps in mirrored order; reverse every row in place
+__global__ __launch_bounds__(256) void k_lr_unmirror(i32 *web, i32 *best, int W, unsigned npx, unsigned half_w,
+                                                     unsigned half_px)
+{
+    const unsigned t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= half_px) return;
+    const unsigned row = t / half_w;
+    const int x = (int)(t - row * half_w);
+    const size_t o = (size_t)blockIdx.y * npx + (size_t)row * W;
+    i32 *r = web + o;
+    const i32 a = r[x], b = r[W - 1 - x];
+    r[x] = b;
+    r[W - 1 - x] = a;
+    if (best) {
+        i32 *q = best + o;
+        const i32 c = q[x], d = q[W - 1 - x];
+        q[x] = d;
+        q[W - 1 - x] = c;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+
+static size_t lr_map_bytes(const sm_plan *plan)
+{
+    return (size_t)plan->max_pairs * plan->width * plan->height * sizeof(i32);
+}
+
+size_t sm_lr_workspace_bytes(const sm_plan *plan)
+{
+    return plan->d_ext_lr ? plan->ext_bytes + lr_map_bytes(plan) : 0;
+}
+
+void sm_lr_free(sm_plan *plan)
+{
+    if (plan->d_ext_lr) (void)hipFree(plan->d_ext_lr);
+    if (plan->d_web_lr) (void)hipFree(plan->d_web_lr);
+    plan->d_ext_lr = nullptr;
+    plan->d_web_lr = nullptr;
+}
+
+// the mirrored packed images (zero-filled: the words beyond each side's row extent stay zero) and the
+// mirrored-order map
+static int reserve_lr(sm_plan *plan, const char *me)
+{
+    if (plan->d_ext_lr) return SM_OK;
+    hipError_t e = hipMalloc((void **)&plan->d_ext_lr, plan->ext_bytes);
+    if (e == hipSuccess) e = hipMemset(plan->d_ext_lr, 0, plan->ext_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&plan->d_web_lr, lr_map_bytes(plan));
+    if (e != hipSuccess) {
+        sm_lr_free(plan);
+        return sm_fail(e == hipErrorOutOfMemory ? SM_ERR_NOMEM : SM_ERR_HIP, "%s: %zu bytes for the mirrored images and "
+                       "map of the consistency check: %s", me, plan->ext_bytes + lr_map_bytes(plan), hipGetErrorString(e));
+    }
+    return SM_OK;
+}
+
+extern "C" int sm_plan_reserve_lr(sm_plan *plan)
+{
+    if (!plan) return sm_fail(SM_ERR_ARG, "sm_plan_reserve_lr: plan is NULL");
+    SM_TRY(sm_use_device(plan->device));
+    return reserve_lr(plan, "sm_plan_reserve_lr");
+}
+
+static int check_pairs(const sm_plan *plan, int pairs, const char *me)
+{
+    if (!plan) return sm_fail(SM_ERR_ARG, "%s: plan is NULL", me);
+    if (pairs < 1 || pairs > plan->max_pairs)
+        return sm_fail(SM_ERR_ARG, "%s: pairs %d outside 1..%d (max_pairs of the plan)", me, pairs, plan->max_pairs);
+    return SM_OK;
+}
+
+// the workspace, allocated here when sm_plan_reserve_lr was not called -- unless the stream is capturing
+static int need_lr(sm_plan *plan, hipStream_t st, const char *me)
+{
+    if (plan->d_ext_lr) return SM_OK;
+    if (sm_stream_capturing(st))
+        return sm_fail(SM_ERR_ARG, "%s: the workspace of the consistency check is not allocated and the stream is capturing "
+                       "(an allocation cannot be captured): call sm_plan_reserve_lr(plan) first", me);
+    return reserve_lr(plan, me);
+}
+
+// A call that reads or rewrites the packed images runs on `stream`; the pipelined calls before it may
+// still be running on the plan's lanes (sm_plan_set_pipelined, sm_run_after): `stream` waits for all of
+// them.  Inside a capture the captured calls have joined `stream` already (and events of eager calls
+// must not be waited for there).
+static int lr_fence_lanes(sm_plan *plan, hipStream_t st)
+{
+    if (sm_stream_capturing(st)) return SM_OK;
+    for (int i = 0; i < 4; i++)
+        if (plan->ev_free_set[i]) SM_HIP(hipStreamWaitEvent(st, plan->ev_free[i], 0));
+    return SM_OK;
+}
+
+// ... and the next pipelined call must not overtake it: as after any sequential launch, its lanes wait for
+// `stream` first (a captured one leaves `stream` after this call, not where the previous captured call ended)
+static void lr_release_lanes(sm_plan *plan)
+{
+    plan->unfenced = 1;
+    plan->cap_live = 0;
+}
+
+// one launch of the plan's match kernel over other packed images (the plan is not modified)
+static int lr_match(const sm_plan *plan, u32 *ext, int pairs, i32 *d_web, i32 *d_best, hipStream_t st)
+{
+    sm_plan view = *plan;
+    view.d_ext = ext;
+    MatchLaunch l;
+    l.g = plan->g;
+    if (((uintptr_t)d_web & 15) != 0 || ((uintptr_t)d_best & 15) != 0) l.g.vec_ok = 0;
+    l.g.web_bytes = 4;
+    l.ev_begin = l.ev_end = nullptr;
+    return sm_match_launch(&view, l, pairs, d_web, d_best, st);
+}
+
+static int lr_mirror(sm_plan *plan, int pairs, hipStream_t st)
+{
+    const MatchGeom &g = plan->g;
+    // one wave per row segment of 64 words (a row is 2 -- 4K, 128 shifts -- to ~70 words: wider workgroups idle)
+    const dim3 grid((g.edge_words_r + 63) / 64, g.ext_rows, pairs * 2), block(64);
+    hipLaunchKernelGGL(k_mirror_ext, grid, block, 0, st, plan->d_ext, plan->d_ext_lr, g, plan->border == SM_GHOST ? 1 : 0);
+    SM_LAUNCH_CHECK("k_mirror_ext");
+    return SM_OK;
+}
+
+static int lr_check_launch(const sm_plan *plan, bool mirrored, const i32 *web, const i32 *right, i32 *out,
+                           i32 *right_out, i32 *rejected, int max_diff, int pairs, hipStream_t st)
+{
+    const int W = plan->width;
+    const unsigned npx = (unsigned)W * plan->height;
+    const int ghost = plan->border == SM_GHOST;
+    if (rejected) SM_HIP(hipMemsetAsync(rejected, 0, (size_t)pairs * sizeof(i32), st));
+    const bool vec = W % 4 == 0 && (((uintptr_t)web | (uintptr_t)right | (uintptr_t)out | (uintptr_t)right_out) & 15) == 0;
+    const unsigned lanes = vec ? npx / 4 : npx;
+    const dim3 grid(std::min((lanes + 255) / 256, (unsigned)SM_LR_BLOCKS), pairs), block(256);
+#define SM_LR_GO(M, V) hipLaunchKernelGGL((k_lr_check<M, V>), grid, block, 0, st, web, right, out, right_out, rejected, \
+                                          W, npx, max_diff, ghost)
+    if (mirrored) { if (vec) SM_LR_GO(true, true); else SM_LR_GO(true, false); }
+    else          { if (vec) SM_LR_GO(false, true); else SM_LR_GO(false, false); }
+#undef SM_LR_GO
+    SM_LAUNCH_CHECK("k_lr_check");
+    return SM_OK;
+}
+
+// do [a, a + a_bytes) and [b, b + b_bytes) share a byte?  (b_bytes = 0: as many as a)
+static bool overlap(const void *a, const void *b, size_t a_bytes, size_t b_bytes = 0)
+{
+    return (uintptr_t)a < (uintptr_t)b + (b_bytes ? b_bytes : a_bytes) && (uintptr_t)b < (uintptr_t)a + a_bytes;
+}
+
+extern "C" int sm_match_wta_right(sm_plan *plan, int pairs, int32_t *d_web_right, int32_t *d_best_right, void *stream)
+{
+    const char *me = "sm_match_wta_right";
+    if (!d_web_right) return sm_fail(SM_ERR_ARG, "%s: d_web_right is NULL", me);
+    SM_TRY(check_pairs(plan, pairs, me));
+    if (pairs > plan->pairs_loaded)
+        return sm_fail(SM_ERR_ARG, "%s: %d pairs requested but edges of only %d are loaded "
+                       "(call sm_find_edges or sm_load_edges first)", me, pairs, plan->pairs_loaded);
+    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
+    if (d_best_right && overlap(d_web_right, d_best_right, map))
+        return sm_fail(SM_ERR_ARG, "%s: d_web_right and d_best_right overlap", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    SM_TRY(need_lr(plan, st, me));
+    SM_TRY(lr_fence_lanes(plan, st));
+    lr_release_lanes(plan);
+    SM_TRY(lr_mirror(plan, pairs, st));
+    // the maps come out in mirrored order, and are turned round in place
+    SM_TRY(lr_match(plan, plan->d_ext_lr, pairs, d_web_right, d_best_right, st));
+    const int W = plan->width;
+    const unsigned half_w = (unsigned)(W + 1) / 2, half_px = half_w * plan->height;
+    hipLaunchKernelGGL(k_lr_unmirror, dim3((half_px + 255) / 256, pairs), dim3(256), 0, st, d_web_right, d_best_right,
+                       W, (unsigned)W * plan->height, half_w, half_px);
+    SM_LAUNCH_CHECK("k_lr_unmirror");
+    return SM_OK;
+}
+
+extern "C" int sm_lr_check(sm_plan *plan, const int32_t *d_web, const int32_t *d_web_right, int max_diff,
+                           int pairs, int32_t *d_web_out, int32_t *d_rejected, void *stream)
+{
+    const char *me = "sm_lr_check";
+    if (!d_web || !d_web_right || !d_web_out) return sm_fail(SM_ERR_ARG, "%s: a map pointer is NULL", me);
+    if (max_diff < 0) return sm_fail(SM_ERR_ARG, "%s: max_diff %d is negative", me, max_diff);
+    SM_TRY(check_pairs(plan, pairs, me));
+    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
+    if (overlap(d_web_right, d_web_out, map))
+        return sm_fail(SM_ERR_ARG, "%s: d_web_right overlaps d_web_out (the check gathers from it while writing)", me);
+    if (d_web != d_web_out && overlap(d_web, d_web_out, map))
+        return sm_fail(SM_ERR_ARG, "%s: d_web_out overlaps d_web without being it", me);
+    const size_t counts = (size_t)pairs * sizeof(i32);
+    if (d_rejected && (overlap(d_rejected, d_web_out, counts, map) || overlap(d_rejected, d_web_right, counts, map) ||
+                       overlap(d_rejected, d_web, counts, map)))
+        return sm_fail(SM_ERR_ARG, "%s: d_rejected overlaps a map", me);
+    SM_TRY(sm_use_device(plan->device));
+    return lr_check_launch(plan, false, d_web, d_web_right, d_web_out, nullptr, d_rejected, max_diff, pairs,
+                           (hipStream_t)stream);
+}
+
+extern "C" int sm_run_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, double threshold,
+                         int pairs, int max_diff, int32_t *d_web, int32_t *d_best, int32_t *d_web_right,
+                         int32_t *d_rejected, void *stream)
+{
+    const char *me = "sm_run_lr";
+    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
+    if (!(threshold >= 0.0 && threshold <= 1.0)) return sm_fail(SM_ERR_ARG, "error: threshold must be between 0 and 1");
+    if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
+    if (max_diff < 0) return sm_fail(SM_ERR_ARG, "%s: max_diff %d is negative", me, max_diff);
+    SM_TRY(check_pairs(plan, pairs, me));
+    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
+    if ((d_best && overlap(d_best, d_web, map)) || (d_web_right && overlap(d_web_right, d_web, map)) ||
+        (d_best && d_web_right && overlap(d_best, d_web_right, map)))
+        return sm_fail(SM_ERR_ARG, "%s: result maps overlap", me);
+    const size_t counts = (size_t)pairs * sizeof(i32);
+    if (d_rejected && (overlap(d_rejected, d_web, counts, map) || (d_best && overlap(d_rejected, d_best, counts, map)) ||
+                       (d_web_right && overlap(d_rejected, d_web_right, counts, map))))
+        return sm_fail(SM_ERR_ARG, "%s: d_rejected overlaps a map", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (sm_stream_capturing(st) && !(plan->tab_valid && memcmp(&plan->tab_threshold, &threshold, sizeof threshold) == 0))
+        return sm_fail(SM_ERR_ARG, "%s: the decision tables of threshold %g are not prepared and the stream is capturing: "
+                       "call sm_plan_prepare_threshold(plan, threshold, stream) before the capture begins", me, threshold);
+    SM_TRY(need_lr(plan, st, me));
+    SM_TRY(lr_fence_lanes(plan, st));
+    lr_release_lanes(plan);
+    // edges into the plan's packed images (as sm_run; they stay loaded), the left match, the mirrored images,
+    // the right match into the mirrored-order map, and the check, which gathers from that map
+    SM_TRY(sm_find_edges(plan, d_gray_left, d_gray_right, threshold, pairs, nullptr, nullptr, stream));
+    SM_TRY(lr_match(plan, plan->d_ext, pairs, d_web, d_best, st));
+    SM_TRY(lr_mirror(plan, pairs, st));
+    SM_TRY(lr_match(plan, plan->d_ext_lr, pairs, plan->d_web_lr, nullptr, st));
+    return lr_check_launch(plan, true, d_web, plan->d_web_lr, d_web, d_web_right, d_rejected, max_diff, pairs, st);
+}

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -31,6 +32,14 @@ class AlgorithmParams:
     square_width: int = DEFAULT_SQUARE_WIDTH
     times: int = DEFAULT_TIMES
     lines_to_draw: int = DEFAULT_LINES
+
+
+class LRResult(NamedTuple):
+    """StereoPlan.run_lr: the checked map (0 = rejected), rejected pixels per pair, and the optional maps"""
+    web: torch.Tensor
+    rejected: torch.Tensor
+    web_right: Optional[torch.Tensor]
+    best: Optional[torch.Tensor]
 
 
 WEB_TYPES = {torch.int32: capi.SM_WEB_I32, torch.uint16: capi.SM_WEB_U16, torch.uint8: capi.SM_WEB_U8}
@@ -111,6 +120,11 @@ class StereoPlan:
         out of stream captures."""
         check(lib.sm_plan_reserve_narrow(self._h))
         self._narrow_ready = True
+
+    def reserve_lr(self):
+        """The workspace of the left-right consistency check (mirrored packed images, one mirrored-order map per
+        pair), allocated now: keeps the allocation out of timed paths and out of stream captures."""
+        check(lib.sm_plan_reserve_lr(self._h))
 
     def time_kernels(self, capacity: int, every: int = 1):
         """Bracket every `every`-th of the coming match launches (at most `capacity` of
@@ -258,6 +272,44 @@ class StereoPlan:
                                WEB_TYPES[web_dtype], _ptr(best if want_best else None), self._stream(), ev))
         return web, (best if want_best else None)
 
+    # ---- left-right consistency check ------------------------------------------
+    def match_wta_right(self, pairs=1, want_best=True, web_right=None, best_right=None):
+        """The right-reference map of the loaded edges (sm_match_wta_right) -> (web_right, best_right):
+        web_right(u, y) = s' means right pixel u matched left pixel u - (s' - 1)."""
+        web_right = self._out(web_right, pairs, "web_right")
+        best_right = self._out(best_right, pairs, "best_right") if want_best else None
+        check(lib.sm_match_wta_right(self._h, pairs, _ptr(web_right), _ptr(best_right), self._stream()))
+        return web_right, best_right
+
+    def lr_check(self, web, web_right, max_diff=0, out=None):
+        """Left-right consistency check (sm_lr_check) -> (checked web, rejected pixels per pair): a left pixel
+        whose right-reference map does not point back to it within max_diff becomes 0.  out=web checks in place."""
+        web = self._images(web, torch.int32, "web")
+        web_right = self._images(web_right, torch.int32, "web_right")
+        pairs = web.shape[0]
+        if web_right.shape[0] != pairs:
+            raise ValueError(f"web_right: {web_right.shape[0]} maps for {pairs} pairs")
+        out = self._out(out, pairs, "out")
+        rejected = torch.empty(pairs, dtype=torch.int32, device=self._dev)
+        check(lib.sm_lr_check(self._h, _ptr(web), _ptr(web_right), int(max_diff), pairs, _ptr(out), _ptr(rejected),
+                              self._stream()))
+        return out, rejected
+
+    def run_lr(self, left, right, threshold=DEFAULT_THRESHOLD, max_diff=0, want_right=False, want_best=False,
+               web=None, web_right=None, best=None) -> LRResult:
+        """Edges, left match, right match and check in one call (sm_run_lr) -> LRResult(web, rejected, web_right,
+        best); web is the checked map (0 = rejected)."""
+        left = self._images(left, torch.uint8, "left")
+        right = self._images(right, torch.uint8, "right")
+        pairs = left.shape[0]
+        web = self._out(web, pairs, "web")
+        web_right = self._out(web_right, pairs, "web_right") if want_right else None
+        best = self._out(best, pairs, "best") if want_best else None
+        rejected = torch.empty(pairs, dtype=torch.int32, device=self._dev)
+        check(lib.sm_run_lr(self._h, _ptr(left), _ptr(right), float(threshold), pairs, int(max_diff), _ptr(web),
+                            _ptr(best), _ptr(web_right), _ptr(rejected), self._stream()))
+        return LRResult(web, rejected, web_right, best)
+
     def cost_wta(self, left, right, cost="sad", want_best=True, web=None, best=None):
         """SAD / SSD cost mode on the uint8 images (parity unpinned: the reference has no
         such mode) -> (web, best): arg-min over the shifts, first shift wins."""
@@ -321,14 +373,22 @@ class StereoPlan:
         return (tmp if which.value else web), out, mm
 
     # ---- the whole of algorithm() --------------------------------------------
-    def algorithm(self, first, second, params: AlgorithmParams = AlgorithmParams(), step3=True):
+    def algorithm(self, first, second, params: AlgorithmParams = AlgorithmParams(), step3=True,
+                  lr_max_diff: int | None = None):
         """Stage order of src/stereo.cu:289-347; returns the images the reference dumps
-        (minus the per-shift planes: see debug_planes)."""
+        (minus the per-shift planes: see debug_planes).  lr_max_diff not None: web-1 is the
+        left-right checked map (0 where rejected: step 3 fills those pixels), and the result
+        adds the right-reference map ("web_right-1") and the rejected pixels per pair
+        ("lr_rejected")."""
         if params.square_width != self.square_width:
             raise ValueError("params.square_width differs from the plan's")
         el, er = self.find_all_edges(first, second, params.threshold)
         web1, best = self.match_wta(el.shape[0], want_best=True)
         res = {"edges-1": el, "edges-2": er, "score_best-0": best, "web-1": web1}
+        if lr_max_diff is not None:
+            web_right, _ = self.match_wta_right(el.shape[0], want_best=False)
+            web1, rejected = self.lr_check(web1, web_right, lr_max_diff, out=web1)
+            res.update({"web-1": web1, "web_right-1": web_right, "lr_rejected": rejected})
         if step3:
             web2 = self.fill_web_holes(web1, params.times)
             res["web-2"] = web2
@@ -336,4 +396,4 @@ class StereoPlan:
         return res
 
 
-__all__ = ["AlgorithmParams", "StereoPlan", "capi"]
+__all__ = ["AlgorithmParams", "LRResult", "StereoPlan", "capi"]

@@ -1,0 +1,117 @@
+"""Left-right consistency check, CPU side: the C ABI declares and exports the new entries and refuses bad
+arguments before it touches a device; the mirror identity that defines the right-reference map holds against
+a direct restatement; the check's definition on hand-built maps."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import lr_reference as lr
+from tests import oracle
+
+NEW = ("sm_match_wta_right", "sm_lr_check", "sm_run_lr", "sm_plan_reserve_lr")
+
+
+def test_new_symbols_are_declared_bound_and_exported():
+    from stereomatching_amd import capi
+    syms = capi.declared_symbols()
+    for s in NEW:
+        assert s in syms and s in capi._SIGNATURES and hasattr(capi.lib, s), s
+
+
+def test_argument_checks_precede_device_use():
+    from stereomatching_amd import capi
+    lib = capi.lib
+    px = C.c_void_p(16)           # never dereferenced: every call below is refused first
+
+    def refused(rc, text):
+        assert rc == capi.SM_ERR_ARG
+        assert text in lib.sm_last_error(), lib.sm_last_error()
+
+    refused(lib.sm_plan_reserve_lr(None), b"plan is NULL")
+    refused(lib.sm_match_wta_right(None, 1, px, None, None), b"plan is NULL")
+    refused(lib.sm_match_wta_right(None, 1, None, None, None), b"d_web_right is NULL")
+    refused(lib.sm_lr_check(None, px, px, 0, 1, px, None, None), b"plan is NULL")
+    refused(lib.sm_lr_check(None, px, px, -1, 1, px, None, None), b"max_diff -1 is negative")
+    refused(lib.sm_lr_check(None, None, px, 0, 1, px, None, None), b"NULL")
+    refused(lib.sm_lr_check(None, px, None, 0, 1, px, None, None), b"NULL")
+    refused(lib.sm_lr_check(None, px, px, 0, 1, None, None, None), b"NULL")
+    refused(lib.sm_run_lr(None, px, px, 0.15, 1, 0, px, None, None, None, None), b"plan is NULL")
+    refused(lib.sm_run_lr(None, px, px, 0.15, 1, -2, px, None, None, None, None), b"max_diff -2 is negative")
+    refused(lib.sm_run_lr(None, None, px, 0.15, 1, 0, px, None, None, None, None), b"input image pointer is NULL")
+    refused(lib.sm_run_lr(None, px, px, 1.5, 1, 0, px, None, None, None, None), b"threshold must be between 0 and 1")
+    refused(lib.sm_run_lr(None, px, px, 0.15, 1, 0, None, None, None, None, None), b"d_web is NULL")
+
+
+def rand_edges(w, h, seed, density=0.5):
+    rng = np.random.default_rng(seed)
+    return ((rng.random((h, w)) < density).astype(np.uint8),
+            (rng.random((h, w)) < density).astype(np.uint8))
+
+
+@pytest.mark.parametrize("mode", ["toroidal", "ghost"])
+@pytest.mark.parametrize("w,h,d,sw", [(40, 23, 12, 5), (33, 17, 45, 3), (31, 21, 7, 0), (17, 9, 9, 1),
+                                      (29, 30, 16, 9), (12, 11, 30, 7)])
+def test_mirror_identity_equals_the_right_reference_definition(mode, w, h, d, sw):
+    """mirror(hot_path(mirror(eR), mirror(eL))) is the right-reference match written out -- odd widths,
+    more shifts than columns, a window of one pixel (S = 0 and 1) -- for both borders"""
+    for seed, dens in ((1, 0.5), (2, 0.15)):
+        el, er = rand_edges(w, h, seed + 10 * w, dens)
+        ob, ow = lr.right_reference(el, er, d, sw, mode)
+        bb, bw = lr.right_reference_bruteforce(el, er, d, sw, mode)
+        assert np.array_equal(ow, bw), (mode, w, h, d, sw, seed)
+        assert np.array_equal(ob, bb), (mode, w, h, d, sw, seed)
+        # a pixel whose neighbourhood holds no edge at all matches every shift: the last one, D, wins
+        z = np.zeros((h, w), np.uint8)
+        assert (lr.right_reference(z, z, d, sw, mode)[1] == d).all()
+
+
+def test_right_reference_of_a_shifted_pair_points_back():
+    """the right image is the left one moved by 5 columns: both directions find the shift, and the check
+    keeps every pixel of the textured image (toroidal)"""
+    rng = np.random.default_rng(4)
+    el = (rng.random((24, 64)) < 0.5).astype(np.uint8)
+    er = np.roll(el, 5, axis=1)                  # eR(u) = eL(u - 5): left pixel x matches right pixel x + 5
+    _, web = oracle.hot_path(el, er, 8, 5, "toroidal")
+    _, web_right = lr.right_reference(el, er, 8, 5, "toroidal")
+    assert (web == 6).all() and (web_right == 6).all()
+    checked, rejected = lr.lr_check(web, web_right, 0, "toroidal")
+    assert rejected == 0 and np.array_equal(checked, web)
+
+
+def test_check_definition_on_hand_built_maps():
+    w = 8
+    # ghost: x = 6 with s = 3 matched u = 8, the halo -> rejected whatever the right map says
+    web = np.array([[1, 1, 1, 1, 1, 1, 3, 1]], np.int32)
+    wr = np.ones((1, w), np.int32)
+    wr[0, 0] = 3
+    out, rej = lr.lr_check(web, wr, 8, "ghost")
+    assert out[0, 6] == 0 and rej == 1 and (np.delete(out[0], 6) == 1).all()
+    # toroidal: the same pixel wraps round to u = 0, where the right map says 3 -> kept (and x = 0, s = 1,
+    # which matched u = 0 as well, is not)
+    out, rej = lr.lr_check(web, wr, 0, "toroidal")
+    assert out[0, 6] == 3 and out[0, 0] == 0 and rej == 1
+    # tolerance: right map off by one at u = 2 (x = 2, s = 1)
+    wr2 = wr.copy()
+    wr2[0, 0] = 1
+    wr2[0, 2] = 2
+    web2 = np.ones((1, w), np.int32)
+    out, rej = lr.lr_check(web2, wr2, 0, "toroidal")
+    assert out[0, 2] == 0 and rej == 1
+    out, rej = lr.lr_check(web2, wr2, 1, "toroidal")
+    assert rej == 0 and np.array_equal(out, web2)
+    # max_diff = D keeps every pixel whose match lands in the image
+    D = 4
+    rng = np.random.default_rng(3)
+    webr = rng.integers(1, D + 1, (5, 13)).astype(np.int32)
+    wrr = rng.integers(1, D + 1, (5, 13)).astype(np.int32)
+    out, rej = lr.lr_check(webr, wrr, D, "toroidal")
+    assert rej == 0 and np.array_equal(out, webr)
+    out, rej = lr.lr_check(webr, wrr, D, "ghost")
+    past = np.arange(13)[None, :] + webr - 1 >= 13
+    assert rej == past.sum() and (out[past] == 0).all() and np.array_equal(out[~past], webr[~past])
+    # and max_diff = 0 keeps exactly the pixels whose partner agrees
+    out, rej = lr.lr_check(webr, wrr, 0, "toroidal")
+    u = (np.arange(13)[None, :] + webr - 1) % 13
+    agree = np.take_along_axis(wrr, u, axis=1) == webr
+    assert rej == (~agree).sum() and np.array_equal(out, np.where(agree, webr, 0))
