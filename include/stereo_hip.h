@@ -351,6 +351,22 @@ int sm_run_typed(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gra
 int sm_cost_wta(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right,
                 int cost, int pairs, int32_t *d_web, int32_t *d_best, void *stream);
 
+/* Subpixel refinement of the cost mode: from a whole-pixel map d_web of sm_cost_wta and the
+ * same gray pair, d_sub (int16, [pairs][H][W]) receives the disparity in 1/16 of a shift.  Per pixel, with
+ * s = web(x, y) and C(d) the window cost at shift index d exactly as sm_cost_wta sums it:
+ *   s outside 1..D: sub = 0 (no taps);   s == 1 or s == D: sub = 16 s;
+ *   otherwise a = C(s-2) - C(s-1), b = C(s) - C(s-1) and
+ *     SM_COST_SSD (parabola):    q = floor((16 (a - b) + den) / (2 den)), den = a + b,
+ *     SM_COST_SAD (equiangular): q = floor((16 (a - b) + m) / (2 m)),     m = max(a, b),
+ *   q = 0 where the denominator is <= 0, else clamped to [-8, 8];  sub = 16 s + q.
+ * sub / 16 - 1 is the subpixel shift (left x matches right x + d).  For a map of sm_cost_wta on the same
+ * images a >= 1 and b >= 0 (first wins), so the clamp never applies.  Work per pixel is 3 n^2 taps, not
+ * D n^2.  d_costs: NULL, or [pairs][3][H][W] int32 receiving C(s-2), C(s-1), C(s), -1 where a shift or the
+ * pixel has no cost.  Arguments are checked as sm_cost_wta checks them; runs in `stream` order and allocates
+ * nothing, so it may be captured.                                                                      */
+int sm_cost_refine(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int cost, int pairs,
+                   const int32_t *d_web, int16_t *d_sub, int32_t *d_costs, void *stream);
+
 /* debug tap: materialise the per-shift planes the reference dumps in debug
  * builds (matches-i, score_all-i, scores-i; src/stereo.c:98-104,:158-164,
  * :189) for one shift of one pair.  Any output may be NULL.  Slow path.    */

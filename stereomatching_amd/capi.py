@@ -120,6 +120,7 @@ _SIGNATURES = {
     "sm_lr_check": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp]),
     "sm_run_lr": (_int, [_vp, _vp, _vp, _dbl, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "sm_plan_reserve_lr": (_int, [_vp]),
+    "sm_cost_refine": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp]),
 }
 
 

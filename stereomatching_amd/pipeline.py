@@ -324,6 +324,24 @@ class StereoPlan:
                               _ptr(web), _ptr(best), self._stream()))
         return web, best
 
+    def cost_refine(self, left, right, web, cost="sad", want_costs=False, out=None):
+        """Subpixel refinement of a cost_wta map (sm_cost_refine) -> (sub, costs): sub is int16 in 1/16 of a shift
+        (SSD: parabola, SAD: equiangular fit over C(s-2), C(s-1), C(s); 0 where web is outside 1..D), costs the
+        three window costs as (pairs, 3, H, W) int32 with -1 where a shift has none, if wanted."""
+        left = self._images(left, torch.uint8, "left")
+        right = self._images(right, torch.uint8, "right")
+        web = self._images(web, torch.int32, "web")
+        pairs = left.shape[0]
+        if right.shape[0] != pairs or web.shape[0] != pairs:
+            raise ValueError(f"right / web: {right.shape[0]} / {web.shape[0]} maps for {pairs} pairs")
+        out = self._out(out, pairs, "out", torch.int16)
+        costs = None
+        if want_costs:
+            costs = torch.empty((pairs, 3, self.height, self.width), dtype=torch.int32, device=self._dev)
+        check(lib.sm_cost_refine(self._h, _ptr(left), _ptr(right), {"sad": 1, "ssd": 2}[cost], pairs, _ptr(web),
+                                 _ptr(out), _ptr(costs), self._stream()))
+        return out, costs
+
     def debug_planes(self, pair: int, shift: int):
         """matches-i, score_all-i, scores-i of the reference's debug build."""
         m = torch.empty((self.height, self.width), dtype=torch.uint8, device=self._dev)
