@@ -147,6 +147,33 @@ def array_record(a):
     return {"sha256": hashlib.sha256(a.tobytes()).hexdigest(), "dtype": str(a.dtype), "shape": list(a.shape)}
 
 
+# near-tie edge images (tests/edge_tie_patterns.py): the first image pair of each batch, at thresholds whose
+# decisions sit on the f32 prefilter's band; only the two edge images are pinned (the contour stage may trap)
+EDGE_TIE_PINNED = [(mode, 40, 31, t) for mode in ("toroidal", "ghost") for t in (0.15, 2.0 / 3.0, 1.0)]
+
+
+def edge_tie_key(mode, w, h, t):
+    return f"edge_ties:{mode}:{w}x{h}:thr{t!r}"
+
+
+def edge_tie_images(mode, w, h, t):
+    from tests import edge_tie_patterns as et
+    lefts, rights = et.batch(w, h, mode, t, variants=1)
+    return lefts[0], rights[0]
+
+
+def edge_tie_cases():
+    cases = {}
+    for mode, w, h, t in EDGE_TIE_PINNED:
+        left, right = edge_tie_images(mode, w, h, t)
+        # repr(float) round-trips: the reference parses exactly this threshold
+        ref = oracle.run_reference(left, right, t, 5, 0, 10, mode, keep=lambda s: s in ("edges-1", "edges-2"),
+                                   allow_sigfpe=True)
+        cases[edge_tie_key(mode, w, h, t)] = {"returncode": ref["returncode"],
+                                              "arrays": {k: array_record(ref[k]) for k in ("edges-1", "edges-2")}}
+    return cases
+
+
 def main_pinned():
     import hashlib
     import json
@@ -169,6 +196,7 @@ def main_pinned():
                                keep=lambda s: s in ("web-1", "score_best-0"), allow_sigfpe=True)
     cases["constant:40x30:sw5"] = {"returncode": ref["returncode"],
                                    "arrays": {k: array_record(ref[k]) for k in ("web-1", "score_best-0")}}
+    cases.update(edge_tie_cases())
     (out_dir / "ref_pinned_cases.json").write_text(json.dumps(cases, indent=1, sort_keys=True) + "\n")
 
     dumps = {}

@@ -185,9 +185,12 @@ def test_edge_threshold_tables_exhaustive(hip):
     """the integer lo/hi tables sm_find_edges decides with reproduce the exact double
     test for every pair of in-image sums, for round and for random thresholds"""
     import ctypes as C
+    from tests import edge_tie_patterns as et
     rng = np.random.default_rng(11)
     thresholds = [0.0, 1.0, 0.15, 0.5, 0.25, 0.75, 1.0 / 3.0, 2.0 / 3.0, 1e-9, 0.999999,
-                  *rng.random(20).tolist()]
+                  *rng.random(20).tolist(),
+                  # where the f32 prefilter's band is widest, and where (float)(T / 2) rounds worst
+                  *(t for t, _ in et.tie_richest_thresholds(12)), *et.worst_rounding_thresholds(6)]
     plan = hip.StereoPlan(32, 32, 16, 5)
     tab = torch.empty((766, 766), dtype=torch.uint8, device="cuda")
     for thr in thresholds:
