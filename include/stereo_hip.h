@@ -143,13 +143,10 @@ typedef struct sm_plan_options {
     int edge_kernel;            /* 1 = the one-pixel-per-lane edge kernel even where the four-pixel one applies */
     int timing_by_records;      /* 1 = sm_plan_time_kernels brackets launches with event records instead of
                                  *     reading the dispatch's own time stamps */
-    int cost_pixels_per_lane;   /* SAD kernel (sm_cost_wta): 2 or 4 where both are built */
+    int cost_pixels_per_lane;   /* no effect; kept for the struct layout */
     int cost_tile_h;            /* SAD / SSD kernels: output rows per wave */
-    int cost_kernel;            /* 1 = the general masked kernel even where the quad-SAD / MFMA / dot kernels apply;
-                                   2 = SSD on the byte dot-product unit instead of the matrix cores;
-                                   3 = the ghost-border strip by the general masked kernel (as until round 3);
-                                   4 = SAD by the round-4 kernel (every window row from scratch) where the
-                                       prefix-chain kernel of round 5 applies */
+    int cost_kernel;            /* 1 = the general masked kernel even where the quad-SAD / MFMA kernels apply;
+                                   any other value = the plan's choice */
     int priority_class;         /* bit-sliced kernel: which of a SIMD's two waves a priority slice favours is told by
                                  * 1 = the wave slot's parity, 2 = the parity of the workgroup's slot on its CU (the two
                                  * waves of a two-wave workgroup are then favoured together); 0 = the plan's choice */
@@ -162,8 +159,8 @@ typedef struct sm_plan_options {
                                  * and 4); shifts_per_lane = 4 forces them where they are built */
     int priority_unit_log2;     /* bit-sliced kernel: log2 of the priority schedule's unit in shader-clock cycles (8 .. 20;
                                  * bit k of priority_pattern covers the k-th unit); 0 = the plan's choice */
-    int cost_workgroup_waves;   /* SAD kernel of round 5 (prefix chains): 1, 2 or 4 waves per workgroup sharing the staged
-                                 * rows; 0 = the plan's choice */
+    int cost_workgroup_waves;   /* SAD kernel of round 5 (prefix chains) and SSD matrix-core kernel: 1, 2 or 4 waves per
+                                 * workgroup sharing the staged rows; 0 = the plan's choice */
 } sm_plan_options;
 int sm_plan_create_ex(int device, int width, int height, int num_shifts, int square_width,
                       int border, int max_pairs, const sm_plan_options *options, sm_plan **out);
@@ -341,9 +338,8 @@ int sm_run_typed(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gra
  * reference treats its edge images (wrap, or zeros past the border and no taps
  * outside the image).  Defined by oracle/stereo_oracle.c smo_cost_hot_path.
  * Windows up to 25 x 25, num_shifts <= 512.  SAD windows 3 .. 21 run on the
- * quad-SAD unit, SSD windows 3 .. 11 with up to 256 shifts on the matrix cores
- * (or, sm_plan_options.cost_kernel = 2, on the byte dot-product unit), the
- * ghost border's columns x < half behind them on a kernel of their own
+ * quad-SAD unit, SSD windows 3 .. 11 with up to 256 shifts on the matrix cores,
+ * the ghost border's columns x < half behind them on a kernel of their own
  * (DESIGN.md 5.4); everything else on a general kernel -- the same results by
  * definition (tests: every path against the definition).                     */
 #define SM_COST_SAD 1

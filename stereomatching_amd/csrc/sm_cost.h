@@ -1,5 +1,6 @@
 // sm_cost.h -- shared between the translation units of the SAD / SSD cost mode
-// (sm_cost.hip: the general masked kernel and the C entry; sm_cost_qs.hip: SAD on the quad-SAD unit).
+// (sm_cost.hip: the general masked kernel and the C entry; sm_cost_pc.hip / sm_cost_qs.hip: SAD on the quad-SAD unit;
+// sm_cost_mfma.hip: SSD on the matrix cores; sm_cost_strip.hip: the ghost-border strip).
 #pragma once
 #include "sm_internal.h"
 
@@ -16,7 +17,6 @@ struct SadGeom {
     int q_tail;              // first quad of a lane that may hold shifts >= D
     int q_last;              // last quad in which some lane has a shift < D
     int fast_stage;          // image rows are dword-aligned and w % 4 == 0
-    int rr_stride;           // k_ssd_dot: dwords between the four residue classes of its RR table
     int tbl_pad;             // k_ssd_mfma: dwords between the staged rows and its (16-byte aligned) RR table
     int lds_bytes;
     int waves;               // k_sad_pc: waves per workgroup (they share the staged rows; the other kernels: 1)
@@ -160,12 +160,12 @@ struct SmcStream {
 };
 #endif
 
-// sm_cost_qs.hip / sm_cost_pc.hip / sm_cost_ssd.hip / sm_cost_mfma.hip: fill *g and return the kernel for this plan, or nullptr if the shape is not built
+// sm_cost_qs.hip / sm_cost_pc.hip / sm_cost_mfma.hip: fill *g and return the kernel for this plan, or nullptr if the shape is not built
+// sm_cost_qs.hip: SAD windows 17 .. 21 (two packed sums per shift), up to 240 shifts
 const void *sm_sad_qs_configure(const sm_plan *plan, int pairs, const void *d_left, const void *d_right, SadGeom *g);
 // sm_cost_pc.hip: SAD with the window rows formed by prefix chains along the row (round 5; windows up to 15 x 15)
 const void *sm_sad_pc_configure(const sm_plan *plan, int pairs, const void *d_left, const void *d_right, SadGeom *g);
-const void *sm_ssd_dot_configure(const sm_plan *plan, int pairs, const void *d_left, const void *d_right, SadGeom *g);
 const void *sm_ssd_mfma_configure(const sm_plan *plan, int pairs, const void *d_left, const void *d_right, SadGeom *g);
-// sm_cost_strip.hip: the ghost-border columns x < half behind a fast kernel's launch; -1 if not built for this shape
+// sm_cost_strip.hip: the ghost-border columns x < half behind a fast kernel's launch (built for every shape a fast kernel takes)
 int sm_cost_strip_launch(const sm_plan *plan, const uint8_t *d_left, const uint8_t *d_right, int cost, int pairs,
                          int32_t *d_web, int32_t *d_best, hipStream_t stream);

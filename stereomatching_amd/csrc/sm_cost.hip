@@ -22,7 +22,6 @@
 
 #include "sm_internal.h"
 #include "sm_cost.h"
-#include <mutex>
 
 #define SMC_DS 8        // shifts per lane
 #define SMC_PX 4        // pixels per lane
@@ -51,7 +50,6 @@ struct CostGeom {
     int nsr, tiles_x, tiles_y;
     int pad;                 // bytes left of the tile in a staged row (multiple of 4, >= half)
     int vec_ok;
-    int xlim;                // only pixel groups left of this column are computed (the whole image: w)
 };
 
 template <int NWD, bool SSD, bool GHOST>
@@ -106,7 +104,7 @@ __global__ __launch_bounds__(256) void k_cost_wta(const u8 *__restrict__ left,
     const int grp = tid >> g.log2nl;
     const int x0l = grp * SMC_PX, x0 = tx0 + x0l;
     const int d0 = s * SMC_DS;
-    if (x0 >= g.xlim) return;                      // (all lanes of a pixel group leave together)
+    if (x0 >= g.w) return;                         // (all lanes of a pixel group leave together)
     const int bL = g.pad + x0l - half;            // byte offset of the window in a staged row
     const int wL = bL >> 2, shL = bL & 3;
     const int bR = bL + d0;
@@ -256,10 +254,9 @@ static const void *cost_ptr(bool ssd, bool ghost)
                : (ghost ? (const void *)k_cost_wta<NWD, false, true> : (const void *)k_cost_wta<NWD, false, false>);
 }
 
-// the general (masked) kernel on the whole image, or -- strip_cols > 0 -- only on the pixel
-// columns [0, strip_cols) (the ghost-border columns the quad-SAD kernel cannot do)
+// the general (masked) kernel on the whole image
 static int launch_general(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int cost,
-                          int pairs, int32_t *d_web, int32_t *d_best, int strip_cols, hipStream_t stream)
+                          int pairs, int32_t *d_web, int32_t *d_best, hipStream_t stream)
 {
     CostGeom g;
     g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts;
@@ -269,16 +266,8 @@ static int launch_general(sm_plan *plan, const uint8_t *d_gray_left, const uint8
                        "(got %dx%d, %d)", g.n, g.n, g.D);
     g.nl = 1; g.log2nl = 0;
     while (g.nl * SMC_DS < g.D) { g.nl <<= 1; g.log2nl++; }
-    // whole image: 256 threads = 256 / nl pixel groups per workgroup; the ghost strip: only the
-    // groups that hold its few columns (a narrow tile: little to stage), rounded up to whole waves
-    int threads = 256;
+    // 256 threads = 256 / nl pixel groups per workgroup
     g.groups = 256 / g.nl;
-    if (strip_cols > 0) {
-        const int need = (strip_cols + SMC_PX - 1) / SMC_PX;
-        if (need < g.groups) g.groups = need;
-        threads = 64 * ((g.groups * g.nl + 63) / 64);
-        g.groups = threads / g.nl;
-    }
     g.tw = g.groups * SMC_PX;
     g.pad = 4 * ((g.half + 3) / 4);
     int nwd = (g.n + 3 + 3) / 4;       // dwords holding the n + 3 window bytes of a lane
@@ -287,15 +276,8 @@ static int launch_general(sm_plan *plan, const uint8_t *d_gray_left, const uint8
     g.lrow = 4 * ((g.pad + g.tw + 4 * (nwd + 1) + 3) / 4);
     g.rrow = 4 * ((g.pad + g.tw + g.nl * SMC_DS + 4 * (nwd + 4) + 3) / 4);
     g.tiles_x = (g.w + g.tw - 1) / g.tw;
-    g.xlim = g.w;
-    if (strip_cols > 0) {
-        g.xlim = strip_cols;
-        g.tiles_x = (strip_cols + g.tw - 1) / g.tw;
-    }
     int th = 64;
-    // (the strip is a few hundred short workgroups whatever the tile height: its duration is one
-    // workgroup's latency, so it takes the shortest tiles)
-    while (th > (strip_cols > 0 ? 2 : 8) && (long long)g.tiles_x * ((g.h + th - 1) / th) * pairs < (strip_cols > 0 ? 4096 : 1024)) th >>= 1;
+    while (th > 8 && (long long)g.tiles_x * ((g.h + th - 1) / th) * pairs < 1024) th >>= 1;
     while ((th + g.n - 1) * (g.lrow + g.rrow) > 60 * 1024 && th > 1) th >>= 1;
     th = th < g.h ? th : g.h;
     g.tile_h = th;
@@ -313,7 +295,7 @@ static int launch_general(sm_plan *plan, const uint8_t *d_gray_left, const uint8
     default: fn = cost_ptr<7>(ssd, ghost); break;
     }
     void *args[] = {(void *)&d_gray_left, (void *)&d_gray_right, (void *)&d_web, (void *)&d_best, (void *)&g};
-    const hipError_t e = hipLaunchKernel(fn, dim3(g.tiles_x, g.tiles_y, pairs), dim3(threads), args,
+    const hipError_t e = hipLaunchKernel(fn, dim3(g.tiles_x, g.tiles_y, pairs), dim3(256), args,
                                          (size_t)g.nsr * (g.lrow + g.rrow), stream);
     if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "sm_cost_wta: %s", hipGetErrorString(e));
     return SM_OK;
@@ -332,28 +314,19 @@ extern "C" int sm_cost_wta(sm_plan *plan, const uint8_t *d_gray_left, const uint
     if (es != hipSuccess) return sm_fail(SM_ERR_HIP, "sm_cost_wta: %s", hipGetErrorString(es));
     {
         // SAD on the quad-SAD unit (sm_cost_pc.hip: window rows by prefix chains, windows up to 15 x 15; sm_cost_qs.hip:
-        // the larger ones, and cost_kernel = 4), SSD on the matrix cores (sm_cost_mfma.hip; cost_kernel = 2: on the
-        // byte dot-product unit, sm_cost_ssd.hip),
-        // where they are built for this window and shift count; otherwise the general masked kernel
+        // 17 .. 21), SSD on the matrix cores (sm_cost_mfma.hip), where they are built for this window and shift count;
+        // otherwise, or with cost_kernel = 1, the general masked kernel
         SadGeom q;
         const void *fn = cost == SM_COST_SAD ? sm_sad_pc_configure(plan, pairs, d_gray_left, d_gray_right, &q)
                                              : sm_ssd_mfma_configure(plan, pairs, d_gray_left, d_gray_right, &q);
         if (!fn && cost == SM_COST_SAD) fn = sm_sad_qs_configure(plan, pairs, d_gray_left, d_gray_right, &q);
-        if (!fn && cost == SM_COST_SSD) fn = sm_ssd_dot_configure(plan, pairs, d_gray_left, d_gray_right, &q);
         if (fn) {
             void *args[] = {(void *)&d_gray_left, (void *)&d_gray_right, (void *)&d_web, (void *)&d_best, (void *)&q};
-            if (q.lds_bytes > 64 * 1024) {
-                // (four-wave workgroups of k_sad_pc: up to 80 of the CU's 160 KB; the limit is raised once per kernel)
-                static std::mutex guard;          // (plans on different host threads may launch the same kernel)
-                static const void *raised[8];
-                static int n_raised = 0;
-                std::lock_guard<std::mutex> lock(guard);
-                bool seen = false;
-                for (int i = 0; i < n_raised; i++) seen = seen || raised[i] == fn;
-                if (!seen) {
-                    SM_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-                    if (n_raised < 8) raised[n_raised++] = fn;
-                }
+            if (q.lds_bytes > 64 * 1024 && !plan->cost_lds_raised) {
+                // Four-wave workgroups of k_sad_pc: up to 80 of the CU's 160 KB.  The limit is raised once per plan, on its
+                // device: N and D are fixed per plan, so this is the only kernel of the plan that asks for more than 64 KB.
+                SM_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+                plan->cost_lds_raised = 1;
             }
             const hipError_t e = hipLaunchKernel(fn, dim3(q.tiles_x, q.tiles_y, pairs), dim3(64 * q.waves), args,
                                                  (size_t)q.lds_bytes, (hipStream_t)stream);
@@ -365,16 +338,11 @@ extern "C" int sm_cost_wta(sm_plan *plan, const uint8_t *d_gray_left, const uint
             // C5 SSD -- the strip's 256-thread workgroups take their CUs' LDS and wave slots first and the main
             // launch's one-wave workgroups no longer spread evenly; enqueued behind the main launch instead of in front
             // of it, the same: 876 vs 754 us.  profiles/r04/ab_cost_strip_beside_rejected.txt)
-            if (q.ghost && plan->square_width / 2 > 0) {
-                // sm_cost_strip.hip: a kernel built for these columns (~10 us at 4K where the general one needs 50-60)
-                const int rc = sm_cost_strip_launch(plan, d_gray_left, d_gray_right, cost, pairs, d_web, d_best,
-                                                    (hipStream_t)stream);
-                if (rc >= 0) return rc;
-                return launch_general(plan, d_gray_left, d_gray_right, cost, pairs, d_web, d_best,
-                                      plan->square_width / 2, (hipStream_t)stream);
-            }
+            // sm_cost_strip.hip: a kernel built for these columns (~10 us at 4K where the general one needs 50-60)
+            if (q.ghost && plan->square_width / 2 > 0)
+                return sm_cost_strip_launch(plan, d_gray_left, d_gray_right, cost, pairs, d_web, d_best, (hipStream_t)stream);
             return SM_OK;
         }
     }
-    return launch_general(plan, d_gray_left, d_gray_right, cost, pairs, d_web, d_best, 0, (hipStream_t)stream);
+    return launch_general(plan, d_gray_left, d_gray_right, cost, pairs, d_web, d_best, (hipStream_t)stream);
 }

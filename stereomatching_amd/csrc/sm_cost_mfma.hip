@@ -25,11 +25,11 @@
 // entry(u) = -(RR(u) << 8) - (u & 255) read as one ds_read_b128 per four positions, and one v_max3_i32 takes
 // two keys -- then one exchange between the lane halves.  Measured at C5 (4K, 256 shifts, 11 x 11): 4.06
 // VALU lane-instructions per (pixel, shift), RR table and operand set-up included, against 14.5 for the
-// dot-product kernel (sm_cost_ssd.hip); 403 us per launch against 974; the matrix pipe is busy 11 % of
+// byte dot-product kernel of rounds 2-4 (k_ssd_dot, retired); 403 us per launch against 974; the matrix pipe is busy 11 % of
 // the time (profiles/r04/cost_ssd_C5.json).
 //
-// Ghost border: as in the other two kernels, rows / columns outside the image are staged as zero pixels in
-// both images; the columns x < half are recomputed by the masked kernel of sm_cost.hip.
+// Ghost border: as in the SAD kernels, rows / columns outside the image are staged as zero pixels in
+// both images; the columns x < half are recomputed by sm_cost_strip.hip.
 //
 // Limits: windows up to 11 x 11 (the key holds RR - 2 LR in 24 signed bits), D <= 256.
 
@@ -42,17 +42,8 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ u32 sdot4(u32 a, u32 b, u32 acc) { return (u32)__builtin_amdgcn_sdot4((int)a, (int)b, (int)acc, false); }
 
-#ifndef MFMA_EXP
-#define MFMA_EXP 0      // (timing experiments only, results wrong: 1 no table reads, 2 no table update, 3 no MFMA, 4 no keys)
-#endif
 // waves per SIMD the register count allows: the NB x 16 accumulators are most of it
-#ifndef MFMA_W3
-#define MFMA_W3 5
-#endif
-#ifndef MFMA_W4
-#define MFMA_W4 3
-#endif
-constexpr int mfma_waves(int nb) { return nb <= MFMA_W4 ? 4 : nb <= MFMA_W3 ? 3 : 2; }
+constexpr int mfma_waves(int nb) { return nb <= 3 ? 4 : nb <= 5 ? 3 : 2; }
 
 template <int N, int NB>
 __global__ __launch_bounds__(256, mfma_waves(NB)) void k_ssd_mfma(const u8 *__restrict__ left, const u8 *__restrict__ right,
@@ -167,13 +158,11 @@ __global__ __launch_bounds__(256, mfma_waves(NB)) void k_ssd_mfma(const u8 *__re
 #pragma unroll
                 for (int k = 0; k < 5; k++) tq[(b + PF) % (PF + 1)][k] = rowR[8 * (b + PF) + k];
             }
-#if MFMA_EXP != 1
             if (KEYS && b + 1 < NB) {
 #pragma unroll
                 for (int q = 0; q < 4; q++) eq[(b + 1) & 1][q] = *reinterpret_cast<const v4i *>(sT + 32 * (b + 1) + 8 * q + 4 * h);
             }
-#endif
-            if (KEYS && MFMA_EXP != 4) {
+            if (KEYS) {
                 i32 keys[16];
 #pragma unroll
                 for (int q = 0; q < 4; q++)
@@ -211,14 +200,9 @@ __global__ __launch_bounds__(256, mfma_waves(NB)) void k_ssd_mfma(const u8 *__re
                 v4i aop;
 #pragma unroll
                 for (int k = 0; k < 4; k++) aop[k] = (int)__builtin_amdgcn_alignbyte(t[k + 1], t[k], rho);
-#if MFMA_EXP != 3
                 acc[b] = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop, bop, acc[b], 0, 0, 0);
-#else
-                acc[b][0] += aop[0] ^ bop[0]; acc[b][5] += aop[1] ^ bop[1]; acc[b][10] += aop[2] ^ bop[2]; acc[b][15] += aop[3] ^ bop[3];
-#endif
                 // T(u) += the entering row's squares; -= the leaving row's squares + 2 x its sum (the drift of the LR sums:
                 // the complemented left operand leaves -sum R behind in every accumulator of position u)
-#if MFMA_EXP != 2
                 u32 s = 0;
 #pragma unroll
                 for (int k = 0; k <= FD; k++) {
@@ -227,7 +211,6 @@ __global__ __launch_bounds__(256, mfma_waves(NB)) void k_ssd_mfma(const u8 *__re
                     s = sdot4(q, c2, s);
                 }
                 __hip_atomic_fetch_add(&sT[32 * b + xl], (u32)__mul24((int)s, sg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
             }
             __builtin_amdgcn_sched_barrier(0);          // (block by block: the scheduler otherwise keeps every block's operands alive)
         }
@@ -291,7 +274,7 @@ const void *sm_ssd_mfma_configure(const sm_plan *plan, int pairs, const void *d_
     g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts; g.waves = 1;
     const int half = plan->square_width / 2, n = 2 * half + 1;
     g.ghost = plan->border == SM_GHOST;
-    if (n < 3 || n > 11 || g.D > 256 || plan->opt.cost_kernel == 1 || plan->opt.cost_kernel == 2) return nullptr;
+    if (n < 3 || n > 11 || g.D > 256 || plan->opt.cost_kernel == 1) return nullptr;
     const int nb = (g.D + 31 + 31) / 32;                // right positions 0 .. D + 30
     g.nl = 1; g.log2nl = 0; g.nql = 0; g.px = 1; g.q_tail = 0; g.q_last = 0;
     g.padl = 4 * ((half + 3 + 3) / 4);
@@ -309,22 +292,28 @@ const void *sm_ssd_mfma_configure(const sm_plan *plan, int pairs, const void *d_
     // slower at the taller tiles the model gives them -- C5: 0.427 / 0.447 / 0.391 ms at 1 / 2 / 4 waves,
     // profiles/r05/ab_ssd_workgroup_waves.txt -- for a reason that was not found; an explicit 2 is honoured)
     int best_th = 0, best_wv = 1; double best_cost = 0;
-    for (int wv = 1; wv <= 4; wv *= 2) {
-        if (plan->opt.cost_workgroup_waves ? plan->opt.cost_workgroup_waves != wv : wv == 2) continue;
-        int lrow, rrow, tbl;
-        shape(wv, &lrow, &rrow, &tbl);
-        if (wv > 1 && 32 * wv / 2 >= g.w) break;
-        if (lrow + rrow > 4 * 4 * 64 * wv) continue;         // (the fast staging path's reach)
-        const int tiles_x = (g.w + 32 * wv - 1) / (32 * wv);
-        for (int th = 8; th <= 128; th += 4) {
-            const size_t lds = (size_t)(th + n - 1) * (lrow + rrow) + tbl;
-            if (lds > (size_t)wv * (160 * 1024 / (4 * per_simd)) || lds > 64 * 1024) break;
-            const long long waves = (long long)tiles_x * ((g.h + th - 1) / th) * pairs * wv;
-            const long long rounds = (waves + slots - 1) / slots;
-            const double cost = (double)rounds * (th + 0.6 * (n - 1) + 2.0);
-            if (!best_th || cost < best_cost * (wv > best_wv ? 0.97 : 1.0)) { best_th = th; best_wv = wv; best_cost = cost; }
+    auto search = [&](int only) {           // only: the one width to consider; 0: the plan's own choice
+        for (int wv = 1; wv <= 4; wv *= 2) {
+            if (only ? only != wv : wv == 2) continue;
+            int lrow, rrow, tbl;
+            shape(wv, &lrow, &rrow, &tbl);
+            if (wv > 1 && 32 * wv / 2 >= g.w) break;
+            if (lrow + rrow > 4 * 4 * 64 * wv) continue;         // (the fast staging path's reach)
+            const int tiles_x = (g.w + 32 * wv - 1) / (32 * wv);
+            for (int th = 8; th <= 128; th += 4) {
+                const size_t lds = (size_t)(th + n - 1) * (lrow + rrow) + tbl;
+                if (lds > (size_t)wv * (160 * 1024 / (4 * per_simd)) || lds > 64 * 1024) break;
+                const long long waves = (long long)tiles_x * ((g.h + th - 1) / th) * pairs * wv;
+                const long long rounds = (waves + slots - 1) / slots;
+                const double cost = (double)rounds * (th + 0.6 * (n - 1) + 2.0);
+                if (!best_th || cost < best_cost * (wv > best_wv ? 0.97 : 1.0)) { best_th = th; best_wv = wv; best_cost = cost; }
+            }
         }
-    }
+    };
+    // an explicit width where it applies; one that does not (not 1, 2 or 4, or wider than the image) is ignored, as
+    // k_sad_pc ignores it.  The plan's own choice always finds the one-wave shape (D <= 256: at most ~8 KB of LDS).
+    search(plan->opt.cost_workgroup_waves);
+    if (!best_th) search(0);
     if (!best_th) return nullptr;
     g.waves = best_wv;
     int tbl_bytes;
@@ -341,7 +330,6 @@ const void *sm_ssd_mfma_configure(const sm_plan *plan, int pairs, const void *d_
     g.fast_stage = g.w % 4 == 0 && ((uintptr_t)d_left & 3) == 0 && ((uintptr_t)d_right & 3) == 0 &&
                    g.lrow + g.rrow <= 4 * 4 * 64 * g.waves;
     // dwords between the end of the staged rows and the table: whatever makes the table 16-byte aligned
-    g.rr_stride = 0;
     g.tbl_pad = (4 - (g.nsr * ((g.lrow + g.rrow) >> 2)) % 4) % 4;
     g.lds_bytes = g.nsr * (g.lrow + g.rrow) + tbl_bytes;
     const void *fn = nullptr;

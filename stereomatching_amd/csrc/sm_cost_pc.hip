@@ -44,15 +44,10 @@
 //     asked for at step s -- staging all rows first was 5 % of a one-round launch (profiles/r05/ab_sad_knockouts.txt);
 //   - workgroups of 1, 2 or 4 waves share the staged rows (the host chooses: at 256 shifts four waves slide 64 rows where a
 //     lone wave's 20 KB hold 16).
-// PC_EXP: timing knock-outs (results wrong), as MFMA_EXP of sm_cost_mfma.hip.
 
 #include "sm_internal.h"
 #include "sm_cost.h"
 #include <type_traits>
-
-#ifndef PC_EXP
-#define PC_EXP 0        // (timing experiments only, results wrong: 1 rows not loaded from memory, 2 no arg-min keys, 3 no E / shifted rows per step)
-#endif
 
 typedef unsigned long long u64;
 typedef unsigned short v4h __attribute__((ext_vector_type(4)));
@@ -121,11 +116,7 @@ __global__ __launch_bounds__(256, 2) void k_sad_pc(const u8 *__restrict__ left, 
     const bool stream = NQL >= 17 && g.fast_stage != 0;
     SmcStream feed;
     if (stream) feed.setup(L, R, g, xw, tid, nthreads);
-#if PC_EXP != 1
     smc_stage_rows(lds, L, R, g, xw, ty0, HALF, tid, 0, nthreads, stream ? 2 : g.nsr);
-#else
-    for (int k = tid; k < g.nsr * (lw + rw); k += nthreads) lds[k] = (u32)k * 2654435761u;
-#endif
     __syncthreads();
 
     // ---- lane role: residue a, shift-lane sl, pixel group j (over all waves)
@@ -162,13 +153,13 @@ __global__ __launch_bounds__(256, 2) void k_sad_pc(const u8 *__restrict__ left, 
         const u32 *rowLo = sL + ro_i * lw, *rowRo = sR + ro_i * rw;
 
         // the row fetched at the step before goes to LDS, the row two steps ahead is asked for (rn_i is the step's number)
-        if (stream && PC_EXP != 1) {
+        if (stream) {
             feed.store(lds);
             if (rn_i + 2 < g.nsr) feed.fetch(g, ty0, HALF, rn_i + 2);
         }
         // per right dword position: E = (bytes the zeroed left bytes pick up in the new row) - (old row), and the
         // two rows RB bytes further on
-        for (int k = tid; k < (PC_EXP == 3 ? 0 : rw - 1); k += nthreads) {
+        for (int k = tid; k < rw - 1; k += nthreads) {
             const u32 n0 = rowRn[k], n1 = rowRn[k + 1];
             const u64 mn = __builtin_amdgcn_mqsad_pk_u16_u8(((u64)n1 << 32) | n0, MASKC, 0ull);   // 255 (4-RB) - T_new
             sSn[k] = __builtin_amdgcn_alignbyte(n1, n0, RB);
@@ -278,7 +269,7 @@ __global__ __launch_bounds__(256, 2) void k_sad_pc(const u8 *__restrict__ left, 
                     // (pinned: nothing of a quad may sink below the quads nested in it)
                     asm volatile("" : : "v"(acc));
                     W[i][q] = acc;
-                    if (OUT && PC_EXP != 2) {
+                    if (OUT) {
                         constexpr int cq = 4 * (q % CH);
                         const u32 lo = (u32)acc, hi = (u32)(acc >> 32);
                         u32 k0 = (lo << 16) | (u32)cq, k1 = bop_and_or(lo, 0xffff0000u, (u32)(cq + 1));
@@ -364,15 +355,15 @@ static const void *sad_pc_ptr(int nql)
     return nullptr;
 }
 
-// fills g and returns the kernel, or nullptr if this shape is not built (caller falls back to k_sad_qs)
+// fills g and returns the kernel, or nullptr if this shape is not built (caller falls back to k_sad_qs, then the general kernel)
 const void *sm_sad_pc_configure(const sm_plan *plan, int pairs, const void *d_left, const void *d_right, SadGeom *out)
 {
     SadGeom g;
-    g.rr_stride = 0; g.tbl_pad = 0;         // (the SSD kernels')
+    g.tbl_pad = 0;                          // (the SSD kernel's)
     g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts;
     const int half = plan->square_width / 2, n = 2 * half + 1;
     g.ghost = plan->border == SM_GHOST;
-    if (n < 3 || n > 15 || g.D > 512 || plan->opt.cost_kernel == 1 || plan->opt.cost_kernel == 4) return nullptr;
+    if (n < 3 || n > 15 || g.D > 512 || plan->opt.cost_kernel == 1) return nullptr;
     const int nq = (g.D + 3 + 3) / 4;               // quads that cover shifts -3 .. D-1
     const int px = 4;
     const int nql = nq <= 5 ? 5 : nq <= 9 ? 9 : 17;

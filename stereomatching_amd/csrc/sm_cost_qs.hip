@@ -1,4 +1,5 @@
-// sm_cost_qs.hip -- SAD cost mode of the hot path on the quad-SAD unit.
+// sm_cost_qs.hip -- SAD cost mode of the hot path on the quad-SAD unit, windows 17, 19 and 21 (rounds 3-4; the smaller
+// windows take the prefix-chain kernel of sm_cost_pc.hip, which is built on this one).
 //
 // PARITY UNPINNED: the reference has no SAD implementation; the mode is
 // the build's own definition (stated at the top of sm_cost.hip; the checker restates it on the CPU).
@@ -12,13 +13,13 @@
 // abs-differences per cycle as v_sad_u8, but the accumulate, the packing and the alignment to
 // the shift come for free.
 //
-// A lane owns PX pixels (4 apart) x 4*NQL shifts and keeps their window sums A as packed u16
-// (n*n*255 < 65536: windows up to 15 x 15 -- larger ones, up to the reference's default 21 x 21, keep
-// TWO packed sums per shift, see SPLIT below).  Per output row and (pixel, 4 shifts):
-//     t = E;   t = qsad(old row groups ..., t)           NG = ceil(n/4) instructions
-//     A = qsad(new row groups ..., A)                    NG
+// A lane owns PX pixels (4 apart) x 4*NQL shifts and keeps their window sums as packed u16 -- TWO per
+// shift, as a window sum of these sizes does not fit 16 bits (see the split below).  Per output row and
+// (pixel, 4 shifts), for each of the two:
+//     t = E or 0;   t = qsad(old row groups ..., t)      NG = ceil(n/4) instructions in all
+//     A = qsad(new row groups ..., A)                    NG in all
 //     A -= t                                             2 x v_pk_sub_u16
-//     keys (A << 16 | shift), first-wins arg-min         4 + 2 x v_min3_u32
+//     keys (A + A2) << 8 | shift, first-wins arg-min     12 + 2 x v_min3_u32
 // All 8-byte right-image operands are dword-ALIGNED: a pixel x only takes the shift quads that
 // start at d = -((x - half) mod 4) (mod 4), so no byte alignment is ever needed on the right row.
 // The left operands (shared by all shifts) are cut with v_alignbyte once per row.
@@ -36,7 +37,7 @@
 // sm_cost_strip.hip, a short launch behind this one (beside it, on a stream of its own, it costs more than it
 // takes: sm_cost_wta).
 //
-// SPLIT (n = 17, 19, 21): a window sum reaches 21 * 21 * 255 = 112 455, more than 16 bits.  The window's
+// The split (n = 17, 19, 21): a window sum reaches 21 * 21 * 255 = 112 455, more than 16 bits.  The window's
 // column groups are split between two packed accumulators -- the first three groups (12 columns: at most
 // 12 * 21 * 255 = 64 260) and the rest (at most 9 columns) -- each slid exactly as the single one; the two
 // are added as 32-bit integers only where the keys are formed (12 more full-rate instructions per pixel
@@ -53,8 +54,6 @@ __device__ __forceinline__ u64 pk4_sub(u64 a, u64 b)
 {
     return __builtin_bit_cast(u64, (v4h)(__builtin_bit_cast(v4h, a) - __builtin_bit_cast(v4h, b)));
 }
-// (a & b) | c in one full-rate v_bitop3 (v_and_or_b32 is one of the half-rate class)
-__device__ __forceinline__ u32 bop_and_or(u32 a, u32 b, u32 c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0xEA); }
 __device__ __forceinline__ u64 qsad(u64 r8, u32 l4, u64 acc) { return __builtin_amdgcn_qsad_pk_u16_u8(r8, l4, acc); }
 
 // 8-byte LDS reads at 4-byte alignment (-> ds_read2_b32 into an even register pair)
@@ -69,9 +68,9 @@ __global__ __launch_bounds__(64, 2) void k_sad_qs(const u8 *__restrict__ left, c
     constexpr u32 MASKR = RB == 1 ? 0x000000ffu : 0x00ffffffu;      // left bytes of the last group
     constexpr u32 MASKC = ~MASKR;                                    // 255 on the bytes zeroed there
     constexpr int WN = NG + PX - 1;                                  // right operands alive per quad
-    constexpr bool SPLIT = N * N * 255 >= 65536;                     // two packed sums per shift
-    constexpr int GL = SPLIT ? 3 : NG;                               // column groups of the first accumulator
+    constexpr int GL = 3;                                            // column groups of the first accumulator
     static_assert(RB == 1 || RB == 3, "odd windows");
+    static_assert(N * N * 255 >= 65536, "two packed sums per shift (smaller windows: k_sad_pc)");
     // What must fit 16 bits is each packed sum BETWEEN slides (n rows).  During a slide the entering row is added before
     // the leaving one comes off, so a field holds up to n + 1 rows for an instant (21 x 21: 12 * 22 * 255 = 67 320) and
     // may wrap -- which is exact: v_qsad_pk_u16_u8 and v_pk_sub_u16 work modulo 2^16 PER FIELD, without carry into the
@@ -79,11 +78,11 @@ __global__ __launch_bounds__(64, 2) void k_sad_qs(const u8 *__restrict__ left, c
     // and the difference of the two is below 2^16 again.  A port to a saturating or carry-propagating form must take the
     // leaving row off first.
     static_assert(4 * GL * N * 255 < 65536 && (N - 4 * GL) * N * 255 < 65536, "each packed sum must fit 16 bits between slides");
-    static_assert(!SPLIT || NG > GL, "the split needs groups on both sides");
-    constexpr int KS = SPLIT ? 8 : 16;                               // bits of the shift in a key
-    // "nothing yet": above every real key of a chunk (a real sum is below 2^16 / 2^17) and far enough from 2^32
+    static_assert(NG > GL, "the split needs groups on both sides");
+    constexpr int KS = 8;                                            // bits of the shift in a key
+    // "nothing yet": above every real key of a chunk (a real sum is below 2^17) and far enough from 2^32
     // for the chunk bases and the lane's first shift to be added without a wrap
-    constexpr u32 KNONE = SPLIT ? 0x7fffff00u : 0xffff0000u;
+    constexpr u32 KNONE = 0x7fffff00u;
 
     extern __shared__ __attribute__((aligned(16))) u32 lds[];
     const int tid = threadIdx.x;
@@ -110,11 +109,11 @@ __global__ __launch_bounds__(64, 2) void k_sad_qs(const u8 *__restrict__ left, c
     const int bR = bL + sl * NQL;                       // ... of shift quad 0's right operand
     const int dconst = 4 * sl * NQL - rho;              // shift of (quad 0, position 0)
 
-    u64 A[PX][NQL], A2[SPLIT ? PX : 1][SPLIT ? NQL : 1];            // (A2: the second group of columns, SPLIT only)
+    u64 A[PX][NQL], A2[PX][NQL];                                     // (A2: the second group of columns)
 #pragma unroll
     for (int i = 0; i < PX; i++)
 #pragma unroll
-        for (int q = 0; q < NQL; q++) { A[i][q] = 0; if (SPLIT) A2[i][q] = 0; }
+        for (int q = 0; q < NQL; q++) { A[i][q] = 0; A2[i][q] = 0; }
 
     auto ld_pair = [&](const u32 *row, int idx) -> u64 { return *reinterpret_cast<const u64a4 *>(row + idx); };
 
@@ -125,7 +124,6 @@ __global__ __launch_bounds__(64, 2) void k_sad_qs(const u8 *__restrict__ left, c
         const u32 *rowLo = sL + ro_i * lw, *rowRo = sR + ro_i * rw;
 
         // E: per right dword position, (bytes the zeroed left bytes pick up in the new row) - (old row)
-#ifndef SAD_EXPERIMENT_NO_E      // (timing experiment only: what the E update and its barrier cost per row)
         for (int k = tid; k < rw - 1; k += 64) {
             const u64 mn = __builtin_amdgcn_mqsad_pk_u16_u8(ld_pair(rowRn, k), MASKC, 0ull);   // 255 (4-RB) - T_new
             u64 e;
@@ -134,7 +132,6 @@ __global__ __launch_bounds__(64, 2) void k_sad_qs(const u8 *__restrict__ left, c
             sE[k] = e;
         }
         __syncthreads();
-#endif
 
         // left operands of this lane's PX windows: NG groups each, 4 pixels apart -> NG + PX - 1 dwords
         u32 un[WN], unp[PX], uo[WN], uop[PX];
@@ -204,43 +201,38 @@ __global__ __launch_bounds__(64, 2) void k_sad_qs(const u8 *__restrict__ left, c
                 }
 #pragma unroll
                 for (int i = 0; i < PX; i++) {
-                    // (SPLIT: the chains of the first GL groups and of the rest run into accumulators of their
+                    // (the chains of the first GL groups and of the rest run into accumulators of their
                     // own; E belongs to the LAST group, i.e. to the second chain)
-                    u64 t = SPLIT ? 0ull : ee[i], t2 = ee[i];
+                    u64 t = 0ull, t2 = ee[i];
                     if (!WARM) {
 #pragma unroll
                         for (int gp = 0; gp < GL; gp++) t = qsad(ro[i + gp], gp == FG ? uop[i] : uo[i + gp], t);
 #pragma unroll
                         for (int gp = GL; gp < NG; gp++) t2 = qsad(ro[i + gp], gp == FG ? uop[i] : uo[i + gp], t2);
                     }
-                    u64 acc = A[i][q], acc2 = SPLIT ? A2[i][q] : 0ull;
+                    u64 acc = A[i][q], acc2 = A2[i][q];
 #pragma unroll
                     for (int gp = 0; gp < GL; gp++) acc = qsad(rn[i + gp], gp == FG ? unp[i] : un[i + gp], acc);
 #pragma unroll
                     for (int gp = GL; gp < NG; gp++) acc2 = qsad(rn[i + gp], gp == FG ? unp[i] : un[i + gp], acc2);
                     acc = pk4_sub(acc, t);
-                    if (SPLIT) acc2 = pk4_sub(acc2, t2);
+                    acc2 = pk4_sub(acc2, t2);
                     // (pinned: nothing of a quad may sink below the quads nested in it -- the compiler
                     // otherwise reads all operands on the way in, spilling them, and computes on the way out)
                     asm volatile("" : : "v"(acc));          // (a use only: an output would cost a wait state behind it)
                     A[i][q] = acc;
-                    if (SPLIT) { asm volatile("" : : "v"(acc2)); A2[i][q] = acc2; }
+                    asm volatile("" : : "v"(acc2));
+                    A2[i][q] = acc2;
                     if (OUT) {
-                        // keys: window sum << 16 | shift within the chunk (SPLIT: << 8); the smallest wins,
+                        // keys: window sum << 8 | shift within the chunk; the smallest wins,
                         // i.e. the lowest sum and among equals the FIRST shift
                         constexpr int cq = 4 * (q % CH);
                         const u32 lo = (u32)acc, hi = (u32)(acc >> 32);
-                        u32 k0, k1, k2, k3;
-                        if (SPLIT) {
-                            const u32 lo2 = (u32)acc2, hi2 = (u32)(acc2 >> 32);
-                            k0 = (((lo & 0xffffu) + (lo2 & 0xffffu)) << KS) | (u32)cq;
-                            k1 = (((lo >> 16) + (lo2 >> 16)) << KS) | (u32)(cq + 1);
-                            k2 = (((hi & 0xffffu) + (hi2 & 0xffffu)) << KS) | (u32)(cq + 2);
-                            k3 = (((hi >> 16) + (hi2 >> 16)) << KS) | (u32)(cq + 3);
-                        } else {
-                            k0 = (lo << 16) | (u32)cq; k1 = bop_and_or(lo, 0xffff0000u, (u32)(cq + 1));
-                            k2 = (hi << 16) | (u32)(cq + 2); k3 = bop_and_or(hi, 0xffff0000u, (u32)(cq + 3));
-                        }
+                        const u32 lo2 = (u32)acc2, hi2 = (u32)(acc2 >> 32);
+                        u32 k0 = (((lo & 0xffffu) + (lo2 & 0xffffu)) << KS) | (u32)cq;
+                        u32 k1 = (((lo >> 16) + (lo2 >> 16)) << KS) | (u32)(cq + 1);
+                        u32 k2 = (((hi & 0xffffu) + (hi2 & 0xffffu)) << KS) | (u32)(cq + 2);
+                        u32 k3 = (((hi >> 16) + (hi2 >> 16)) << KS) | (u32)(cq + 3);
                         if (q == 0 || q >= q_tail) {        // uniform: shifts < 0 or >= D may be among these
                             const u32 dlim = (u32)g.D;
                             if ((u32)(dc + 4 * q) >= dlim) k0 = 0xffffffffu;
@@ -307,20 +299,9 @@ __global__ __launch_bounds__(64, 2) void k_sad_qs(const u8 *__restrict__ left, c
 // host
 // ---------------------------------------------------------------------------
 
+// the lane shapes the registers of two packed sums per shift allow
 template <int N>
 static const void *sad_qs_ptr(int nql, int px)
-{
-    if (nql == 33 && px == 2) return (const void *)k_sad_qs<N, 33, 2>;
-    if (nql == 17 && px == 2) return (const void *)k_sad_qs<N, 17, 2>;
-    if (nql == 17 && px == 4) return (const void *)k_sad_qs<N, 17, 4>;
-    if (nql == 9 && px == 4) return (const void *)k_sad_qs<N, 9, 4>;
-    if (nql == 5 && px == 4) return (const void *)k_sad_qs<N, 5, 4>;
-    return nullptr;
-}
-
-// the windows with two packed sums per shift (17, 19, 21): the lane shapes their registers allow
-template <int N>
-static const void *sad_qs2_ptr(int nql, int px)
 {
     if (nql == 17 && px == 2) return (const void *)k_sad_qs<N, 17, 2>;
     if (nql == 9 && px == 2) return (const void *)k_sad_qs<N, 9, 2>;
@@ -332,21 +313,17 @@ static const void *sad_qs2_ptr(int nql, int px)
 const void *sm_sad_qs_configure(const sm_plan *plan, int pairs, const void *d_left, const void *d_right, SadGeom *out)
 {
     SadGeom g;
-    g.rr_stride = 0; g.tbl_pad = 0;         // (the SSD kernels')
+    g.tbl_pad = 0;                          // (the SSD kernel's)
     g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts; g.waves = 1;
     const int half = plan->square_width / 2, n = 2 * half + 1;
     g.ghost = plan->border == SM_GHOST;
-    if (n < 3 || n > 21 || g.D > 512 || plan->opt.cost_kernel == 1) return nullptr;     // (512: the entry's own limit)
-    const bool split = n > 15;                      // two packed sums per shift: 8 key bits for the shift
-    if (split && g.D > 240) return nullptr;
+    // (8 key bits for the shift: up to 240 shifts)
+    if (n < 17 || n > 21 || g.D > 240 || plan->opt.cost_kernel == 1) return nullptr;
     const int nq = (g.D + 3 + 3) / 4;               // quads that cover shifts -3 .. D-1
     int nql, px;
     if (nq <= 5) { nql = 5; px = 4; }
-    else if (nq <= 9) { nql = 9; px = split ? 2 : 4; }
-    else if (nq <= 17 || split) { nql = 17; px = split ? 2 : 4; }
-    else { nql = 33; px = 2; }
-    // (an explicit choice applies where both widths are built; anything else is ignored, not launched)
-    if ((plan->opt.cost_pixels_per_lane == 2 || plan->opt.cost_pixels_per_lane == 4) && nql == 17 && !split) px = plan->opt.cost_pixels_per_lane;
+    else if (nq <= 9) { nql = 9; px = 2; }
+    else { nql = 17; px = 2; }
     g.nl = 1; g.log2nl = 0;
     while (g.nl * nql < nq) { g.nl <<= 1; g.log2nl++; }
     g.tw = 4 * px * (16 / g.nl);
@@ -388,16 +365,9 @@ const void *sm_sad_qs_configure(const sm_plan *plan, int pairs, const void *d_le
     g.nql = nql; g.px = px;
     const void *fn = nullptr;
     switch (n) {
-    case 3: fn = sad_qs_ptr<3>(nql, px); break;
-    case 5: fn = sad_qs_ptr<5>(nql, px); break;
-    case 7: fn = sad_qs_ptr<7>(nql, px); break;
-    case 9: fn = sad_qs_ptr<9>(nql, px); break;
-    case 11: fn = sad_qs_ptr<11>(nql, px); break;
-    case 13: fn = sad_qs_ptr<13>(nql, px); break;
-    case 15: fn = sad_qs_ptr<15>(nql, px); break;
-    case 17: fn = sad_qs2_ptr<17>(nql, px); break;
-    case 19: fn = sad_qs2_ptr<19>(nql, px); break;
-    case 21: fn = sad_qs2_ptr<21>(nql, px); break;
+    case 17: fn = sad_qs_ptr<17>(nql, px); break;
+    case 19: fn = sad_qs_ptr<19>(nql, px); break;
+    case 21: fn = sad_qs_ptr<21>(nql, px); break;
     }
     *out = g;
     return fn;

@@ -2,8 +2,8 @@
 //
 // PARITY UNPINNED, as the whole cost mode (top of sm_cost.hip).
 //
-// With the ghost border a window tap outside the image counts 0.  The fast kernels (sm_cost_qs.hip,
-// sm_cost_mfma.hip, sm_cost_ssd.hip) stage zero pixels there, which is the same thing wherever BOTH
+// With the ghost border a window tap outside the image counts 0.  The fast kernels (sm_cost_pc.hip,
+// sm_cost_qs.hip, sm_cost_mfma.hip) stage zero pixels there, which is the same thing wherever BOTH
 // images are outside -- above, below and right of the image -- but not left of it: the left pixel is
 // outside, the right one at x' + d is not.  Those taps exist for the columns x < half only, a strip of
 // half x H pixels (0.13 % of a 4K image at 11 x 11) that the fast kernels leave out.  Until round 4 the
@@ -165,7 +165,9 @@ static const void *strip_ptr(bool ssd, int ns)
     return ns == 1 ? (const void *)k_cost_strip<H, false, 1> : (const void *)k_cost_strip<H, false, 2>;
 }
 
-// the strip of the fast kernels' launches; returns -1 if this shape is not built (the caller runs the general kernel on it)
+// the strip of the fast kernels' launches.  Built for every half-window and shift count a fast kernel takes (SAD: half
+// up to 10, SSD: up to 5; at most 512 shifts), and its LDS need is at most ~34 KB (half = 10, D = 512, 32-row tiles):
+// a shape it cannot take is an error, not a fall-back.
 int sm_cost_strip_launch(const sm_plan *plan, const uint8_t *d_left, const uint8_t *d_right, int cost, int pairs,
                          int32_t *d_web, int32_t *d_best, hipStream_t stream)
 {
@@ -173,7 +175,9 @@ int sm_cost_strip_launch(const sm_plan *plan, const uint8_t *d_left, const uint8
     const bool ssd = cost == SM_COST_SSD;
     StripGeom g;
     g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts;
-    if (half < 1 || half > 10 || g.D > 512 || (ssd && half > 5) || plan->opt.cost_kernel == 3) return -1;
+    if (half < 1 || half > 10 || g.D > 512 || (ssd && half > 5))
+        return sm_fail(SM_ERR_ARG, "sm_cost_wta: no ghost-border strip kernel for %dx%d windows, %d shifts (%s)",
+                       2 * half + 1, 2 * half + 1, g.D, ssd ? "SSD" : "SAD");
     const int ns = (g.D + 255) / 256;
     const int nwd = (2 * half + 3) / 4;
     // a thread reads dwords (d >> 2) .. (d >> 2) + nwd of a right row, d < 256 ns
@@ -185,7 +189,8 @@ int sm_cost_strip_launch(const sm_plan *plan, const uint8_t *d_left, const uint8
     g.tile_h = th;
     g.nsr = th + 2 * half;
     const size_t lds = 4 * ((size_t)g.nsr * (nwd + g.rw) + (size_t)th * half * 4);
-    if (lds > 64 * 1024) return -1;
+    if (lds > 64 * 1024)
+        return sm_fail(SM_ERR_ARG, "sm_cost_wta: the ghost-border strip needs %zu bytes of LDS", lds);
     const void *fn = nullptr;
     switch (half) {
     case 1: fn = strip_ptr<1>(ssd, ns); break;
@@ -199,7 +204,7 @@ int sm_cost_strip_launch(const sm_plan *plan, const uint8_t *d_left, const uint8
     case 9: fn = strip_ptr<9>(ssd, ns); break;
     case 10: fn = strip_ptr<10>(ssd, ns); break;
     }
-    if (!fn) return -1;
+    if (!fn) return sm_fail(SM_ERR_ARG, "sm_cost_wta: no ghost-border strip kernel for half-window %d", half);
     void *args[] = {(void *)&d_left, (void *)&d_right, (void *)&d_web, (void *)&d_best, (void *)&g};
     const hipError_t e = hipLaunchKernel(fn, dim3(1, (g.h + th - 1) / th, pairs), dim3(256), args, lds, stream);
     if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "sm_cost_wta: %s", hipGetErrorString(e));

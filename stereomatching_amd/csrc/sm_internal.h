@@ -110,6 +110,7 @@ struct sm_plan {
     // or the first call that needs them; part of the workspace from then on
     u32 *d_ext_lr;       // mirrored packed images, d_ext's layout: side 0 = mirror(right), side 1 = mirror(left)
     i32 *d_web_lr;       // right-reference map of sm_run_lr in mirrored order: max_pairs * W * H
+    int cost_lds_raised; // sm_cost_wta: the LDS limit of this plan's four-wave SAD kernel is raised (on `device`)
     char describe[512];
 };
 

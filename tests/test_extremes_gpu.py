@@ -217,11 +217,10 @@ def check_cost(hip, sw, d, mode, cost, option_sets):
 @pytest.mark.parametrize("d", [1, 31, 32, 33, 64, 65, 224, 225, 255, 256])
 @pytest.mark.parametrize("sw", [3, 5, 7, 9, 11])
 def test_ssd_kernels_at_the_extremes(hip, sw, d, mode):
-    """k_ssd_mfma<N, NB> (the plan's choice; NB = 1 .. 9, so that bands cross position 256 from D = 225 on), the
-    byte-dot kernel (cost_kernel = 2), the general kernel (1) and, in ghost mode, the border strip both by
-    k_cost_strip (the plan's) and by the general masked kernel (3): the largest sums N^2 x 65025 and every shift
-    tying, where the first must win -- across the split of positions 0 .. 255 and 256 .."""
-    sets = [None, dict(cost_kernel=2), dict(cost_kernel=1)] + ([dict(cost_kernel=3)] if mode == "ghost" else [])
+    """k_ssd_mfma<N, NB> (the plan's choice; NB = 1 .. 9, so that bands cross position 256 from D = 225 on; in ghost
+    mode k_cost_strip behind it) and the general masked kernel (cost_kernel = 1) on the whole image: the largest sums
+    N^2 x 65025 and every shift tying, where the first must win -- across the split of positions 0 .. 255 and 256 .."""
+    sets = [None, dict(cost_kernel=1)]
     names, ob = check_cost(hip, sw, d, mode, "ssd", sets)
     if mode == "toroidal":
         assert (ob[names.index("black_white")] == sw * sw * 65025).all()
@@ -230,12 +229,10 @@ def test_ssd_kernels_at_the_extremes(hip, sw, d, mode):
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("sw", [3, 5, 7, 9, 11, 13, 15, 17, 19, 21])
 def test_sad_kernels_at_the_extremes(hip, sw, mode):
-    """the quad-SAD / prefix-chain kernels in workgroups of 1, 2 and 4 waves, the every-row kernel (cost_kernel =
-    4) and in ghost mode the general strip (3), at 1, 33 and the most shifts they are built for (240 from 17 x 17
-    on: the 8-bit shift field of the split keys; 500 below)"""
-    sets = [dict(cost_kernel=ck, cost_workgroup_waves=wv) for ck in (0, 4) for wv in (1, 2, 4)]
-    if mode == "ghost":
-        sets.append(dict(cost_kernel=3))
+    """the quad-SAD / prefix-chain kernels in workgroups of 1, 2 and 4 waves (in ghost mode k_cost_strip behind them)
+    and the general masked kernel (cost_kernel = 1) on the whole image, at 1, 33 and the most shifts they are built
+    for (240 from 17 x 17 on: the 8-bit shift field of the split keys; 500 below)"""
+    sets = [dict(cost_kernel=0, cost_workgroup_waves=wv) for wv in (1, 2, 4)] + [dict(cost_kernel=1)]
     for d in (1, 33, 240 if sw > 15 else 500):
         names, ob = check_cost(hip, sw, d, mode, "sad", sets)
         if mode == "toroidal":

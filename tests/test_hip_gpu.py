@@ -987,9 +987,10 @@ SAD_QS = [  # (w, h, D, S): quads per lane / shift-lanes / pixels per lane of th
 @pytest.mark.parametrize("cost", ["sad", "ssd"])
 @pytest.mark.parametrize("w,h,d,sw", SAD_QS)
 def test_quad_sad_kernel_matches_own_oracle(hip, mode, tile_h, cost, w, h, d, sw):
-    """k_sad_qs / k_ssd_mfma / k_ssd_dot: every shape of (quads per lane, shift-lanes), windows 3 .. 21 (SAD from 17 on with
-    two packed sums per shift; SSD: .. 11, the larger ones take the general kernel), both borders, tiles of 3 rows (several slides per wave, a
-    ragged last tile) and the plan's own height, unaligned input"""
+    """k_sad_pc / k_sad_qs / k_ssd_mfma: every shape of (quads per lane, shift-lanes), windows 3 .. 21 (SAD from 17 on with
+    two packed sums per shift; SSD: .. 11, the larger ones take the general kernel), both borders (ghost: k_cost_strip behind
+    the launch), tiles of 3 rows (several slides per wave, a ragged last tile) and the plan's own height, unaligned input,
+    against the CPU definition and the general masked kernel (cost_kernel = 1) on the whole image"""
     left, right = make_pair(w, h, d, seed=w * 3 + d, kind="noise" if (w + d) % 3 == 0 else "scene")
     if (w + h) % 2:             # saturate some pixels: 0 and 255 are the masked-SAD corner cases
         left[::3, ::5] = 0; left[1::4, 2::7] = 255; right[::5, ::3] = 255; right[2::3, 1::4] = 0
@@ -1003,16 +1004,6 @@ def test_quad_sad_kernel_matches_own_oracle(hip, mode, tile_h, cost, w, h, d, sw
     web2, best2 = gen.cost_wta(dev(left), dev(right), cost)
     assert torch.equal(web2, web) and torch.equal(best2, best)
     plan.close(); gen.close()
-    if mode == "ghost":         # the border strip x < half: k_cost_strip by default, the general masked kernel on request
-        old = hip.StereoPlan(w, h, d, sw, mode, options=dict(cost_kernel=3, cost_tile_h=tile_h))
-        web4, best4 = old.cost_wta(dev(left), dev(right), cost)
-        assert torch.equal(web4, web) and torch.equal(best4, best)
-        old.close()
-    if cost == "ssd":           # the plan's choice is the matrix-core kernel (k_ssd_mfma); the byte-dot kernel on request
-        dot = hip.StereoPlan(w, h, d, sw, mode, options=dict(cost_kernel=2, cost_tile_h=tile_h))
-        web3, best3 = dot.cost_wta(dev(left), dev(right), cost)
-        assert torch.equal(web3, web) and torch.equal(best3, best)
-        dot.close()
 
 
 @pytest.mark.parametrize("mode", ["toroidal", "ghost"])
@@ -1058,9 +1049,10 @@ def test_quad_sad_unaligned_images_and_batches(hip, cost):
 def test_cost_kernels_random_shapes_match_own_oracle(hip):
     """A seeded sweep of 160 random shapes through sm_cost_wta: widths from 8 to 300 (multiples of 4 and
     not), heights down to the window, 1 .. 300 shifts, every window 3 .. 17, both borders and costs, tile
-    heights 0 (the plan's) .. 9, images with saturated pixels -- the index arithmetic of the quad-SAD and
-    byte-dot kernels (aligned window starts, shift quads, ghost strip, ragged last tiles) against the
-    build's own CPU definition."""
+    heights 0 (the plan's) .. 9, workgroups of 1, 2 and 4 waves (also where the image is narrower than
+    that), images with saturated pixels -- the index arithmetic of the quad-SAD and matrix-core kernels
+    (aligned window starts, shift quads, ghost strip, ragged last tiles) against the build's own CPU
+    definition; a share of the cases on the general masked kernel (cost_kernel = 1)."""
     # (SM_SOAK_COST=<cases> [SM_SOAK_SEED=<seed>]: the same sweep, longer and wider, as a one-off soak)
     soak = int(os.environ.get("SM_SOAK_COST", "0"))
     rng = np.random.default_rng(int(os.environ.get("SM_SOAK_SEED", "1")) + 977 if soak else 20261004)
@@ -1080,9 +1072,8 @@ def test_cost_kernels_random_shapes_match_own_oracle(hip):
         if case % 4 == 0:
             left[rng.random((h, w)) < 0.2] = 0
             right[rng.random((h, w)) < 0.2] = 255
-        ck = 2 if cost == "ssd" and case % 3 == 1 else 0         # SSD: a third of the cases on the byte-dot kernel
-        if cost == "sad" and case % 5 == 2:
-            ck = 4                                               # SAD: a fifth on the round-4 kernel (every window row from scratch)
+        # the general masked kernel: SSD a third of the cases, SAD a fifth
+        ck = 1 if (cost == "ssd" and case % 3 == 1) or (cost == "sad" and case % 5 == 2) else 0
         wv = int(rng.choice([0, 0, 1, 2, 4]))                    # waves per workgroup sharing the staged rows (round 5)
         plan = hip.StereoPlan(w, h, d, sw, mode, options=dict(cost_tile_h=th, cost_kernel=ck, cost_workgroup_waves=wv))
         web, best = plan.cost_wta(dev(left), dev(right), cost)
@@ -1100,10 +1091,11 @@ def test_cost_workgroups_of_several_waves_share_their_rows(hip, mode, cost):
     """k_sad_pc / k_ssd_mfma in workgroups of 1, 2 and 4 waves (round 5: the waves stage one set of rows and share it --
     one right-image span for all of them): images a few workgroups wide and not a multiple of any workgroup width,
     shift counts that give 1 .. 16 shift lanes per pixel group (SAD) and 1 .. 9 position blocks (SSD), tiles of the
-    plan's height and of 5 rows, web and best against the CPU definition; the plan's own choice equals them all."""
+    plan's height and of 5 rows, web and best against the CPU definition; the plan's own choice equals them all.
+    The last image is narrower than a four-wave workgroup: where an explicit width cannot apply, the plan's own is taken."""
     rng = np.random.default_rng(61)
     for sw, d, w, h in ((9, 128, 700, 41), (11, 256, 452, 33), (7, 64, 1030, 27), (5, 16, 530, 19), (13, 200, 390, 29),
-                        (3, 500 if cost == "sad" else 250, 300, 17)):
+                        (3, 500 if cost == "sad" else 250, 300, 17), (9, 100, 60, 23)):
         left = rng.integers(0, 256, (h, w), dtype=np.uint8)
         right = np.roll(left, int(rng.integers(0, min(d, w))), 1)
         right = np.clip(right.astype(np.int32) + rng.integers(-2, 3, (h, w)), 0, 255).astype(np.uint8)
@@ -1125,7 +1117,7 @@ def test_ssd_matrix_core_kernel_every_instantiation(hip, mode):
     """k_ssd_mfma<N, NB>: every window 3 .. 11 x every block count 1 .. 9, with the shift counts either side of
     each block boundary (the band's partial blocks: D a multiple of 32 takes the complementary-triangle masks,
     anything else the per-key compares on the last two blocks), web and best, against the CPU definition and the
-    byte-dot kernel; ghost mode adds k_cost_strip<half, SSD> behind it."""
+    general masked kernel (cost_kernel = 1); ghost mode adds k_cost_strip<half, SSD> behind it."""
     rng = np.random.default_rng(41)
     for sw in (3, 5, 7, 9, 11):
         for d in (1, 2, 31, 32, 33, 34, 64, 65, 95, 96, 97, 128, 129, 160, 161, 191, 192, 193, 224, 225, 255, 256):
@@ -1140,14 +1132,17 @@ def test_ssd_matrix_core_kernel_every_instantiation(hip, mode):
             ob, ow = oracle.cost_hot_path(left, right, d, sw, mode, "ssd")
             assert np.array_equal(host(web)[0], ow), (mode, sw, d)
             assert np.array_equal(host(best)[0], ob), (mode, sw, d)
-            plan.close()
+            gen = hip.StereoPlan(w, h, d, sw, mode, options=dict(cost_kernel=1))
+            web2, best2 = gen.cost_wta(dev(left), dev(right), "ssd")
+            assert torch.equal(web2, web) and torch.equal(best2, best), (mode, sw, d)
+            plan.close(); gen.close()
 
 
 @pytest.mark.parametrize("cost", ["sad", "ssd"])
 def test_ghost_strip_kernel_every_instantiation(hip, cost):
     """k_cost_strip<half, SSD, slots>: every half-window 1 .. 10 (SSD: .. 5), one and two shifts per thread,
     images no wider than the window, heights around its tile boundaries, against the CPU definition and the
-    general masked kernel on the same columns (cost_kernel = 3)"""
+    general masked kernel (cost_kernel = 1, which computes the same columns with its masked path)"""
     rng = np.random.default_rng(43)
     for half in range(1, 11 if cost == "sad" else 6):
         sw = 2 * half + 1
@@ -1161,10 +1156,10 @@ def test_ghost_strip_kernel_every_instantiation(hip, cost):
             ob, ow = oracle.cost_hot_path(left, right, d, sw, "ghost", cost)
             assert np.array_equal(host(web)[0], ow), (cost, half, d, w, h)
             assert np.array_equal(host(best)[0], ob), (cost, half, d, w, h)
-            old = hip.StereoPlan(w, h, d, sw, "ghost", options=dict(cost_kernel=3))
-            web2, best2 = old.cost_wta(dev(left), dev(right), cost)
+            gen = hip.StereoPlan(w, h, d, sw, "ghost", options=dict(cost_kernel=1))
+            web2, best2 = gen.cost_wta(dev(left), dev(right), cost)
             assert torch.equal(web2, web) and torch.equal(best2, best)
-            plan.close(); old.close()
+            plan.close(); gen.close()
 
 
 @pytest.mark.parametrize("cfg,cost", [("C3", "sad"), ("C5", "sad"), ("C3", "ssd"), ("C5", "ssd")])
@@ -1420,7 +1415,9 @@ def test_result_buffers_are_validated(hip):
 
 
 def test_plan_on_another_device(hip):
-    """sm_plan_create(device = k > 0): the same parity check on the last visible device."""
+    """sm_plan_create(device = k > 0): the same parity check on the last visible device; and the SAD cost mode at C5
+    (4K, 256 shifts, 11 x 11, ghost), whose plan takes four-wave k_sad_pc workgroups over 64 KB of LDS (64-row tiles:
+    ~66 KB) -- the raised LDS limit must hold on device k after a plan on device 0 has raised it there."""
     if torch.cuda.device_count() < 2:
         pytest.skip("one visible device")
     k = torch.cuda.device_count() - 1
@@ -1436,6 +1433,18 @@ def test_plan_on_another_device(hip):
     ob, ow = oracle.hot_path(oel, oer, d, sw, "toroidal")
     assert np.array_equal(host(web)[0], ow) and np.array_equal(host(best)[0], ob)
     plan.close()
+    w, h, d, sw, mode = CONFIGS["C5"]
+    left, right = make_pair(w, h, d, seed=3)
+    maps = {}
+    for dv, opts in ((0, None), (k, None), (k, dict(cost_kernel=1))):
+        plan = hip.StereoPlan(w, h, d, sw, mode, device=dv, options=opts)
+        with torch.cuda.device(dv):
+            web, best = plan.cost_wta(torch.from_numpy(left).cuda(dv), torch.from_numpy(right).cuda(dv), "sad")
+            torch.cuda.synchronize(dv)
+        maps[dv, opts is None] = (host(web), host(best))
+        plan.close()
+    for key in ((k, True), (k, False)):
+        assert np.array_equal(maps[key][0], maps[0, True][0]) and np.array_equal(maps[key][1], maps[0, True][1]), key
 
 
 def test_bench_two_ranks_on_one_gpu():
@@ -1559,7 +1568,8 @@ def test_plan_options_struct_size_rules(hip):
     left, right = make_pair(200, 50, 64, seed=3)
     for cost in ("sad", "ssd"):
         ob, ow = oracle.cost_hot_path(left, right, 64, 9, "toroidal", cost)
-        for opts in (dict(cost_tile_h=100000), dict(cost_pixels_per_lane=7), dict(cost_pixels_per_lane=-3, cost_tile_h=1)):
+        for opts in (dict(cost_tile_h=100000), dict(cost_pixels_per_lane=7), dict(cost_pixels_per_lane=-3, cost_tile_h=1),
+                     dict(cost_workgroup_waves=3)):
             plan = hip.StereoPlan(200, 50, 64, 9, "toroidal", options=opts)
             web, best = plan.cost_wta(dev(left), dev(right), cost)
             torch.cuda.synchronize()

@@ -73,8 +73,9 @@ def test_sweep_against_the_definition(hip, mode, cost, n, d):
         plan.close()
 
 
-KERNEL_CHOICES = ([("sad", dict(cost_kernel=k)) for k in range(5)] + [("ssd", dict(cost_kernel=k)) for k in range(5)] +
-                  [("sad", dict(cost_kernel=k, cost_workgroup_waves=wv)) for k in (0, 4) for wv in (1, 2, 4)])
+# the plan's choice, the general masked kernel (cost_kernel = 1) and the fast kernels in workgroups of 1, 2 and 4 waves
+KERNEL_CHOICES = ([(c, dict(cost_kernel=k)) for c in ("sad", "ssd") for k in (0, 1)] +
+                  [(c, dict(cost_kernel=0, cost_workgroup_waves=wv)) for c in ("sad", "ssd") for wv in (1, 2, 4)])
 
 
 @pytest.mark.parametrize("cost,opts", KERNEL_CHOICES,

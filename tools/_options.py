@@ -14,7 +14,6 @@ NAMES = {
     "SM_PATTERN": lambda v: {"priority_pattern": int(v, 16)},
     "SM_EDGES1": lambda v: {"edge_kernel": int(v)},
     "SM_TIMING_RECORDS": lambda v: {"timing_by_records": int(v)},
-    "SM_COST_PX": lambda v: {"cost_pixels_per_lane": int(v)},
     "SM_COST_TILE_H": lambda v: {"cost_tile_h": int(v)},
     "SM_COST_KERNEL": lambda v: {"cost_kernel": int(v)},
     "SM_PRIO_CLASS": lambda v: {"priority_class": int(v)},

@@ -6,7 +6,7 @@ import torch
 from stereomatching_amd import pipeline
 from stereomatching_amd.synth import CONFIGS, make_pair
 
-from tools._options import from_env          # SM_COST_PX / SM_COST_TILE_H / SM_COST_KERNEL in this tool's environment
+from tools._options import from_env          # SM_COST_TILE_H / SM_COST_KERNEL / SM_COST_WAVES in this tool's environment
 import re
 for a in sys.argv[1:]:
     m = re.fullmatch(r"(\d+)x(\d+)x(\d+)x(\d+)(g?)", a)
