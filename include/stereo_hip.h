@@ -139,7 +139,7 @@ typedef struct sm_plan_options {
     int shifts_per_lane;        /* bit-sliced kernel: 4, 8 or 16 */
     int workgroup_waves;        /* bit-sliced kernel: 1 = one-wave workgroups, 2 = two-wave workgroups (shared warm-up) */
     int no_two_wave_cap;        /* 1 = never launch the variant capped at two waves per SIMD */
-    unsigned priority_pattern;  /* bit-sliced kernel: time-sliced wave priority, bit k = favoured slot parity in unit k */
+    unsigned priority_pattern;  /* no effect; kept for the struct layout */
     int edge_kernel;            /* 1 = the one-pixel-per-lane edge kernel even where the four-pixel one applies */
     int timing_by_records;      /* 1 = sm_plan_time_kernels brackets launches with event records instead of
                                  *     reading the dispatch's own time stamps */
@@ -147,18 +147,14 @@ typedef struct sm_plan_options {
     int cost_tile_h;            /* SAD / SSD kernels: output rows per wave */
     int cost_kernel;            /* 1 = the general masked kernel even where the quad-SAD / MFMA kernels apply;
                                    any other value = the plan's choice */
-    int priority_class;         /* bit-sliced kernel: which of a SIMD's two waves a priority slice favours is told by
-                                 * 1 = the wave slot's parity, 2 = the parity of the workgroup's slot on its CU (the two
-                                 * waves of a two-wave workgroup are then favoured together); 0 = the plan's choice */
-    int priority_on_change;     /* bit-sliced kernel: 1 = s_setprio only when the wanted priority changes, 2 = once per row;
-                                 * 0 = the plan's choice */
+    int priority_class;         /* no effect; kept for the struct layout */
+    int priority_on_change;     /* no effect; kept for the struct layout */
     int lane_merge;             /* bit-sliced kernel: how the lanes that split a word's shift range are merged:
                                  * 1 = per row with DPP, 2 = through LDS every four rows (where >= 4 lanes share a word);
                                  * 0 = the plan's choice */
     int no_four_shift_lanes;    /* bit-sliced kernel: 1 = never 4 shifts per lane (the plan's own choice is between 16, 8
                                  * and 4); shifts_per_lane = 4 forces them where they are built */
-    int priority_unit_log2;     /* bit-sliced kernel: log2 of the priority schedule's unit in shader-clock cycles (8 .. 20;
-                                 * bit k of priority_pattern covers the k-th unit); 0 = the plan's choice */
+    int priority_unit_log2;     /* no effect; kept for the struct layout */
     int cost_workgroup_waves;   /* SAD kernel of round 5 (prefix chains) and SSD matrix-core kernel: 1, 2 or 4 waves per
                                  * workgroup sharing the staged rows; 0 = the plan's choice */
 } sm_plan_options;

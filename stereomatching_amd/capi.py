@@ -47,7 +47,8 @@ class Geometry(C.Structure):
 
 
 class PlanOptions(C.Structure):
-    """sm_plan_options of include/stereo_hip.h (every field 0 = the plan's own choice)"""
+    """sm_plan_options of include/stereo_hip.h (every field 0 = the plan's own choice).  cost_pixels_per_lane
+    and the four priority_* fields have no effect; they are kept for the struct layout."""
     _fields_ = [("struct_size", C.c_int), ("kernel_family", C.c_int), ("tile_h", C.c_int),
                 ("shifts_per_lane", C.c_int), ("workgroup_waves", C.c_int), ("no_two_wave_cap", C.c_int),
                 ("priority_pattern", C.c_uint), ("edge_kernel", C.c_int), ("timing_by_records", C.c_int),

@@ -324,9 +324,7 @@ __global__ __launch_bounds__(256) void k_edges_ext(const u8 *__restrict__ src_l,
 // bottom sums of row y are the top sums of row y+2); column sums serve as `left`
 // of one pixel and `right` of another.  A lane's 4 decisions form a nibble; 8
 // adjacent lanes OR their nibbles together (DPP) into one ext word.
-#ifndef SM_EDGE4_ROWS
-#define SM_EDGE4_ROWS 4
-#endif
+#define SM_EDGE4_ROWS 4   // ext rows of a wave's strip (8: profiles/r05/ab_edge_strips_rejected.txt)
 template <bool GHOST, bool TABLES, bool STACKED = false>
 __global__ __launch_bounds__(256) void k_edges_ext4(const u8 *__restrict__ src_l,
                                                     const u8 *__restrict__ src_r,

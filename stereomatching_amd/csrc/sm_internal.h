@@ -58,10 +58,8 @@ struct MatchGeom {
     int lds_bytes;
     int cap2;            // bit-sliced kernel: launch the two-waves-per-SIMD variant
     int duo;             // bit-sliced kernel: two-wave workgroups of 2 * tile_h rows (shared warm-up)
-    unsigned prio_pattern;   // bit-sliced kernel: the time-sliced priority schedule (sm_match_bs_kernel.h)
-    int prio_unit;           // ... log2 of the schedule's unit in shader-clock cycles (14: 16384 cycles, ~8 us)
-    int prio_shift;          // ... the HW_ID bit that tells a SIMD's two waves apart: 0 wave slot, 16 workgroup slot (TG_ID)
-    int prio_on_change;      // ... s_setprio only when the wanted priority changes (else once per row)
+    int unused[4];       // (where the retired priority fields were: the kernel arguments 16 bytes shorter measured
+                         //  2 % slower in the C1 step, edges + match, same device; no kernel reads these words)
     int xmerge;          // bit-sliced kernel: the shift lanes of a word are merged through LDS every 4 rows (nl >= 4)
     int xm_off;          // ... word offset in LDS where the exchange slots of a two-wave workgroup meet and the
                          //     merge buffers lie (wave 0's from here up, wave 1's from here down; a lone wave's from here up)
@@ -164,7 +162,6 @@ void sm_lr_free(sm_plan *plan);                       // sm_lr.hip: sm_plan_dest
 // sm_match_bs.hip (bit-sliced kernel; nullptr if not built for this window)
 const void *sm_bs_kernel_ptr(int n, int ds, bool fulld, bool ghost, bool cap2, bool duo = false);
 int sm_bs_default_ds(int n);
-unsigned sm_bs_default_pattern(bool duo);
 // what ONE launch adds to the plan's geometry: passed by value, the plan is not modified
 struct MatchLaunch {
     MatchGeom g;                        // plan->g with vec_ok / web_bytes of this launch

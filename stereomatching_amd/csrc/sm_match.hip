@@ -504,11 +504,7 @@ int sm_match_configure(sm_plan *plan)
         g.ext_image_words = (long long)g.ext_words * g.ext_rows;
         g.tile_h = g.tw = g.runs = g.nl = g.log2nl = g.threads = g.ds = 0;
         g.plw = g.prw = g.nsr = g.tiles_x = g.tiles_y = g.vec_ok = g.lds_bytes = g.cap2 = g.duo = 0;
-        g.prio_pattern = 0;
-        g.prio_unit = 14;
         g.xmerge = g.xm_off = g.xm_words = 0;
-        g.prio_shift = 0;
-        g.prio_on_change = 0;
         g.edge_words_l = g.edge_words_r = g.ext_words;
         snprintf(plan->describe, sizeof plan->describe,
                  "generic kernel (n=%d, D=%d): 1 lane/pixel, direct window sums", g.n, D);
@@ -743,48 +739,18 @@ int sm_match_configure(sm_plan *plan)
     }
     configure_best(ds, gsel, rws);
     g = gsel;
-#ifndef SM_EDGE_TRIM
-#define SM_EDGE_TRIM 1      // 0: edges for every ext column (same-device A/B builds)
-#endif
-    g.edge_words_l = g.edge_words_r = g.ext_words;
-    if (SM_EDGE_TRIM) {
-        g.edge_words_l = std::min(g.ext_words, (g.pad_l + W + g.half - 1) / 32 + 1);
-        g.edge_words_r = std::min(g.ext_words, (g.pad_l + W + g.half + D - 2) / 32 + 1);
-    }
-    g.prio_pattern = sm_bs_default_pattern(g.duo != 0);
-    g.prio_unit = 14;
-    // The launches of the 8- and 4-shifts-per-lane builds are short (a single small pair: 16 us; the reference's
-    // defaults at 4K: 58 us): with slices of four units (~31 us) the favoured wave of a SIMD pair never or hardly
-    // changes, and the other one finishes alone.  They swap every unit (~8 us): C2's match launch 17.1 -> 15.6 us,
-    // step -4 %; 21 x 21 / 30 shifts at 4K -1..2 %; the long launches (16 shifts per lane) lose 2-3 % with it and
-    // keep the four-unit slices (profiles/r04/ab_prio_unit.txt).
-    if (bs && g.ds < 16) g.prio_pattern = 0xAAAAAAAAu;
-    if (plan->opt.priority_pattern) g.prio_pattern = plan->opt.priority_pattern;   // tuning
-    if (plan->opt.priority_unit_log2 >= 8 && plan->opt.priority_unit_log2 <= 20) g.prio_unit = plan->opt.priority_unit_log2;
-    // the bit that tells a SIMD's two waves apart (see the kernel): the wave slot.  The workgroup's slot on its
-    // CU (priority_class 2) wins 1-2 % (6 % at 21 x 21) when the match launch follows ITSELF, as in a timing loop
-    // of match launches -- and LOSES 5 % in the real step, where it follows the edge kernel and its workgroups
-    // find other slots (tools/sustained_ab.sh, profiles/r03/sustained_ab.txt): an option for tuning, not the default
-    g.prio_shift = 0;
-    if (plan->opt.priority_class == 2) {
-        // the workgroup's slot tells a SIMD's two waves apart only for two-wave workgroups of a launch that fits
-        // the chip in ONE round (later workgroups land in whatever slot is free): anything else keeps the wave slot
-        const long long tiles = (long long)g.tiles_x * g.tiles_y * plan->max_pairs;
-        if (bs && g.duo && tiles <= 4ll * cus) g.prio_shift = 16;                           // tuning
-    }
-    g.prio_on_change = plan->opt.priority_on_change == 1;                                 // tuning (default: once per row)
+    g.edge_words_l = std::min(g.ext_words, (g.pad_l + W + g.half - 1) / 32 + 1);
+    g.edge_words_r = std::min(g.ext_words, (g.pad_l + W + g.half + D - 2) / 32 + 1);
 
     snprintf(plan->describe, sizeof plan->describe,
              "%s (n=%d, D=%d, %s): tile %dx%d px, %d threads "
-             "(%d runs x %d shift-lanes of %d), grid %dx%d, LDS %d B/wg%s%s%s, ext %dx%d words",
+             "(%d runs x %d shift-lanes of %d), grid %dx%d, LDS %d B/wg%s%s, ext %dx%d words",
              bs ? "bit-sliced kernel" : kernel == SM_KERNEL_A ? "tiled kernel A"
                 : kernel == SM_KERNEL_B ? "tiled kernel B" : "tiled kernel C",
              g.n, D, ghost ? "ghost" : "toroidal",
              g.tw, g.duo ? 2 * g.tile_h : g.tile_h, g.threads, g.runs, g.nl, g.ds, g.tiles_x, g.tiles_y, g.lds_bytes,
              g.duo ? ", two-wave workgroups" : g.cap2 ? ", 2 waves/SIMD variant" : "",
              g.xmerge ? ", lanes merged through LDS" : "",
-             g.prio_shift ? ", favoured by workgroup slot"
-                          : plan->opt.priority_class == 2 ? ", priority class 2 not applicable: by wave slot" : "",
              g.ext_words, g.ext_rows);
     return SM_OK;
 }

@@ -43,9 +43,7 @@
 #define SM_BS_CAT2(a, b) a##b
 #define SM_BS_CAT(a, b) SM_BS_CAT2(a, b)
 
-#ifndef SM_BS_WAVES
 #define SM_BS_WAVES 2   // min waves per SIMD: keeps VGPR + AGPR <= 256 (one AGPR more halves the occupancy)
-#endif
 
 // Diagnostic build only (-DSM_STAMPS, tools/wave_timeline.py): every wave records
 // when it started, finished staging, finished its warm-up rows and ended (constant
@@ -94,7 +92,7 @@ __device__ __forceinline__ u32 alignbit(u32 hi, u32 lo, u32 sh)
 }
 
 // ---------------------------------------------------------------------------
-// LDS reads that stay in flight (SM_BS_PREFETCH).  Left to itself the compiler issues a
+// LDS reads that stay in flight.  Left to itself the compiler issues a
 // row's ds_reads right in front of their first use and the wave then sits in s_waitcnt
 // for the LDS latency, twice per output row, with one other wave on the SIMD to cover
 // for it.  These reads are issued one whole row EARLIER: VOLATILE loads, which the
@@ -113,13 +111,6 @@ __device__ __forceinline__ u32 alignbit(u32 hi, u32 lo, u32 sh)
 // Same speed: C3 93.2 vs 93.0 us, C5 193.3 vs 193.3, 21 x 21 at 4K 78.5 vs 78.8, same
 // device, profiles/r02/ab_prefetch_volatile.txt.)
 // ---------------------------------------------------------------------------
-#ifndef SM_BS_PREFETCH
-#define SM_BS_PREFETCH 1
-#endif
-// the shift lanes of a word merged through LDS every four rows (g.xmerge) instead of per row with DPP
-#ifndef SM_BS_XMERGE
-#define SM_BS_XMERGE 1
-#endif
 typedef unsigned long long u64;
 struct RawRow { u64 l01; u32 l2; u64 r01, r23; };      // 3 left words, 4 right words
 struct RawCentre { u32 l; u64 r01; u32 r2; };          // centre word, 3 right words
@@ -141,66 +132,18 @@ __device__ __forceinline__ void lds_issue(RawCentre &o, u32 aL, u32 aR)
     o.r2 = *(lds_vu32 *)(uintptr_t)(aR + 8);
 }
 
-// result stores: 0 = nt (streaming hint, the line still stays in L2), 1 = sc1
-// (write-through: the bytes leave L2 while the kernel runs instead of in one
-// write-back burst when it ends), 2 = plain
-#ifndef SM_BS_STORE
-#define SM_BS_STORE 1   // measured, same device: sc1 1 % faster than nt at C3 / C4 x 8, 4 % at C2
-#endif
+// result stores are sc1 (write-through: the bytes leave L2 while the kernel runs instead of in
+// one write-back burst when it ends).  Measured, same device: 1 % faster than nt at C3 / C4 x 8,
+// 4 % at C2 (profiles/r04/ab_store_flavour.txt)
 typedef int v4i __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void store_map4(i32 *p, v4i v)
 {
-#if SM_BS_STORE == 1
     // (the s_nop belongs to the statement: the compiler does not see a store of more than 8 bytes
     // here, so nothing else keeps a VALU write of the data registers one wait state away from it)
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
-#elif SM_BS_STORE == 2
-    *reinterpret_cast<v4i *>(p) = v;
-#else
-    __builtin_nontemporal_store(v, reinterpret_cast<v4i *>(p));
-#endif
 }
 
 constexpr int bits_for(int v) { int b = 0; while ((1 << b) <= v) b++; return b; }   // v < 2^b
-
-// ---------------------------------------------------------------------------
-// carry-save tree: N one-bit inputs -> their count on HB planes.  Everything
-// about the wiring is known at compile time; after unrolling only the
-// v_bitop3 / v_xor / v_and of the adders remain (5 full + 2 half adders for 9).
-// ---------------------------------------------------------------------------
-template <int N, int HB>
-__device__ __forceinline__ void count_bits(const u32 (&x)[N], u32 (&h)[HB])
-{
-    u32 q[2 * N + 2];          // wires of the current weight, used as a queue
-    int head = 0, tail = 0;
-#pragma unroll
-    for (int i = 0; i < N; i++) q[tail++] = x[i];
-#pragma unroll
-    for (int w = 0; w < HB; w++) {
-        u32 nx[N + 1];         // carries: wires of the next weight
-        int nn = 0;
-#pragma unroll
-        for (int it = 0; it < N; it++) {
-            if (tail - head >= 3) {
-                const u32 a = q[head], b = q[head + 1], c = q[head + 2];
-                head += 3;
-                q[tail++] = bop<BOP_XOR3>(a, b, c);
-                nx[nn++] = bop<BOP_MAJ>(a, b, c);
-            }
-        }
-        if (tail - head == 2) {
-            const u32 a = q[head], b = q[head + 1];
-            head += 2;
-            q[tail++] = a ^ b;
-            nx[nn++] = a & b;
-        }
-        h[w] = tail - head == 1 ? q[head] : 0u;
-        head = tail = 0;
-#pragma unroll
-        for (int i = 0; i < N + 1; i++)
-            if (i < nn) q[tail++] = nx[i];
-    }
-}
 
 // s += h  (s: SB planes, h: HB planes, HB <= SB; the sum is known to fit)
 template <int SB, int HB>
@@ -223,33 +166,8 @@ __device__ __forceinline__ void add_planes(u32 (&s)[SB], const u32 (&h)[HB])
     }
 }
 
-// s += hn - ho in one pass: the HB-plane difference in two's complement (its sign is
-// the borrow out), then one ripple add of the sign-extended difference
-template <int SB, int HB>
-__device__ __forceinline__ void addsub_planes(u32 (&s)[SB], const u32 (&hn)[HB], const u32 (&ho)[HB])
-{
-    u32 dl[HB];
-    u32 b = ~hn[0] & ho[0];
-    dl[0] = hn[0] ^ ho[0];
-#pragma unroll
-    for (int k = 1; k < HB; k++) {
-        dl[k] = bop<BOP_XOR3>(hn[k], ho[k], b);
-        b = bop<BOP_BORROW>(hn[k], ho[k], b);
-    }
-    const u32 sg = b;                       // all higher planes of the difference
-    u32 c = s[0] & dl[0];
-    s[0] ^= dl[0];
-#pragma unroll
-    for (int k = 1; k < SB; k++) {
-        const u32 a = k < HB ? dl[k] : sg;
-        const u32 cn = k + 1 < SB ? bop<BOP_MAJ>(s[k], a, c) : 0u;
-        s[k] = bop<BOP_XOR3>(s[k], a, c);
-        c = cn;
-    }
-}
-
 // ---------------------------------------------------------------------------
-// LOCKSTEP forms (SM_BS_LOCKSTEP).  Measured on gfx950 with exactly two waves per SIMD
+// Lockstep forms.  Measured on gfx950 with exactly two waves per SIMD
 // (tools/ubench_issue.hip, tools/ubench_body.hip): a VALU instruction that reads the
 // result of the instruction issued 1 / 2 / 3 instructions earlier in its own wave costs
 // the SIMD 8 / 4 / ~2.7 issue cycles instead of 2, and the OLDER wave of the pair keeps
@@ -262,9 +180,6 @@ __device__ __forceinline__ void addsub_planes(u32 (&s)[SB], const u32 (&hn)[HB],
 // then has a distance >= IT -- and each operation is followed by a scheduling barrier
 // (SM_PIN) so that the order written here is the order issued.
 // ---------------------------------------------------------------------------
-#ifndef SM_BS_LOCKSTEP
-#define SM_BS_LOCKSTEP 1
-#endif
 #define SM_PIN() __builtin_amdgcn_sched_barrier(0)
 // Re-phase the two waves of a SIMD.  Measured (tools/gen_ubench_bankrules.py, two waves per
 // SIMD): ONE half-rate VALU instruction (v_alignbit, DPP moves, v_bfe, v_perm, v_lshl_or,
@@ -272,26 +187,15 @@ __device__ __forceinline__ void addsub_planes(u32 (&s)[SB], const u32 (&hn)[HB],
 // older wave issues every 4 cycles and the younger only every 8 -- 2.67 cycles per
 // instruction for the SIMD instead of 2 -- and they STAY there until a scalar instruction
 // passes: 1 alignbit per 64 v_bitop3 costs 3.9 cycles per instruction, the same with an
-// s_nop behind each alignbit 2.7.  SM_SYNC(level) emits that s_nop where SM_BS_NOP >= level.
-#ifndef SM_BS_PRIO
-#define SM_BS_PRIO 0      // a STATIC priority only swaps which wave of the pair is starved (measured)
-#endif
-#ifndef SM_BS_SLICE
-#define SM_BS_SLICE 16    // swap every 65536 cycles (~31 us): 13 / 15 / 17 measured slower
-#endif
-#ifndef SM_BS_PATTERN
-#define SM_BS_PATTERN 0xF0F0F0F0u   // 4 units (65536 cycles) per slice; 2 / 3 / 5 / 6 units, shifted phases, unequal duty
-                                    // cycles and the inverse measured, for both workgroup shapes: all within +-1.5 %
-#endif
-#ifndef SM_BS_NOP
-#define SM_BS_NOP 3
-#endif
-#define SM_SYNC(level) do { if (SM_BS_NOP >= (level)) { asm volatile("s_nop 0"); SM_PIN(); } } while (0)
+// s_nop behind each alignbit 2.7.  SM_SYNC() emits that s_nop (fewer of them: measured in
+// profiles/r02/ab_nop_levels.txt).
+#define SM_SYNC() do { asm volatile("s_nop 0"); SM_PIN(); } while (0)
 #define BOP_ANDN 0x0C      // ~a & b
 #define BOP_ORN 0xCF       // ~a | b   (a ? b : all ones)
 #define BOP_XNOR 0xC3      // ~(a ^ b)            (c ignored)
 
-// IT counters side by side: inputs come from xin(item, i), made when first used
+// carry-save trees: N one-bit inputs -> their count on HB planes, for IT counters side by side.
+// Inputs come from xin(item, i), made when first used
 template <int N, int HB, int IT, typename XF>
 __device__ __forceinline__ void count_lockstep(XF xin, u32 (&h)[IT][HB])
 {
@@ -316,7 +220,7 @@ __device__ __forceinline__ void count_lockstep(XF xin, u32 (&h)[IT][HB])
                 for (int it = 0; it < IT; it++) { q[it][tail] = bop<BOP_XOR3>(a[it], b[it], c[it]); SM_PIN(); }
 #pragma unroll
                 for (int it = 0; it < IT; it++) { nx[it][nn] = bop<BOP_MAJ>(a[it], b[it], c[it]); SM_PIN(); }
-                SM_SYNC(2);
+                SM_SYNC();
                 head += 3; tail++; nn++;
             }
         }
@@ -375,7 +279,7 @@ __device__ __forceinline__ void add_lockstep(u32 (&S)[DS][SB], int dd0, const u3
         }
 #pragma unroll
         for (int g = 0; g < GS; g++) c[g] = cn[g];
-        SM_SYNC(3);
+        SM_SYNC();
     }
 }
 
@@ -396,7 +300,7 @@ __device__ __forceinline__ void addsub_lockstep(u32 (&S)[DS][SB], int dd0, const
         for (int g = 0; g < GS; g++) { dl[g][k] = bop<BOP_XOR3>(hn[g][k], ho[g][k], b[g]); SM_PIN(); }
 #pragma unroll
         for (int g = 0; g < GS; g++) { b[g] = bop<BOP_BORROW>(hn[g][k], ho[g][k], b[g]); SM_PIN(); }
-        SM_SYNC(3);
+        SM_SYNC();
     }
     u32 c[GS];
 #pragma unroll
@@ -418,7 +322,7 @@ __device__ __forceinline__ void addsub_lockstep(u32 (&S)[DS][SB], int dd0, const
         }
 #pragma unroll
         for (int g = 0; g < GS; g++) c[g] = cn[g];
-        SM_SYNC(3);
+        SM_SYNC();
     }
 }
 
@@ -484,72 +388,44 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
     const int wv = DUO ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
     const int pair = blockIdx.z;
     SM_STAMP(0);
-#if SM_BS_PRIO
-    // Unequal priorities for the waves that share a SIMD.  With equal priority the SIMD's
-    // arbiter serves the OLDEST wave first, and once any half-rate instruction (v_alignbit,
-    // DPP, v_bfe, ...) has passed, the younger wave gets an issue slot only every 8 cycles
-    // while the older keeps its 4 (tools/gen_ubench_bankrules.py, "mix 16": 4.0 cycles per
-    // instruction for the SIMD; with a raised priority on the odd hardware wave slots 2.5;
-    // this kernel: older waves done after 74 us, younger after 107).  The hardware wave
-    // slot (HW_ID bits 3:0) tells the co-resident waves apart: slot parity -> priority.
-    if (__builtin_amdgcn_s_getreg(63492) & 1) __builtin_amdgcn_s_setprio(SM_BS_PRIO);
-#endif
-#if SM_BS_SLICE
-    // Time-sliced priority: the wave whose hardware slot parity equals bit SM_BS_SLICE of
-    // the shader clock runs at raised priority, the other at 0, and the roles swap every
-    // 2^SM_BS_SLICE cycles (with SM_BS_PATTERN: after a schedule counted from the wave's own
-    // start) -- both read the same clock, so exactly one of a pair is favoured at any time.
+    // Time-sliced priority for the two waves that share a SIMD.  With equal priority the SIMD's
+    // arbiter serves the OLDEST wave first, and once any half-rate instruction (v_alignbit, DPP,
+    // v_bfe, ...) has passed, the younger wave gets an issue slot only every 8 cycles while the
+    // older keeps its 4 (tools/gen_ubench_bankrules.py, "mix 16"; this kernel: older waves done
+    // after 74 us, younger after 107).  A static priority only swaps which wave of the pair is
+    // starved (profiles/r02/wave_timeline_static_priority.txt).  So the wave whose hardware slot
+    // parity (bit 0 of HW_ID) is favoured by the current slice of a schedule runs at raised
+    // priority, the other at 0, and the roles swap from slice to slice -- both read the same
+    // clock, so exactly one of a pair is favoured at any time; the two waves of a SIMD always
+    // differ in slot parity (tools/wave_timeline.py: 1016 of 1016 pairs).
     // (A feedback variant -- every wave publishes its finished rows per SIMD and slot in
     // global memory, the one that is behind takes the priority -- was built and measured
     // slower, 96.6 vs 91.3 us: a store, a load and a v_readfirstlane per row, and the waves
     // still finished 15 us apart.)  The SIMD serves its favoured wave at the rate of a wave alone
     // and gives the other what is left (measured: 4.9 vs 9.0 cycles per instruction here);
     // without the swap the favoured wave finishes a third earlier and the SIMD then runs
-    // half empty until the other is done.
-    // Which of a SIMD's two waves a slice favours: bit g.prio_shift of HW_ID -- bit 0 of the wave slot, or
-    // (two-wave workgroups of a launch that fits the chip in one round) bit 0 of TG_ID, the workgroup's slot
-    // on its CU.  The two waves of a SIMD differ in either (tools/wave_timeline.py: 1016 of 1016 pairs), but
-    // the two waves of a WORKGROUP share the second: their barrier-coupled warm-up is then favoured as a
-    // whole instead of running at the pace of whichever of the two is not (a workgroup with one wave in
-    // each slot parity -- half of them -- was never favoured as a whole).  In a launch of several rounds
-    // later workgroups land in whatever slot is free and the bit no longer separates a SIMD's pair:
-    // those keep the wave slot.
-    const unsigned slot_parity = (__builtin_amdgcn_s_getreg(63492) >> g.prio_shift) & 1;
+    // half empty until the other is done.  Telling the pair apart by the workgroup's slot on its CU
+    // instead lost 5 % in the real step (profiles/r03/ab_priority_class.txt, sustained_ab.txt).
+    const unsigned slot_parity = __builtin_amdgcn_s_getreg(63492) & 1;
     // the clock is read one row ahead of its use (s_memtime is a scalar memory read: its
     // value takes ~100 cycles to arrive, and a wave that uses it at once waits that long)
     unsigned long long clk = __builtin_amdgcn_s_memtime();
-#if SM_BS_PATTERN
-    // slices counted from the wave's own start (the waves of a launch start within 0.5 us of
-    // each other): bit k of the plan's pattern (g.prio_pattern: SM_BS_PATTERN unless SM_PATTERN
-    // in the environment overrides it for tuning) says which slot parity is favoured during
-    // the k-th unit of 2^g.prio_unit cycles (16384, ~8 us; short launches take finer ones), so the schedule is the
-    // same in every launch
+    // Slices counted from the wave's own start (the waves of a launch start within 0.5 us of
+    // each other): bit k of the pattern says which slot parity is favoured during the k-th unit
+    // of 2^14 cycles (16384, ~8 us), so the schedule is the same in every launch.  16 shifts
+    // per lane: four units per slice (other lengths, phases and duty cycles all within +-1.5 %,
+    // profiles/r02/ab_priority_pattern.txt).  The launches of 8 and 4 shifts per lane are short
+    // and swap every unit (C2's match launch 17.1 -> 15.6 us, profiles/r04/ab_prio_unit.txt).
+    // s_setprio is issued once per row (issuing it only on a change measured no faster, profiles/r03).
+    constexpr unsigned PATTERN = DS == 16 ? 0xF0F0F0F0u : 0xAAAAAAAAu;
     const unsigned long long clk0 = clk;
-    // (g.prio_on_change, tuning: s_setprio only when the wanted priority changes instead of once per row --
-    // on part of the pool a wave that re-issues it every row is served as if it had none)
-    unsigned prio_now = 2;
 #define SM_SLICE_PRIO()                                                               \
     do {                                                                              \
-        const unsigned unit_ = (unsigned)((clk - clk0) >> g.prio_unit) & 31u;         \
-        const unsigned want_ = ((g.prio_pattern >> unit_) ^ slot_parity) & 1;         \
-        if (!g.prio_on_change || want_ != prio_now) {                                 \
-            if (want_) __builtin_amdgcn_s_setprio(3);                                 \
-            else __builtin_amdgcn_s_setprio(0);                                       \
-            prio_now = want_;                                                         \
-        }                                                                             \
-    } while (0)
-#else
-#define SM_SLICE_PRIO()                                                               \
-    do {                                                                              \
-        if ((((unsigned)(clk >> SM_BS_SLICE)) ^ slot_parity) & 1) __builtin_amdgcn_s_setprio(3); \
+        const unsigned unit_ = (unsigned)((clk - clk0) >> 14) & 31u;                  \
+        if (((PATTERN >> unit_) ^ slot_parity) & 1) __builtin_amdgcn_s_setprio(3);    \
         else __builtin_amdgcn_s_setprio(0);                                           \
     } while (0)
-#endif
 #define SM_SLICE_READ() do { clk = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define SM_SLICE_PRIO() do { } while (0)
-#define SM_SLICE_READ() do { } while (0)
-#endif
     int tile_x, tile_y;
     sm_xcd_tile(g.tiles_x, g.tiles_y, tile_x, tile_y);
     const int tx0 = tile_x * g.tw;
@@ -635,18 +511,7 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
     auto rview = [&](const RowViews &v, int j) -> u32 {
         return (j & 31) ? alignbit(v.rw[(j >> 5) + 1], v.rw[j >> 5], j & 31) : v.rw[j >> 5];
     };
-#if !SM_BS_LOCKSTEP
-    // mismatch count of shift dd in one row (win = the N right views of this shift)
-    auto count_row = [&](const RowViews &v, const u32 (&win)[N], u32 (&h)[HB]) {
-        u32 x[N];
-#pragma unroll
-        for (int i = 0; i < N; i++)
-            x[i] = GHOST ? bop<BOP_XOR_AND>(v.lv[i], win[i], cvv[i]) : (v.lv[i] ^ win[i]);
-        count_bits<N, HB>(x, h);
-    };
-#endif
 
-#if SM_BS_LOCKSTEP
     constexpr int GW = DS >= 4 ? 4 : DS;      // shifts side by side in a warm-up row
     constexpr int GS = 2;                     // ... in a steady-state row (2 x {row in, row out})
     static_assert(DS % GW == 0 && DS % GS == 0, "shift groups");
@@ -663,7 +528,7 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
             for (int m = 0; m < N - 1; m++) rv[m] = rv[m + GW];
 #pragma unroll
             for (int m = 0; m < GW; m++) { rv[N - 1 + m] = rview(v, dd0 + N - 1 + m); SM_PIN(); }
-            SM_SYNC(1);
+            SM_SYNC();
             u32 h[GW][HB];
             count_lockstep<N, HB, GW>([&](int it, int i) -> u32 {
                 const u32 x = GHOST ? bop<BOP_XOR_AND>(v.lv[i], rv[it + i], cvv[i]) : (v.lv[i] ^ rv[it + i]);
@@ -687,7 +552,7 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
                 rn[N - 1 + m] = rview(vn, dd0 + N - 1 + m); SM_PIN();
                 ro[N - 1 + m] = rview(vo, dd0 + N - 1 + m); SM_PIN();
             }
-            SM_SYNC(1);
+            SM_SYNC();
             u32 h[2 * GS][HB];                // item 2g = shift dd0 + g row in, 2g + 1 = row out
             count_lockstep<N, HB, 2 * GS>([&](int it, int i) -> u32 {
                 const u32 l = (it & 1) ? vo.lv[i] : vn.lv[i];
@@ -702,53 +567,9 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
 #pragma unroll
                 for (int k = 0; k < HB; k++) { hn[gq][k] = h[2 * gq][k]; ho[gq][k] = h[2 * gq + 1][k]; }
             addsub_lockstep<SB, HB, GS, DS>(S, dd0, hn, ho);
-            SM_SYNC(2);
+            SM_SYNC();
         }
     };
-#else
-    // warm-up: one window row into all sums
-    auto slide_in = [&](int srow) {
-        RowViews v;
-        load_views(srow, v);
-        u32 win[N];
-#pragma unroll
-        for (int i = 0; i < N - 1; i++) win[i + 1] = rview(v, i);
-#pragma unroll
-        for (int dd = 0; dd < DS; dd++) {
-#pragma unroll
-            for (int i = 0; i < N - 1; i++) win[i] = win[i + 1];
-            win[N - 1] = rview(v, dd + N - 1);
-            u32 h[HB];
-            count_row(v, win, h);
-            add_planes<SB, HB>(S[dd], h);
-        }
-    };
-    // steady state: one row in and one row out, applied as a single signed difference
-    auto slide_views = [&](const RowViews &vn, const RowViews &vo) {
-        u32 wn[N], wo[N];
-#pragma unroll
-        for (int i = 0; i < N - 1; i++) { wn[i + 1] = rview(vn, i); wo[i + 1] = rview(vo, i); }
-#pragma unroll
-        for (int dd = 0; dd < DS; dd++) {
-#pragma unroll
-            for (int i = 0; i < N - 1; i++) { wn[i] = wn[i + 1]; wo[i] = wo[i + 1]; }
-            wn[N - 1] = rview(vn, dd + N - 1);
-            wo[N - 1] = rview(vo, dd + N - 1);
-            u32 hn[HB], ho[HB];
-            count_row(vn, wn, hn);
-            count_row(vo, wo, ho);
-            addsub_planes<SB, HB>(S[dd], hn, ho);
-        }
-    };
-#endif
-#if !SM_BS_PREFETCH
-    auto slide_both = [&](int srow_new, int srow_old) {
-        RowViews vn, vo;
-        load_views(srow_new, vn);
-        load_views(srow_old, vo);
-        slide_views(vn, vo);
-    };
-#endif
 
     // Staged row e is image row ty0 - HALF + e.  Ghost rows outside the image need no
     // special case: their ext rows are all zero in BOTH images, so every tap reads
@@ -838,15 +659,12 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
     SM_SLICE_READ();
     SM_STAMP(2);
 
-#if SM_BS_XMERGE
     // lane merge through LDS (see the row loop): this wave's buffer of g.xm_words words = 4 x NPG blocks of 1 KB.  In a two-wave
     // workgroup wave 0's begins at word g.xm_off (over exchange slot 1, which wave 0 is the last to read) and
     // wave 1's ends there (over slot 0); a lone wave's begins there.
     u32 *xm_base = lds + g.xm_off - ((DUO && wv) ? g.xm_words : 0);
     u32 *xm_wbase = xm_base + (s & 3) * ((SB + AB + 3) / 4) * 256;
     const u32 xm_wunit = (u32)(wi * (g.nl >> 2) + (s >> 2) + 2 * (s & 3));
-#endif
-#if SM_BS_PREFETCH
     // byte addresses (LDS offsets: the low half of the flat address) of this lane's words
     // in staged row 0, and the row strides; the reads of iteration t + 1 are issued while
     // iteration t computes
@@ -863,26 +681,18 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
         lds_issue(qn, aNewL, aNewR);
         lds_issue(qo, aNewL - sL * N, aNewR - sR * N);
     }
-#endif
 #pragma unroll 1
     for (int t = 0;;) {
         SM_SLICE_PRIO();
         // ---- winner-take-all of output row t over this lane's 16 shifts
         const int y = y0 + sgn * t;
-#if SM_BS_PREFETCH
         const u32 lc = qc.l;
         const u32 c0_ = (u32)qc.r01, c1_ = (u32)(qc.r01 >> 32), c2_ = qc.r2;
         const u32 rc0 = alignbit(c1_, c0_, shRc), rc1 = alignbit(c2_, c1_, shRc);
-#else
-        const u32 lc = pL[(c0 + sgn * t) * plw + wLc];
-        const u32 *rrc = pR + (c0 + sgn * t) * prw + wRc;
-        const u32 rc0 = alignbit(rrc[1], rrc[0], shRc), rc1 = alignbit(rrc[2], rrc[1], shRc);
-#endif
 
         u32 B[SB], arg[ABMAX];
 #pragma unroll
         for (int k = 0; k < ABMAX; k++) arg[k] = 0;
-#if SM_BS_LOCKSTEP
         {
             // Four independent scans side by side, one per quarter of the lane's shifts
             // (ascending, <=: the last of equal counts wins), then the quarters are merged
@@ -900,7 +710,7 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
                     const int dd = qd * QS + i;
                     rcd[qd] = dd ? alignbit(rc1, rc0, dd) : rc0; SM_PIN();
                 }
-                SM_SYNC(1);
+                SM_SYNC();
                 if (i == 0) {
                     // first shift of a quarter: it wins wherever its centre pixel matches
 #pragma unroll
@@ -923,7 +733,7 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
 #pragma unroll
                         for (int qd = 0; qd < Q; qd++) {
                             bw[qd] = bop<BOP_BORROW>(Bq[qd][k], S[qd * QS + i][k], k ? bw[qd] : 0u); SM_PIN();
-                            if (qd == Q - 1 && (k & 1)) SM_SYNC(3);
+                            if (qd == Q - 1 && (k & 1)) SM_SYNC();
                         }
 #pragma unroll
                     for (int qd = 0; qd < Q; qd++) {
@@ -935,7 +745,7 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
 #pragma unroll
                         for (int qd = 0; qd < Q; qd++) {
                             Bq[qd][k] = bop<BOP_SEL>(upd[qd], S[qd * QS + i][k], Bq[qd][k]); SM_PIN();
-                            if (qd == Q - 1 && (k & 1)) SM_SYNC(3);
+                            if (qd == Q - 1 && (k & 1)) SM_SYNC();
                         }
 #pragma unroll
                     for (int a = 0; a < AQ; a++)
@@ -982,25 +792,6 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
             for (int k = 0; k <= AQ; k++) { arg[k] = bop<BOP_SEL>(bwf, ah[0][k], ah[1][k]); SM_PIN(); }
             arg[AQ + 1] = ~bwf; SM_PIN();
         }
-#else
-#pragma unroll
-        for (int k = 0; k < SB; k++) B[k] = 0xffffffffu;
-#pragma unroll
-        for (int dd = 0; dd < DS; dd++) {
-            const u32 rcd = dd ? alignbit(rc1, rc0, dd) : rc0;
-            u32 bw = 0;                                  // borrow of B - S: 1 <=> B < S
-#pragma unroll
-            for (int k = 0; k < SB; k++) bw = bop<BOP_BORROW>(B[k], S[dd][k], bw);
-            u32 upd = bop<BOP_UPD>(lc, rcd, bw);         // centre matches and S <= B
-            if (!FULLD) upd &= (u32)__builtin_amdgcn_sbfe((int)dvalid, dd, 1);
-#pragma unroll
-            for (int k = 0; k < SB; k++) B[k] = bop<BOP_SEL>(upd, S[dd][k], B[k]);
-#pragma unroll
-            for (int k = 0; k < AB; k++) {
-                if ((dd >> k) & 1) arg[k] |= upd; else arg[k] &= ~upd;
-            }
-        }
-#endif
 
         // ---- planes -> integers, for `per` pixels of the word at image column xw, row yy, starting at
         // pixel pfirst of the word, in chunks of up to 4.  nib = the chunk's bits of a plane;
@@ -1015,7 +806,6 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
             u32 allone = B[0];
 #pragma unroll
             for (int k = 1; k < SB; k++) allone &= B[k];
-#if SM_BS_XMERGE
             // "no shift matched" (all planes of the count set) -> web = D: folded in on the PLANES,
             // 32 pixels per operation, instead of a select per pixel (bit k of D - 1 for all lanes)
             u32 dm1 = (u32)(g.D - 1);
@@ -1026,7 +816,6 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
                 if (k >= AB && k >= AB + g.log2nl) continue;   // uniform: planes no merge level set
                 arg[k] = bop<BOP_SEL>(allone, (u32)-(i32)((dm1 >> k) & 1u), arg[k]);
             }
-#endif
             for (int c = 0, p0 = pfirst; c < per; c += 4, p0 += pstep) {
                 u32 bb = 0, bhi = 0, alo = 0, ahi = 0;
                 if (best) {                          // uniform: the counts are wanted at all
@@ -1055,11 +844,7 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
                         taps = cols * rws;
                     }
                     const i32 a = (i32)(((alo >> (8 * q)) & 255u) | (((ahi >> (8 * q)) & 255u) << 8));
-#if SM_BS_XMERGE
                     wv[q] = a + 1;
-#else
-                    wv[q] = no ? g.D : a + 1;
-#endif
                     bv[q] = no ? 0 : taps - (i32)(((bb >> (8 * q)) & 255u) | (((bhi >> (8 * q)) & 255u) << 8));
                 }
                 const int x = xw + p0;
@@ -1120,7 +905,7 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
             u32 pb[SB], pa[NA];                                                        \
             _Pragma("unroll") for (int k = 0; k < SB; k++) pb[k] = from_partner<K>(B[k]);      \
             _Pragma("unroll") for (int k = 0; k < NA; k++) pa[k] = from_partner<K>(arg[k]);    \
-            SM_PIN(); SM_SYNC(1);                                                      \
+            SM_PIN(); SM_SYNC();                                                       \
             const u32 mine_high = ((me) >> K) & 1 ? 0xffffffffu : 0u;                  \
             u32 bw = mine_high;          /* borrow-in 1: partner - mine - 1 < 0 <=> partner <= mine */ \
             bw = ~bw;                    /* partner is the high one iff I am not */   \
@@ -1130,7 +915,6 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
             _Pragma("unroll") for (int k = 0; k < NA; k++) arg[k] = bop<BOP_SEL>(take, pa[k], arg[k]); \
             arg[NA] = take ^ mine_high;   /* partner's bit K = ~mine */              \
         }
-#if SM_BS_XMERGE
         if (g.xmerge) {
             // ---- THE NL LANES OF A WORD ARE MERGED THROUGH LDS, FOUR ROWS AT A TIME.  Merging them per
             // row with DPP costs log2(nl) full compare-and-select levels per lane and row (~105 VALU
@@ -1230,9 +1014,7 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
                 }
                 __builtin_amdgcn_wave_barrier();
             }
-        } else
-#endif
-        {
+        } else {
             // ---- merge the nl lanes of this word per row (DPP; ds_bpermute beyond 16 lanes)
             if (g.nl > 1) SM_MERGE(0, s, AB)
             if (g.nl > 2) SM_MERGE(1, s, AB + 1)
@@ -1250,9 +1032,8 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
 #undef SM_MERGE
 
         // ---- slide the window down: staged row t + N - 1 in, staged row t - 1 out
-        SM_SYNC(1);
+        SM_SYNC();
         if (++t >= rows_out) break;
-#if SM_BS_PREFETCH
         {
             // cut the views of this slide out of the raw words, which frees their
             // registers for the reads of the NEXT iteration: a whole slide ahead of use
@@ -1266,12 +1047,9 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
                 lds_issue(qo, aNewL - sL * N, aNewR - sR * N);
             }
             SM_SLICE_READ();         // behind the reads above: it is waited for with them, a row later
-            SM_PIN(); SM_SYNC(1);
+            SM_PIN(); SM_SYNC();
             slide_views(vn, vo);
         }
-#else
-        slide_both(c0 + sgn * (t + HALF), c0 + sgn * (t - 1 - HALF));
-#endif
     }
     SM_STAMP(3);
 }

@@ -96,7 +96,7 @@ def test_plan_options_struct_and_argument_checks():
     from tools import _options
     assert [n for n, _ in _options.PlanOptions._fields_] == fields
     for name, to_fields in _options.NAMES.items():
-        probe = "popcount" if name == "SM_KERNEL" else ("0x3" if name == "SM_PATTERN" else "2")
+        probe = "popcount" if name == "SM_KERNEL" else "2"
         assert set(to_fields(probe)) <= set(fields), name
 
 

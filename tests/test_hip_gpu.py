@@ -1577,6 +1577,34 @@ def test_plan_options_struct_size_rules(hip):
             plan.close()
 
 
+RETIRED_PRIORITY = dict(priority_pattern=0x3, priority_class=2, priority_on_change=1, priority_unit_log2=10)
+
+
+@pytest.mark.parametrize("mode", ["toroidal", "ghost"])
+@pytest.mark.parametrize("shape,want", [({}, "bit-sliced kernel"),
+                                        (dict(TWO_WAVES, shifts_per_lane=16), "two-wave workgroups"),
+                                        (dict(ONE_WAVE, shifts_per_lane=8), "shift-lanes of 8)"),
+                                        (dict(TWO_WAVES, shifts_per_lane=4), "shift-lanes of 4)")])
+def test_retired_priority_options_have_no_effect(hip, shape, want, mode):
+    """The four priority_* fields of sm_plan_options are kept for the struct layout only: set, they change
+    neither the plan (describe, geometry) nor the maps.  The two-wave launch of this shape fits the chip in
+    one round, where priority_class = 2 used to pick another schedule."""
+    w, h, d, sw = 300, 150, 128, 9
+    le, re = rand_edges(w, h, seed=31)
+    obest, oweb = oracle.hot_path(le, re, d, sw, mode)
+    seen = []
+    for opts in (shape, dict(shape, **RETIRED_PRIORITY)):
+        plan = hip.StereoPlan(w, h, d, sw, mode, options=opts or None)
+        plan.load_edges(dev(le), dev(re))
+        web, best = plan.match_wta(1, want_best=True)
+        torch.cuda.synchronize()
+        seen.append((plan.describe(), plan.geometry()))
+        assert want in seen[-1][0], seen[-1][0]
+        assert np.array_equal(host(web)[0], oweb) and np.array_equal(host(best)[0], obest), (opts, seen[-1][0])
+        plan.close()
+    assert seen[1] == seen[0]
+
+
 @pytest.mark.parametrize("mode", ["toroidal", "ghost"])
 @pytest.mark.parametrize("w,h,d,sw,opts", [(300, 150, 128, 9, None), (1920, 64, 64, 7, None), (257, 61, 64, 7, None),
                                           (300, 150, 128, 9, dict(edge_kernel=1)), (120, 80, 30, 23, None)])

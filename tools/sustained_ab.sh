@@ -1,10 +1,13 @@
 #!/bin/bash
 # One box, the REAL step (edges + match back to back, as bench.py runs it), one setting after the other, twice over.
 # (A timing loop of match launches alone is NOT a stand-in for it: the match launch that follows the edge kernel finds
-# its workgroups in other slots than one that follows itself, and priority settings rank differently.)
-#   gpurun -- 'bash tools/sustained_ab.sh [cfg] [settings file]'  -> gpurun_out/sustained_ab.txt
-CFG=${1:-C3}
-SETTINGS=${2:-tools/sustained_ab.settings}
+# its workgroups in other slots than one that follows itself, and settings that depend on the slots rank differently.)
+# The settings file holds one setting per line, short option names as tools/_options.py takes them
+# ("SM_TILE_H=8 SM_DUO=1"; a blank line = the plan's own choice).
+#   bash tools/sustained_ab.sh <cfg> <settings file>
+if [ $# -lt 2 ]; then echo "usage: $0 <cfg> <settings file>" >&2; exit 2; fi
+CFG=$1
+SETTINGS=$2
 { for rep in 1 2; do
   while IFS= read -r s; do
     echo "== rep $rep: ${s:-shipped}"
