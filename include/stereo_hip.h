@@ -417,10 +417,12 @@ int sm_run_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_r
 int sm_plan_reserve_lr(sm_plan *plan);
 
 /* ---- step 3 -------------------------------------------------------------- *
- * fill_web_holes (src/stereo.cu:235-256): `times` Jacobi sweeps over pixels
- * that are 0, ping-ponging d_web and d_tmp exactly as the reference swaps
- * its pointers; *result_in_tmp tells which buffer holds the returned image.
- * Both buffers are W*H int32 per pair.                                      */
+ * fill_web_holes (src/stereo.cu:235-256): every pixel that is 0 becomes the
+ * truncated mean of its four flat-index neighbours.  The reference's pointer
+ * SWAP is a no-op (its macro's local `tmp` shadows the buffer), so each of its
+ * `times` sweeps reads the unfilled map: times >= 1 is one sweep, times <= 0
+ * none.  d_tmp is workspace; *result_in_tmp tells which buffer holds the
+ * returned image (d_web: it is 0).  Both buffers are W*H int32 per pair.    */
 int sm_fill_web_holes(sm_plan *plan, int32_t *d_web, int32_t *d_tmp, int times,
                       int pairs, int *result_in_tmp, void *stream);
 

@@ -311,32 +311,31 @@ void smo_fill_web_holes(int32_t *web, int w, int h, int times)
      * +-w with NO wrap (IDX, not idx): x-1 at x=0 is the previous row's last
      * pixel.  Offsets that leave the array are undefined behaviour in the
      * reference and unreachable from its pipeline (the web never holds a 0,
-     * SURVEY.md section 8f); here they read as 0.  The reference ping-pongs
-     * two buffers by swapping pointers and returns whichever is current,
-     * leaving stale values in non-hole pixels of the other one; copying the
-     * current buffer back reproduces the returned image exactly. */
+     * SURVEY.md section 8f); here they read as 0.
+     *
+     * The reference's SWAP(i32 *, web, tmp) (src/util.h:27-32) declares a
+     * local named `tmp`, which shadows the buffer of that name: the macro
+     * assigns web to itself and swaps nothing.  So every sweep reads the
+     * untouched copy `tmp` and writes the same values into `web`: for
+     * times >= 1 the result is ONE sweep over the original map, whatever
+     * `times` is, and the caller's buffer is the one returned (src/stereo.cu's
+     * fill_web_holes has the same macro and the same result).  The compiled
+     * reference's own functions pin this (tests/golden/step3/). */
+    if (times <= 0)
+        return;
     const long n = (long)w * h;
-    i32 *cur = zalloc(sizeof(i32) * (size_t)n); /* "web" of the reference */
-    i32 *oth = zalloc(sizeof(i32) * (size_t)n); /* "tmp" */
-    memcpy(cur, web, sizeof(i32) * (size_t)n);
-    memcpy(oth, web, sizeof(i32) * (size_t)n);
-    for (int it = 0; it < times; it++) {
-        for (long p = 0; p < n; p++) {
-            if (oth[p] == 0) {
-                i32 r = p + 1 < n ? oth[p + 1] : 0;
-                i32 u = p + w < n ? oth[p + w] : 0;
-                i32 l = p - 1 >= 0 ? oth[p - 1] : 0;
-                i32 d = p - w >= 0 ? oth[p - w] : 0;
-                cur[p] = (r + u + l + d) / 4;
-            }
+    i32 *tmp = zalloc(sizeof(i32) * (size_t)n);
+    memcpy(tmp, web, sizeof(i32) * (size_t)n);
+    for (long p = 0; p < n; p++) {
+        if (tmp[p] == 0) {
+            i32 r = p + 1 < n ? tmp[p + 1] : 0;
+            i32 u = p + w < n ? tmp[p + w] : 0;
+            i32 l = p - 1 >= 0 ? tmp[p - 1] : 0;
+            i32 d = p - w >= 0 ? tmp[p - w] : 0;
+            web[p] = (r + u + l + d) / 4;
         }
-        i32 *t = cur;
-        cur = oth;
-        oth = t;
     }
-    memcpy(web, cur, sizeof(i32) * (size_t)n);
-    free(cur);
-    free(oth);
+    free(tmp);
 }
 
 int smo_draw_contour_map(const int32_t *web, int w, int h, int num_lines,

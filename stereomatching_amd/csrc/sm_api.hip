@@ -572,10 +572,10 @@ __global__ __launch_bounds__(256) void k_debug_planes(const u32 *__restrict__ ex
 // step 3
 // ---------------------------------------------------------------------------
 
-// one Jacobi sweep of src/stereo.cu:235-245: read `oth`, write `cur` where
-// oth == 0.  Neighbours at flat offsets +-1, +-w (the reference's unwrapped
-// IDX); offsets that leave the image array are undefined in the reference and
-// read as 0 here.
+// the sweep of src/stereo.cu:235-245: read `oth`, write `cur` where oth == 0.
+// Neighbours at flat offsets +-1, +-w (the reference's unwrapped IDX); offsets
+// that leave the image array are undefined in the reference and read as 0 here
+// (SURVEY.md section 8f).
 __global__ __launch_bounds__(256) void k_fill_holes_step(i32 *__restrict__ cur,
                                                          const i32 *__restrict__ oth, int w,
                                                          long long n)
@@ -1609,18 +1609,19 @@ extern "C" int sm_draw_contour_map(sm_plan *plan, const int32_t *d_web, const in
 static int run_sweeps(sm_plan *plan, i32 *d_web, i32 *d_tmp, int times, int pairs, int *result_in_tmp,
                       hipStream_t st)
 {
-    // tmp <- web, then `times` sweeps with the two buffers trading places
-    // (src/stereo.cu:247-256,:328)
+    // tmp <- web (src/stereo.cu:328), then the reference's `times` sweeps
+    // (:247-256).  Its SWAP(i32 *, web, tmp) (src/util.h:27-32) declares a local
+    // named `tmp` that shadows the buffer: the macro swaps nothing, so every sweep
+    // reads the untouched copy and writes the same values into web.  `times` >= 1
+    // sweeps are ONE sweep over the original map, and web is the returned buffer
+    // (pinned to the reference's own functions by tests/golden/step3/).
     const long long n = (long long)plan->width * plan->height;
+    *result_in_tmp = 0;
+    if (times <= 0) return SM_OK;
     SM_HIP(hipMemcpyAsync(d_tmp, d_web, sizeof(i32) * n * pairs, hipMemcpyDeviceToDevice, st));
-    i32 *cur = d_web, *oth = d_tmp;
-    const dim3 grid((unsigned)((n + 255) / 256), pairs), block(256);
-    for (int i = 0; i < times; i++) {
-        hipLaunchKernelGGL(k_fill_holes_step, grid, block, 0, st, cur, oth, plan->width, n);
-        i32 *t = cur; cur = oth; oth = t;
-    }
+    hipLaunchKernelGGL(k_fill_holes_step, dim3((unsigned)((n + 255) / 256), pairs), dim3(256), 0, st, d_web,
+                       d_tmp, plan->width, n);
     SM_LAUNCH_CHECK("k_fill_holes_step");
-    *result_in_tmp = cur == d_tmp;
     return SM_OK;
 }
 

@@ -79,7 +79,7 @@ def main():
         print(name, {k: v.shape for k, v in keep.items() if k in ("left", "web-1")})
 
 
-if __name__ == "__main__" and "--big" not in sys.argv and "--pinned" not in sys.argv:
+if __name__ == "__main__" and not {"--big", "--pinned", "--step3"} & set(sys.argv):
     main()
 
 
@@ -217,3 +217,67 @@ def main_pinned():
 
 if __name__ == "__main__" and "--pinned" in sys.argv:
     main_pinned()
+
+
+# ---------------------------------------------------------------------------
+# step 3 on maps WITH holes, pinned to the reference's own fill_web_holes and draw_contour_map (both
+# source files; oracle/ref_step3_driver.c runs them on a map of ours):
+#     make -C oracle ref && python tests/golden/make_golden.py --step3
+# writes tests/golden/step3/<case>.npz for every case of tests/step3_patterns.py.CASES: the input map,
+# [times, lines], and per source file the map fill_web_holes returned, the contour image and the exit
+# status (-8: the zero contour interval trapped; the contour is then all 0 and not compared).  The
+# AddressSanitizer / UBSan build of the driver runs every case as well and must be clean: no fixture
+# reads outside its map.  (A subdirectory: the *.npz of tests/golden/ itself are pipeline fixtures.)
+# The files are written byte for byte the same on every run (fixed zip time stamps).
+# ---------------------------------------------------------------------------
+STEP3_DIR = Path(__file__).resolve().parent / "step3"
+STEP3_SOURCES = {"stereo": "tor", "stereo-ghost": "gh"}      # source file -> key suffix
+
+
+def save_npz_stable(path, **arrays):
+    """np.savez_compressed with fixed member time stamps, so that a rerun writes identical bytes"""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
+        for k, a in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
+            info = zipfile.ZipInfo(f"{k}.npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            zf.writestr(info, buf.getvalue(), compresslevel=9)
+
+
+def step3_reference(web, times, lines):
+    """the fixture arrays of one map: both source files, each also run under ASan / UBSan"""
+    keep = {"web": web, "params": np.array([times, lines], np.int32)}
+    for source, sfx in STEP3_SOURCES.items():
+        r = oracle.run_step3_reference(web, times, lines, source)
+        if r["returncode"] not in (0, -8) or r["filled"] is None:
+            raise RuntimeError(f"{source}: driver exited {r['returncode']}: {r['stderr']}")
+        s = oracle.run_step3_reference(web, times, lines, source, asan=True)
+        if s["returncode"] != r["returncode"] or s["stderr"] or not np.array_equal(s["filled"], r["filled"]):
+            raise RuntimeError(f"{source}: sanitizer run differs (exit {s['returncode']}):\n{s['stderr']}")
+        keep[f"filled_{sfx}"] = r["filled"]
+        keep[f"contour_{sfx}"] = r["contour"] if r["contour"] is not None else np.zeros(web.shape, np.uint8)
+        keep[f"rc_{sfx}"] = np.array(r["returncode"], np.int32)
+    return keep
+
+
+def main_step3():
+    from tests import step3_patterns as sp
+    if not (oracle.step3_ref_available() and oracle.step3_ref_available(asan=True)):
+        sys.exit("oracle/_ref/step3-ref* is missing: run `make -C oracle ref` where /root/reference exists")
+    STEP3_DIR.mkdir(exist_ok=True)
+    for old in STEP3_DIR.glob("*.npz"):
+        if old.stem not in sp.CASES:
+            old.unlink()
+    for name in sp.CASES:
+        web, times, lines = sp.case(name)
+        keep = step3_reference(web, times, lines)
+        save_npz_stable(STEP3_DIR / f"{name}.npz", **keep)
+        print(name, web.shape, "holes", int((web == 0).sum()), "exit", int(keep["rc_tor"]), flush=True)
+
+
+if __name__ == "__main__" and "--step3" in sys.argv:
+    main_step3()

@@ -206,6 +206,37 @@ def run_reference(left, right, threshold=0.15, square_width=21, times=32, lines=
     return out
 
 
+STEP3_SOURCES = {"stereo": "step3-ref", "stereo-ghost": "step3-ref-ghost"}
+
+
+def step3_ref_available(asan=False) -> bool:
+    return all((REF_DIR / (exe + ("-asan" if asan else ""))).exists() for exe in STEP3_SOURCES.values())
+
+
+def run_step3_reference(web, times, lines, source="stereo", asan=False):
+    """The reference's OWN fill_web_holes + draw_contour_map (src/<source>.c, unmodified, driven by
+    oracle/ref_step3_driver.c) on one int32 map -> dict(filled, contour, returncode, stderr).
+    returncode -8: the contour interval was 0 and the reference trapped (SIGFPE); contour is then
+    None.  asan: the AddressSanitizer / UBSan build of the same driver (a read outside the map
+    makes it fail with its report on stderr)."""
+    web = np.ascontiguousarray(web, np.int32)
+    h, w = web.shape
+    exe = REF_DIR / (STEP3_SOURCES[source] + ("-asan" if asan else ""))
+    env = dict(os.environ)
+    if asan:
+        # SIGFPE stays a signal (the trap being pinned), not a sanitizer report; no leak checker
+        env["ASAN_OPTIONS"] = "handle_sigfpe=0:detect_leaks=0"
+    with tempfile.TemporaryDirectory() as td:
+        hdr = np.array([w, h, times, lines], "<i4").tobytes()
+        Path(f"{td}/in").write_bytes(hdr + web.astype("<i4").tobytes())
+        p = subprocess.run([str(exe), f"{td}/in", f"{td}/out"], env=env, capture_output=True, text=True)
+        data = Path(f"{td}/out").read_bytes() if Path(f"{td}/out").exists() else b""
+    n = w * h
+    filled = np.frombuffer(data, "<i4", n).reshape(h, w).astype(np.int32) if len(data) >= 4 * n else None
+    contour = np.frombuffer(data, np.uint8, n, 4 * n).reshape(h, w).copy() if len(data) == 5 * n else None
+    return dict(filled=filled, contour=contour, returncode=p.returncode, stderr=p.stderr)
+
+
 # ---------------------------------------------------------------------------
 # full-size images: the same restatement, run on row bands in threads
 # ---------------------------------------------------------------------------

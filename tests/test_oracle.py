@@ -118,12 +118,18 @@ def test_edge_decision_is_a_function_of_the_side_sums():
 
 def test_fill_web_holes_and_contour_semantics():
     web = np.array([[3, 0, 5, 2], [0, 7, 0, 1], [4, 4, 0, 9]], np.int32)
-    # one observable sweep for times=2 (the reference returns the buffer it READ last)
+    # the reference's SWAP swaps nothing (its local `tmp` shadows the buffer): every sweep reads
+    # the unfilled map, so times >= 1 is one sweep (tests/test_step3_cpu.py pins this to it)
     assert np.array_equal(oracle.fill_web_holes(web, 0), web)
     got1 = oracle.fill_web_holes(web, 1)
-    assert np.array_equal(got1, web)          # the only sweep's output is discarded
-    got2 = oracle.fill_web_holes(web, 2)
-    assert got2[0, 1] == (5 + 7 + 3 + 0) // 4 and got2[1, 0] == (7 + 4 + 2 + 3) // 4
+    want = web.copy()
+    want[0, 1] = (5 + 7 + 3 + 0) // 4                    # r u l d; d = p - w is outside: 0
+    want[1, 0] = (7 + 4 + 2 + 3) // 4                    # l = p - 1 is the previous row's last pixel
+    want[1, 2] = (1 + 0 + 7 + 5) // 4                    # u is a hole: read as 0, not as its fill
+    want[2, 2] = (9 + 0 + 4 + 0) // 4                    # u = p + w is outside; d is a hole
+    assert np.array_equal(got1, want)
+    for times in (2, 3, 32):
+        assert np.array_equal(oracle.fill_web_holes(web, times), want), times
     with pytest.raises(ZeroDivisionError):
         oracle.draw_contour_map(np.full((4, 4), 3, np.int32), 10)
     out = oracle.draw_contour_map(np.arange(1, 31, dtype=np.int32).reshape(5, 6), 10)
