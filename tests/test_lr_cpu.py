@@ -51,10 +51,17 @@ def rand_edges(w, h, seed, density=0.5):
 
 @pytest.mark.parametrize("mode", ["toroidal", "ghost"])
 @pytest.mark.parametrize("w,h,d,sw", [(40, 23, 12, 5), (33, 17, 45, 3), (31, 21, 7, 0), (17, 9, 9, 1),
-                                      (29, 30, 16, 9), (12, 11, 30, 7)])
+                                      (29, 30, 16, 9), (12, 11, 30, 7),
+                                      # the shapes the GPU sweeps reach (tests/test_lr_sweep_gpu.py): widths 1 to 9,
+                                      # D >= 3W, and the generic kernel's windows 27 and 31
+                                      (1, 6, 3, 0), (1, 4, 5, 1), (2, 5, 6, 1), (3, 7, 9, 3), (4, 3, 12, 3),
+                                      (5, 9, 15, 5), (6, 8, 19, 4), (7, 7, 21, 7), (8, 11, 24, 7), (9, 9, 27, 9),
+                                      (9, 4, 40, 3), (16, 12, 48, 11), (23, 5, 70, 5), (40, 27, 30, 27),
+                                      (27, 29, 81, 27), (31, 33, 93, 31)])
 def test_mirror_identity_equals_the_right_reference_definition(mode, w, h, d, sw):
-    """mirror(hot_path(mirror(eR), mirror(eL))) is the right-reference match written out -- odd widths,
-    more shifts than columns, a window of one pixel (S = 0 and 1) -- for both borders"""
+    """mirror(hot_path(mirror(eR), mirror(eL))) is the right-reference match written out -- widths from one
+    column, odd widths, more shifts than columns (up to 3W and more), windows of one pixel (S = 0 and 1) up to
+    the whole image (27 and 31) -- for both borders"""
     for seed, dens in ((1, 0.5), (2, 0.15)):
         el, er = rand_edges(w, h, seed + 10 * w, dens)
         ob, ow = lr.right_reference(el, er, d, sw, mode)
