@@ -391,8 +391,8 @@ int sm_debug_edge_table_fast(sm_plan *plan, double threshold, uint8_t *d_table,
  *   checked map holds s where kept, 0 where rejected.
  * The maps given to sm_lr_check come from the same plan and pairs (every value in 1..num_shifts); other
  * values get what the formula gives (ghost: u outside 0..W-1 is rejected) and no read outside a row.
- * Narrow maps and the SAD / SSD cost mode have no consistency check.  The workspace (mirrored packed
- * images and one mirrored-order map per pair) is allocated by sm_plan_reserve_lr or, without it, by the
+ * Narrow maps have no consistency check; the SAD / SSD cost mode has its own (sm_cost_lr, below).  The
+ * workspace (mirrored packed images and one mirrored-order map per pair) is allocated by sm_plan_reserve_lr or, without it, by the
  * first call that needs it (a hipMalloc, which synchronises the device).  All calls run in `stream`
  * order; on a pipelined plan (sm_plan_set_pipelined, sm_run_after) `stream` first waits for every
  * earlier call on the lanes, and the next call on the lanes waits for this one.  STREAM CAPTURE: as
@@ -413,8 +413,42 @@ int sm_run_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_r
               int pairs, int max_diff, int32_t *d_web, int32_t *d_best, int32_t *d_web_right,
               int32_t *d_rejected, void *stream);
 /* adds: allocates the mirrored packed images and the mirrored-order map of the calls above (counted in
- * sm_plan_workspace_bytes from then on); a plan that never calls them allocates neither.  Idempotent.  */
+ * sm_plan_workspace_bytes from then on); a plan that never calls them allocates neither.  Idempotent.
+ * The map is shared with the cost mode's check below: if sm_plan_reserve_cost_lr came first, only the
+ * mirrored packed images are added.                                                                    */
 int sm_plan_reserve_lr(sm_plan *plan);
+
+/* ---- left-right consistency check of the SAD / SSD cost mode --------------- *
+ * The same check with sm_cost_wta's map in place of the edge matcher's:
+ *   (best_right, web_right) = mirror(smo_cost_hot_path(mirror(R), mirror(L), D, S, border, cost)),
+ * i.e. right pixel u is scored against left pixel u - d: |R(u) - L(u - d)| or its square, toroidal:
+ * u - d mod W, ghost: L is 0 left of column 0 and window taps outside the image count 0; the minimum
+ * wins, the first shift on a tie.  The check of sm_lr_check then keeps left pixel x with s = web(x,y)
+ * iff |web_right(x + s - 1, y) - s| <= max_diff (toroidal: mod W; ghost: a match into the halo is
+ * rejected) and writes 0 for the others.  int32 maps only; windows up to 25 x 25 and at most 512 shifts
+ * (as sm_cost_wta's general kernel).  The right-reference map is the plan's own cost launch over the
+ * mirrored gray images, so every cost kernel sm_cost_wta can choose has a right-reference mode.
+ * Workspace: the mirrored gray images, 2 * round_up(max_pairs * W * H, 256) bytes, and the mirrored-order
+ * map of sm_plan_reserve_lr (max_pairs * W * H int32; allocated here unless the edge check has it
+ * already); allocated by sm_plan_reserve_cost_lr or, without it, by the first call that needs it (a
+ * hipMalloc, which synchronises the device), counted in sm_plan_workspace_bytes from then on, freed by
+ * sm_plan_destroy.  Arguments are checked before any device call.  All calls run in `stream` order; they
+ * use nothing the pipelined lanes use (sm_plan_set_pipelined, sm_run_after), so they neither wait for
+ * the lanes nor hold the next call on the lanes back.  The plan's calls share the mirrored-order map
+ * (and sm_cost_wta's LDS set-up): keep them on one stream.  STREAM CAPTURE: as sm_cost_wta, once
+ * sm_plan_reserve_cost_lr has been called; before, the call is refused with SM_ERR_ARG, a message naming
+ * it, and the capture valid.                                                                            */
+/* adds: the cost mode's right-reference map (and, d_best_right non-NULL, its winning costs), natural order */
+int sm_cost_wta_right(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int cost,
+                      int pairs, int32_t *d_web_right, int32_t *d_best_right, void *stream);
+/* adds: left cost WTA + right cost WTA + check in one call; d_web = checked map (0 = rejected),
+ * d_best = the left costs (exactly sm_cost_wta's); d_best / d_web_right / d_rejected may be NULL;
+ * d_rejected: one int32 per pair, the number of rejected pixels                                          */
+int sm_cost_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int cost, int pairs,
+               int max_diff, int32_t *d_web, int32_t *d_best, int32_t *d_web_right, int32_t *d_rejected,
+               void *stream);
+/* adds: allocates the mirrored gray images (and the mirrored-order map) of the two calls above; idempotent */
+int sm_plan_reserve_cost_lr(sm_plan *plan);
 
 /* ---- step 3 -------------------------------------------------------------- *
  * fill_web_holes (src/stereo.cu:235-256): every pixel that is 0 becomes the

@@ -122,6 +122,9 @@ _SIGNATURES = {
     "sm_run_lr": (_int, [_vp, _vp, _vp, _dbl, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "sm_plan_reserve_lr": (_int, [_vp]),
     "sm_cost_refine": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp]),
+    "sm_cost_wta_right": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "sm_cost_lr": (_int, [_vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    "sm_plan_reserve_cost_lr": (_int, [_vp]),
 }
 
 

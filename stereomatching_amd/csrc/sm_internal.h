@@ -107,7 +107,10 @@ struct sm_plan {
     // left-right consistency check (sm_lr.hip): NOT allocated with the plan, but by sm_plan_reserve_lr
     // or the first call that needs them; part of the workspace from then on
     u32 *d_ext_lr;       // mirrored packed images, d_ext's layout: side 0 = mirror(right), side 1 = mirror(left)
-    i32 *d_web_lr;       // right-reference map of sm_run_lr in mirrored order: max_pairs * W * H
+    i32 *d_web_lr;       // right-reference map of sm_run_lr / sm_cost_lr in mirrored order: max_pairs * W * H
+                         // (shared by the two checks: allocated by whichever reserves first)
+    u8 *d_gray_lr;       // sm_cost_lr: mirrored gray images, batch 0 = mirror(right), batch 1 = mirror(left),
+                         // each of max_pairs * W * H bytes starting 256-byte aligned (sm_plan_reserve_cost_lr)
     int cost_lds_raised; // sm_cost_wta: the LDS limit of this plan's four-wave SAD kernel is raised (on `device`)
     char describe[512];
 };
@@ -156,7 +159,7 @@ int sm_fail(int code, const char *fmt, ...);
 // sm_api.hip
 int sm_use_device(int device);                    // hipSetDevice, failure as SM_ERR_HIP
 bool sm_stream_capturing(hipStream_t st);         // is `st` recording into a graph?
-size_t sm_lr_workspace_bytes(const sm_plan *plan);    // sm_lr.hip: 0 until sm_plan_reserve_lr
+size_t sm_lr_workspace_bytes(const sm_plan *plan);    // sm_lr.hip: 0 until sm_plan_reserve_lr / _cost_lr
 void sm_lr_free(sm_plan *plan);                       // sm_lr.hip: sm_plan_destroy
 
 // sm_match_bs.hip (bit-sliced kernel; nullptr if not built for this window)

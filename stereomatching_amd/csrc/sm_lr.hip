@@ -8,6 +8,12 @@
 // kernel variant the plan can choose gets a right-reference mode without a new instantiation.
 // The new kernels: k_mirror_ext (packed images -> mirrored packed images, a row of words in
 // reverse order, each bit-reversed) and k_lr_check (one pass over the left map, bandwidth bound).
+//
+// The SAD / SSD cost mode's check is the same construction on the gray images:
+//     web_right = mirror(cost_hot_path(mirror(R), mirror(L)))
+// by the plan's own sm_cost_wta launch over the images k_mirror_gray writes -- every cost kernel
+// (quad-SAD, matrix-core SSD, the ghost strip, the general kernel) without a new instantiation --
+// then the same k_lr_check.
 
 #include "sm_internal.h"
 
@@ -104,6 +110,15 @@ __device__ __forceinline__ void lr_count(i32 *rejected, int cnt)
     }
 }
 
+// the per-pair counts k_lr_check adds to, zeroed by a kernel rather than hipMemsetAsync: captured into a graph, the
+// memset of these 4-byte counts filled them with 0x08080808 instead of 0 on the second replay (measured on MI355X,
+// DESIGN.md section 12); a kernel node replays as captured
+__global__ __launch_bounds__(64) void k_lr_zero_counts(i32 *rejected, int pairs)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < pairs) rejected[i] = 0;
+}
+
 // The check, one pass over the left map: web (in place allowed: out == web, so neither is
 // __restrict__), the gather from the right-reference row, out, and -- MIRRORED, right_out
 // non-NULL -- the right-reference map in natural order.  Grid: x strides over the pixels of one
@@ -165,6 +180,39 @@ __global__ __launch_bounds__(256) void k_lr_unmirror(i32 *web, i32 *best, int W,
     }
 }
 
+// Mirrored gray images for the cost mode's right-reference pass (sm_cost_wta_right, sm_cost_lr): output
+// side 0 (the pass's "left" batch) is mirror(R), side 1 is mirror(L), each row reversed byte by byte.
+// Grid: x = image row of the batch (pair * H + y), y = 256-unit segment of the row, z = side.  A lane
+// moves V bytes: 16 where W % 16 == 0 (and the inputs are 16-byte aligned; 4K rows), 4 where
+// W % 4 == 0, else 1.  Lane j of a row writes unit j and reads unit W/V - 1 - j: the wave's loads and
+// its stores each cover one contiguous span (1 KiB at V = 16), the loads in descending order.  A unit
+// is reversed in registers: the dwords in reverse order, each byte-reversed with v_perm_b32.  Rows of
+// V = 16 and V = 4 start V-aligned because W is a multiple of V and the bases are (checked by the host;
+// the output batches are 256-byte aligned).
+__device__ __forceinline__ u32 lr_bswap(u32 v) { return __builtin_amdgcn_perm(v, v, 0x00010203u); }
+
+template <int V>
+__global__ __launch_bounds__(256) void k_mirror_gray(const u8 *__restrict__ left, const u8 *__restrict__ right,
+                                                     u8 *__restrict__ dst, size_t batch_stride, int W)
+{
+    const int units = W / V;
+    const int j = blockIdx.y * 256 + threadIdx.x;
+    if (j >= units) return;
+    const int side = blockIdx.z;
+    const size_t row = (size_t)blockIdx.x * W;
+    const u8 *s = (side ? left : right) + row;
+    u8 *d = dst + side * batch_stride + row;
+    const int k = units - 1 - j;
+    if constexpr (V == 16) {
+        const uint4 v = reinterpret_cast<const uint4 *>(s)[k];
+        reinterpret_cast<uint4 *>(d)[j] = make_uint4(lr_bswap(v.w), lr_bswap(v.z), lr_bswap(v.y), lr_bswap(v.x));
+    } else if constexpr (V == 4) {
+        reinterpret_cast<u32 *>(d)[j] = lr_bswap(reinterpret_cast<const u32 *>(s)[k]);
+    } else {
+        d[j] = s[k];
+    }
+}
+
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
@@ -174,17 +222,46 @@ static size_t lr_map_bytes(const sm_plan *plan)
     return (size_t)plan->max_pairs * plan->width * plan->height * sizeof(i32);
 }
 
+// one batch of mirrored gray images (sm_cost_lr), rounded up so that the second batch starts 256-byte aligned
+static size_t lr_gray_batch_bytes(const sm_plan *plan)
+{
+    return ((size_t)plan->max_pairs * plan->width * plan->height + 255) & ~(size_t)255;
+}
+
 size_t sm_lr_workspace_bytes(const sm_plan *plan)
 {
-    return plan->d_ext_lr ? plan->ext_bytes + lr_map_bytes(plan) : 0;
+    return (plan->d_ext_lr ? plan->ext_bytes : 0) + (plan->d_web_lr ? lr_map_bytes(plan) : 0) +
+           (plan->d_gray_lr ? 2 * lr_gray_batch_bytes(plan) : 0);
 }
 
 void sm_lr_free(sm_plan *plan)
 {
     if (plan->d_ext_lr) (void)hipFree(plan->d_ext_lr);
     if (plan->d_web_lr) (void)hipFree(plan->d_web_lr);
+    if (plan->d_gray_lr) (void)hipFree(plan->d_gray_lr);
     plan->d_ext_lr = nullptr;
     plan->d_web_lr = nullptr;
+    plan->d_gray_lr = nullptr;
+}
+
+// `*buf` (bytes long) and, if the plan has none yet, the mirrored-order map shared by both checks; on failure
+// neither is kept (what the plan had before stays)
+static int reserve_with_map(sm_plan *plan, void **buf, size_t bytes, bool zero, const char *what, const char *me)
+{
+    void *b = nullptr, *map = nullptr;
+    const bool need_map = !plan->d_web_lr;
+    hipError_t e = hipMalloc(&b, bytes);
+    if (e == hipSuccess && zero) e = hipMemset(b, 0, bytes);
+    if (e == hipSuccess && need_map) e = hipMalloc(&map, lr_map_bytes(plan));
+    if (e != hipSuccess) {
+        if (b) (void)hipFree(b);
+        if (map) (void)hipFree(map);
+        return sm_fail(e == hipErrorOutOfMemory ? SM_ERR_NOMEM : SM_ERR_HIP, "%s: %zu bytes for the %s and map of the "
+                       "consistency check: %s", me, bytes + (need_map ? lr_map_bytes(plan) : 0), what, hipGetErrorString(e));
+    }
+    *buf = b;
+    if (need_map) plan->d_web_lr = (i32 *)map;
+    return SM_OK;
 }
 
 // the mirrored packed images (zero-filled: the words beyond each side's row extent stay zero) and the
@@ -192,15 +269,15 @@ void sm_lr_free(sm_plan *plan)
 static int reserve_lr(sm_plan *plan, const char *me)
 {
     if (plan->d_ext_lr) return SM_OK;
-    hipError_t e = hipMalloc((void **)&plan->d_ext_lr, plan->ext_bytes);
-    if (e == hipSuccess) e = hipMemset(plan->d_ext_lr, 0, plan->ext_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&plan->d_web_lr, lr_map_bytes(plan));
-    if (e != hipSuccess) {
-        sm_lr_free(plan);
-        return sm_fail(e == hipErrorOutOfMemory ? SM_ERR_NOMEM : SM_ERR_HIP, "%s: %zu bytes for the mirrored images and "
-                       "map of the consistency check: %s", me, plan->ext_bytes + lr_map_bytes(plan), hipGetErrorString(e));
-    }
-    return SM_OK;
+    return reserve_with_map(plan, (void **)&plan->d_ext_lr, plan->ext_bytes, true, "mirrored images", me);
+}
+
+// the mirrored gray images (every byte a cost launch reads is written by k_mirror_gray first) and the map
+static int reserve_cost_lr(sm_plan *plan, const char *me)
+{
+    if (plan->d_gray_lr) return SM_OK;
+    return reserve_with_map(plan, (void **)&plan->d_gray_lr, 2 * lr_gray_batch_bytes(plan), false,
+                            "mirrored gray images", me);
 }
 
 extern "C" int sm_plan_reserve_lr(sm_plan *plan)
@@ -277,7 +354,10 @@ static int lr_check_launch(const sm_plan *plan, bool mirrored, const i32 *web, c
     const int W = plan->width;
     const unsigned npx = (unsigned)W * plan->height;
     const int ghost = plan->border == SM_GHOST;
-    if (rejected) SM_HIP(hipMemsetAsync(rejected, 0, (size_t)pairs * sizeof(i32), st));
+    if (rejected) {
+        hipLaunchKernelGGL(k_lr_zero_counts, dim3((pairs + 63) / 64), dim3(64), 0, st, rejected, pairs);
+        SM_LAUNCH_CHECK("k_lr_zero_counts");
+    }
     const bool vec = W % 4 == 0 && (((uintptr_t)web | (uintptr_t)right | (uintptr_t)out | (uintptr_t)right_out) & 15) == 0;
     const unsigned lanes = vec ? npx / 4 : npx;
     const dim3 grid(std::min((lanes + 255) / 256, (unsigned)SM_LR_BLOCKS), pairs), block(256);
@@ -376,5 +456,111 @@ extern "C" int sm_run_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_
     SM_TRY(lr_match(plan, plan->d_ext, pairs, d_web, d_best, st));
     SM_TRY(lr_mirror(plan, pairs, st));
     SM_TRY(lr_match(plan, plan->d_ext_lr, pairs, plan->d_web_lr, nullptr, st));
+    return lr_check_launch(plan, true, d_web, plan->d_web_lr, d_web, d_web_right, d_rejected, max_diff, pairs, st);
+}
+
+// ---------------------------------------------------------------------------
+// the SAD / SSD cost mode's check
+// ---------------------------------------------------------------------------
+
+extern "C" int sm_plan_reserve_cost_lr(sm_plan *plan)
+{
+    if (!plan) return sm_fail(SM_ERR_ARG, "sm_plan_reserve_cost_lr: plan is NULL");
+    SM_TRY(sm_use_device(plan->device));
+    return reserve_cost_lr(plan, "sm_plan_reserve_cost_lr");
+}
+
+// what the cost entries check besides their maps (before any device call): cost, plan, pairs, the general kernel's reach
+static int cost_lr_args(const sm_plan *plan, int cost, int pairs, const char *me)
+{
+    if (cost != SM_COST_SAD && cost != SM_COST_SSD)
+        return sm_fail(SM_ERR_ARG, "%s: cost %d is neither SM_COST_SAD nor SM_COST_SSD", me, cost);
+    SM_TRY(check_pairs(plan, pairs, me));
+    const int n = 2 * (plan->square_width / 2) + 1;
+    if (n > 25 || plan->num_shifts > 512)
+        return sm_fail(SM_ERR_ARG, "%s: built for windows up to 25x25 and at most 512 shifts (got %dx%d, %d)", me, n, n,
+                       plan->num_shifts);
+    return SM_OK;
+}
+
+// the workspace, allocated here when sm_plan_reserve_cost_lr was not called -- unless the stream is capturing
+static int need_cost_lr(sm_plan *plan, hipStream_t st, const char *me)
+{
+    if (plan->d_gray_lr) return SM_OK;
+    if (sm_stream_capturing(st))
+        return sm_fail(SM_ERR_ARG, "%s: the workspace of the cost mode's consistency check is not allocated and the stream "
+                       "is capturing (an allocation cannot be captured): call sm_plan_reserve_cost_lr(plan) first", me);
+    return reserve_cost_lr(plan, me);
+}
+
+// k_mirror_gray: mirror(right) into the workspace's first batch, mirror(left) into its second; returns the two
+static int cost_lr_mirror(sm_plan *plan, const uint8_t *left, const uint8_t *right, int pairs, hipStream_t st,
+                          const u8 **mleft, const u8 **mright)
+{
+    const int W = plan->width;
+    const size_t batch = lr_gray_batch_bytes(plan);
+    const uintptr_t a = (uintptr_t)left | (uintptr_t)right;
+    const int v = W % 16 == 0 && (a & 15) == 0 ? 16 : W % 4 == 0 && (a & 3) == 0 ? 4 : 1;
+    const dim3 grid((unsigned)pairs * plan->height, (W / v + 255) / 256, 2), block(256);
+    if (v == 16) hipLaunchKernelGGL(k_mirror_gray<16>, grid, block, 0, st, left, right, plan->d_gray_lr, batch, W);
+    else if (v == 4) hipLaunchKernelGGL(k_mirror_gray<4>, grid, block, 0, st, left, right, plan->d_gray_lr, batch, W);
+    else hipLaunchKernelGGL(k_mirror_gray<1>, grid, block, 0, st, left, right, plan->d_gray_lr, batch, W);
+    SM_LAUNCH_CHECK("k_mirror_gray");
+    *mleft = plan->d_gray_lr;
+    *mright = plan->d_gray_lr + batch;
+    return SM_OK;
+}
+
+extern "C" int sm_cost_wta_right(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int cost,
+                                 int pairs, int32_t *d_web_right, int32_t *d_best_right, void *stream)
+{
+    const char *me = "sm_cost_wta_right";
+    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
+    if (!d_web_right) return sm_fail(SM_ERR_ARG, "%s: d_web_right is NULL", me);
+    SM_TRY(cost_lr_args(plan, cost, pairs, me));
+    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
+    if (d_best_right && overlap(d_web_right, d_best_right, map))
+        return sm_fail(SM_ERR_ARG, "%s: d_web_right and d_best_right overlap", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    SM_TRY(need_cost_lr(plan, st, me));
+    const u8 *ml, *mr;
+    SM_TRY(cost_lr_mirror(plan, d_gray_left, d_gray_right, pairs, st, &ml, &mr));
+    // the plan's cost launch over the mirrored images writes the maps in mirrored order; they are turned round in place
+    SM_TRY(sm_cost_wta(plan, ml, mr, cost, pairs, d_web_right, d_best_right, stream));
+    const int W = plan->width;
+    const unsigned half_w = (unsigned)(W + 1) / 2, half_px = half_w * plan->height;
+    hipLaunchKernelGGL(k_lr_unmirror, dim3((half_px + 255) / 256, pairs), dim3(256), 0, st, d_web_right, d_best_right,
+                       W, (unsigned)W * plan->height, half_w, half_px);
+    SM_LAUNCH_CHECK("k_lr_unmirror");
+    return SM_OK;
+}
+
+extern "C" int sm_cost_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int cost, int pairs,
+                          int max_diff, int32_t *d_web, int32_t *d_best, int32_t *d_web_right, int32_t *d_rejected,
+                          void *stream)
+{
+    const char *me = "sm_cost_lr";
+    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
+    if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
+    if (max_diff < 0) return sm_fail(SM_ERR_ARG, "%s: max_diff %d is negative", me, max_diff);
+    SM_TRY(cost_lr_args(plan, cost, pairs, me));
+    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
+    if ((d_best && overlap(d_best, d_web, map)) || (d_web_right && overlap(d_web_right, d_web, map)) ||
+        (d_best && d_web_right && overlap(d_best, d_web_right, map)))
+        return sm_fail(SM_ERR_ARG, "%s: result maps overlap", me);
+    const size_t counts = (size_t)pairs * sizeof(i32);
+    if (d_rejected && (overlap(d_rejected, d_web, counts, map) || (d_best && overlap(d_rejected, d_best, counts, map)) ||
+                       (d_web_right && overlap(d_rejected, d_web_right, counts, map))))
+        return sm_fail(SM_ERR_ARG, "%s: d_rejected overlaps a map", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    SM_TRY(need_cost_lr(plan, st, me));
+    // the left cost launch (sm_cost_wta's maps exactly), the mirrored images, the right launch into the mirrored-order
+    // map, and the check, which gathers from that map
+    SM_TRY(sm_cost_wta(plan, d_gray_left, d_gray_right, cost, pairs, d_web, d_best, stream));
+    const u8 *ml, *mr;
+    SM_TRY(cost_lr_mirror(plan, d_gray_left, d_gray_right, pairs, st, &ml, &mr));
+    SM_TRY(sm_cost_wta(plan, ml, mr, cost, pairs, plan->d_web_lr, nullptr, stream));
     return lr_check_launch(plan, true, d_web, plan->d_web_lr, d_web, d_web_right, d_rejected, max_diff, pairs, st);
 }

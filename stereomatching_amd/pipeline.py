@@ -35,7 +35,7 @@ class AlgorithmParams:
 
 
 class LRResult(NamedTuple):
-    """StereoPlan.run_lr: the checked map (0 = rejected), rejected pixels per pair, and the optional maps"""
+    """StereoPlan.run_lr / cost_lr: the checked map (0 = rejected), rejected pixels per pair, and the optional maps"""
     web: torch.Tensor
     rejected: torch.Tensor
     web_right: Optional[torch.Tensor]
@@ -125,6 +125,12 @@ class StereoPlan:
         """The workspace of the left-right consistency check (mirrored packed images, one mirrored-order map per
         pair), allocated now: keeps the allocation out of timed paths and out of stream captures."""
         check(lib.sm_plan_reserve_lr(self._h))
+
+    def reserve_cost_lr(self):
+        """The workspace of the cost mode's consistency check (mirrored gray images, and the mirrored-order map if
+        reserve_lr has not allocated it), allocated now: keeps the allocation out of timed paths and out of stream
+        captures."""
+        check(lib.sm_plan_reserve_cost_lr(self._h))
 
     def time_kernels(self, capacity: int, every: int = 1):
         """Bracket every `every`-th of the coming match launches (at most `capacity` of
@@ -323,6 +329,37 @@ class StereoPlan:
         check(lib.sm_cost_wta(self._h, _ptr(left), _ptr(right), {"sad": 1, "ssd": 2}[cost], pairs,
                               _ptr(web), _ptr(best), self._stream()))
         return web, best
+
+    def cost_wta_right(self, left, right, cost="sad", want_best=True, web_right=None, best_right=None):
+        """The cost mode's right-reference map (sm_cost_wta_right) -> (web_right, best_right): web_right(u, y) = s'
+        means right pixel u matched left pixel u - (s' - 1), best_right its window cost."""
+        left = self._images(left, torch.uint8, "left")
+        right = self._images(right, torch.uint8, "right")
+        pairs = left.shape[0]
+        if right.shape[0] != pairs:
+            raise ValueError(f"right: {right.shape[0]} images for {pairs} pairs")
+        web_right = self._out(web_right, pairs, "web_right")
+        best_right = self._out(best_right, pairs, "best_right") if want_best else None
+        check(lib.sm_cost_wta_right(self._h, _ptr(left), _ptr(right), {"sad": 1, "ssd": 2}[cost], pairs,
+                                    _ptr(web_right), _ptr(best_right), self._stream()))
+        return web_right, best_right
+
+    def cost_lr(self, left, right, cost="sad", max_diff=0, want_right=False, want_best=False, web=None,
+                web_right=None, best=None) -> LRResult:
+        """Left cost WTA, right cost WTA and check in one call (sm_cost_lr) -> LRResult(web, rejected, web_right,
+        best); web is the checked map (0 = rejected), best the left window costs as cost_wta gives them."""
+        left = self._images(left, torch.uint8, "left")
+        right = self._images(right, torch.uint8, "right")
+        pairs = left.shape[0]
+        if right.shape[0] != pairs:
+            raise ValueError(f"right: {right.shape[0]} images for {pairs} pairs")
+        web = self._out(web, pairs, "web")
+        web_right = self._out(web_right, pairs, "web_right") if want_right else None
+        best = self._out(best, pairs, "best") if want_best else None
+        rejected = torch.empty(pairs, dtype=torch.int32, device=self._dev)
+        check(lib.sm_cost_lr(self._h, _ptr(left), _ptr(right), {"sad": 1, "ssd": 2}[cost], pairs, int(max_diff),
+                             _ptr(web), _ptr(best), _ptr(web_right), _ptr(rejected), self._stream()))
+        return LRResult(web, rejected, web_right, best)
 
     def cost_refine(self, left, right, web, cost="sad", want_costs=False, out=None):
         """Subpixel refinement of a cost_wta map (sm_cost_refine) -> (sub, costs): sub is int16 in 1/16 of a shift
