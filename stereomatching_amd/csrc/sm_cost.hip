@@ -283,7 +283,8 @@ static int launch_general(sm_plan *plan, const uint8_t *d_gray_left, const uint8
     g.tile_h = th;
     g.tiles_y = (g.h + th - 1) / th;
     g.nsr = th + g.n - 1;
-    g.vec_ok = g.w % 4 == 0;
+    // int4 stores need rows that start 16-byte aligned: W % 4 == 0 and 16-byte aligned maps (d_best may be NULL)
+    g.vec_ok = g.w % 4 == 0 && (((uintptr_t)d_web | (uintptr_t)d_best) & 15) == 0;
     const bool ssd = cost == SM_COST_SSD, ghost = plan->border == SM_GHOST;
     const void *fn;
     switch (nwd) {

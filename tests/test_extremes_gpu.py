@@ -15,7 +15,7 @@ import torch
 from tests import extreme_patterns as xp
 from tests import lr_reference as lr
 from tests import oracle
-from tests.test_hip_gpu import BUILT_BS, NO_CAP2, ONE_WAVE, TWO_WAVES
+from tests.test_hip_gpu import BUILT_BS, NO_CAP2, ONE_WAVE, TWO_WAVES, poisoned
 from tests.test_lr_gpu import KERNEL_CHOICES
 
 pytestmark = pytest.mark.gpu
@@ -75,7 +75,8 @@ def match_batch(hip, le, re, d, sw, mode, options=None, web_dtype=torch.int32):
     h, w = le.shape[-2:]
     plan = hip.StereoPlan(w, h, d, sw, mode, max_pairs=len(le), options=options)
     plan.load_edges(dev(le), dev(re))
-    web, best = plan.match_wta(len(le), want_best=True, web_dtype=web_dtype)
+    web, best = plan.match_wta(len(le), want_best=True, web=poisoned(len(le), h, w, web_dtype),
+                               best=poisoned(len(le), h, w), web_dtype=web_dtype)
     torch.cuda.synchronize()
     desc = plan.describe()
     plan.close()
@@ -197,7 +198,8 @@ def test_right_reference_mode_at_the_extremes(hip, opts, sw, d, mode):
 def cost_batch(hip, left, right, d, sw, mode, cost, options=None):
     h, w = left.shape[-2:]
     plan = hip.StereoPlan(w, h, d, sw, mode, max_pairs=len(left), options=options)
-    web, best = plan.cost_wta(dev(left), dev(right), cost)
+    web, best = plan.cost_wta(dev(left), dev(right), cost, web=poisoned(len(left), h, w),
+                              best=poisoned(len(left), h, w))
     torch.cuda.synchronize()
     plan.close()
     return host(best), host(web)

@@ -15,7 +15,7 @@ from stereomatching_amd.synth import make_pair
 from tests import lr_reference as lr
 from tests import oracle
 from tests.test_extremes_gpu import differences
-from tests.test_hip_gpu import BUILT_BS
+from tests.test_hip_gpu import BUILT_BS, poisoned
 from tests.test_lr_gpu import KERNEL_CHOICES, expected_lr
 
 pytestmark = pytest.mark.gpu
@@ -53,7 +53,10 @@ def check_run_lr(plan, tag, left, right, d, sw, mode, max_diff, want_right=True,
     these pairs, when already known"""
     pairs = len(left)
     want = expect or [expected_lr(left[q], right[q], d, sw, mode, max_diff) for q in range(pairs)]
-    res = plan.run_lr(dev(left), dev(right), 0.15, max_diff=max_diff, want_right=want_right, want_best=want_best)
+    h, w = left.shape[-2:]
+    res = plan.run_lr(dev(left), dev(right), 0.15, max_diff=max_diff, want_right=want_right, want_best=want_best,
+                      web=poisoned(pairs, h, w), web_right=poisoned(pairs, h, w) if want_right else None,
+                      best=poisoned(pairs, h, w) if want_best else None)
     bad = compare(f"{tag} run_lr", "web", host(res.web), [x["checked"] for x in want])
     got_rej, want_rej = host(res.rejected).tolist(), [x["rejected"] for x in want]
     if got_rej != want_rej:
@@ -67,7 +70,9 @@ def check_run_lr(plan, tag, left, right, d, sw, mode, max_diff, want_right=True,
 
 def check_right_reference(plan, tag, pairs, want_web, want_best):
     """sm_match_wta_right on the edges the plan holds -> list of differences"""
-    web_right, best_right = plan.match_wta_right(pairs)
+    h, w = want_web[0].shape
+    web_right, best_right = plan.match_wta_right(pairs, web_right=poisoned(pairs, h, w),
+                                                 best_right=poisoned(pairs, h, w))
     return (compare(f"{tag} match_wta_right", "web_right", host(web_right), want_web) +
             compare(f"{tag} match_wta_right", "best_right", host(best_right), want_best))
 
