@@ -450,6 +450,52 @@ int sm_cost_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_
 /* adds: allocates the mirrored gray images (and the mirrored-order map) of the two calls above; idempotent */
 int sm_plan_reserve_cost_lr(sm_plan *plan);
 
+/* ---- census cost mode: PARITY UNPINNED ------------------------------------- *
+ * New work (no reference counterpart, like SAD / SSD).  A matching cost that only sees the ORDER of a
+ * pixel against its neighbours, so a strictly increasing change of either image's intensities (gain, offset, gamma
+ * of one camera) leaves every descriptor, and so every map, exactly as it was.  census_width c in {3, 5, 7} is a
+ * per-call argument, independent of square_width; h = c / 2.
+ *   descriptor C_I(x, y): a uint64; the neighbours (dx, dy) of the c x c window in row-major order (dy outer, dx
+ *     inner) without (0, 0), the k-th gives bit k (bit 0 least significant) = I(x+dx, y+dy) < I(x, y), strictly;
+ *     8, 24 or 48 bits, the higher ones 0.  Toroidal: neighbour coordinates wrap (mod W, mod H); ghost: a neighbour
+ *     outside the image reads 0, so a halo pixel's descriptor is 0.
+ *   cost c_d(x, y) = popcount(C_L(x, y) XOR C_R(x + d, y)); toroidal: x + d mod W; ghost: C_R = 0 for x + d >= W.
+ *   A_d = n x n window sum of c_d (toroidal: taps wrap; ghost: taps outside the image count 0), A_d <= 48 * 625;
+ *   best = min_d A_d, web = 1 + the FIRST d reaching it.
+ *   right reference: (best_right, web_right) = mirror(census_wta(mirror(R), mirror(L))), mirror(a)(x) = a(W-1-x);
+ *     mirroring permutes the bits of every descriptor alike, so the pass reads the left pass's descriptors in
+ *     mirrored order.  The check is sm_lr_check's (section 10).
+ *   subpixel: sm_cost_refine's SM_COST_SAD (equiangular) formula and edge rules on the census window costs
+ *     C(s-2), C(s-1), C(s); d_costs -1 where a cost does not exist.
+ * Windows up to 25 x 25 and at most 512 shifts.  Arguments are checked before any device call; a refusal names the
+ * function.  Workspace: the descriptors of both images of max_pairs pairs (8 bytes per pixel, 133 MB per 4K pair;
+ * 4-byte descriptors inside it for c <= 5) and the mirrored-order map of sm_plan_reserve_lr (added only if the plan has
+ * none yet); allocated by sm_plan_reserve_census or, without it, by the first call that needs it (a hipMalloc, which
+ * synchronises the device), counted in sm_plan_workspace_bytes from then on, freed by sm_plan_destroy.  A plan that
+ * never calls these allocates nothing.  All calls run in `stream` order and use nothing the pipelined lanes use.
+ * STREAM CAPTURE: once sm_plan_reserve_census has been called; before, a call that needs the workspace is refused
+ * with SM_ERR_ARG, a message naming it, and the capture valid.                                                  */
+/* adds: the descriptors of `images` consecutive gray images (images <= 2 * max_pairs) into d_desc, one uint64 per
+ * pixel; needs no workspace                                                                                      */
+int sm_census_transform(sm_plan *plan, const uint8_t *d_gray, int census_width, int images, uint64_t *d_desc,
+                        void *stream);
+/* adds: the census arg-min -> d_web (and, d_best non-NULL, the window costs), int32 maps */
+int sm_census_wta(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width, int pairs,
+                  int32_t *d_web, int32_t *d_best, void *stream);
+/* adds: the right-reference map (and, d_best_right non-NULL, its costs), natural order */
+int sm_census_wta_right(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+                        int pairs, int32_t *d_web_right, int32_t *d_best_right, void *stream);
+/* adds: the descriptors once, left and right arg-min and the check (tolerance max_diff >= 0): d_web = checked map
+ * (0 = rejected), d_best = the left costs; d_best / d_web_right / d_rejected (one int32 per pair) may be NULL    */
+int sm_census_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width, int pairs,
+                 int max_diff, int32_t *d_web, int32_t *d_best, int32_t *d_web_right, int32_t *d_rejected,
+                 void *stream);
+/* adds: subpixel refinement of a census map: d_sub int16 in 1/16 of a shift; d_costs NULL or [pairs][3][H][W] */
+int sm_census_refine(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+                     int pairs, const int32_t *d_web, int16_t *d_sub, int32_t *d_costs, void *stream);
+/* adds: allocates the census workspace now; idempotent */
+int sm_plan_reserve_census(sm_plan *plan);
+
 /* ---- step 3 -------------------------------------------------------------- *
  * fill_web_holes (src/stereo.cu:235-256): every pixel that is 0 becomes the
  * truncated mean of its four flat-index neighbours.  The reference's pointer

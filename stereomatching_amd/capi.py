@@ -125,6 +125,12 @@ _SIGNATURES = {
     "sm_cost_wta_right": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp]),
     "sm_cost_lr": (_int, [_vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "sm_plan_reserve_cost_lr": (_int, [_vp]),
+    "sm_census_transform": (_int, [_vp, _vp, _int, _int, _vp, _vp]),
+    "sm_census_wta": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "sm_census_wta_right": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "sm_census_lr": (_int, [_vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    "sm_census_refine": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp]),
+    "sm_plan_reserve_census": (_int, [_vp]),
 }
 
 

@@ -978,6 +978,7 @@ extern "C" void sm_plan_destroy(sm_plan *plan)
     for (int b = 0; b < 2; b++) (void)hipEventDestroy(plan->ev_fork[b]);
     if (plan->d_web_tmp) (void)hipFree(plan->d_web_tmp);
     sm_lr_free(plan);
+    sm_census_free(plan);
     (void)hipFree(plan->d_flags);
     (void)hipFree(plan->d_edge_tab);
     (void)hipHostFree(plan->h_flags);
@@ -1025,7 +1026,8 @@ extern "C" size_t sm_plan_workspace_bytes(const sm_plan *plan)
 {
     if (!plan) return 0;
     const size_t staging = plan->d_web_tmp ? (size_t)plan->max_pairs * plan->width * plan->height * sizeof(i32) : 0;
-    return 2 * plan->ext_bytes + 4 * sizeof(i32) + 768 * sizeof(u32) + staging + sm_lr_workspace_bytes(plan);
+    return 2 * plan->ext_bytes + 4 * sizeof(i32) + 768 * sizeof(u32) + staging + sm_lr_workspace_bytes(plan) +
+           sm_census_workspace_bytes(plan);
 }
 
 // synchronise `st` and return the plan's flags as they were at that point; flags in

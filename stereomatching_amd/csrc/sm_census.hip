@@ -1,0 +1,742 @@
+// sm_census.hip -- census cost mode: census transform, Hamming-distance cost, n x n box sum, first-minimum arg-min,
+// the right-reference pass and the check, and the equiangular subpixel fit (include/stereo_hip.h).
+//
+// PARITY UNPINNED, like SAD / SSD: the reference has no census mode.  Definition (census width c in {3, 5, 7}):
+//   C_I(x, y) bit k = I(x + dx, y + dy) < I(x, y), the k-th neighbour of the c x c window in row-major order without
+//   (0, 0); toroidal: coordinates wrap; ghost: a neighbour outside the image reads 0 (a halo pixel's descriptor is 0);
+//   c_d(x, y) = popcount(C_L(x, y) ^ C_R(x + d, y)) (toroidal: x + d mod W; ghost: C_R = 0 past the right border);
+//   A_d = n x n window sum of c_d (toroidal: taps wrap; ghost: taps outside the image count 0);
+//   best = min_d A_d, web = 1 + the first d reaching it.
+//
+// Kernels:
+//   k_census_transform  descriptors of a batch of images, a 64 x 16 tile per workgroup from gray rows staged in LDS
+//                       with the border rule applied (coalesced row loads; 64 consecutive descriptors per wave store).
+//   k_census_wta        the cost, the box sum and the arg-min.  The descriptor rows stream through a ring of n + 1 rows
+//                       in LDS while the tile marches down.  A lane owns 4 columns x 8 shifts and keeps their VERTICAL
+//                       window sums in VGPRs: per row it adds the Hamming costs of the row that enters and subtracts
+//                       those of the row that leaves -- each (column, shift, row) cost is computed once per slide, one
+//                       v_bcnt per descriptor dword.  The horizontal sums go through LDS as packed u16 (A_d <= 48 * 625
+//                       = 30000): every lane publishes its 4 x 8 column sums, and the lanes of the tile's output columns
+//                       slide an n-wide window over them with v_pk_add_u16 / v_pk_sub_u16.  The shift range of a column
+//                       group is split over nl adjacent lanes whose keys (A << 16 | d) are merged with DPP.  At most 128
+//                       shifts per launch: wider ranges take several launches, each merging its keys into the web map
+//                       (first-wins: the smaller key), the last one writing web and best.  MIRROR: the right-reference
+//                       pass, the left pass over mirror(R), mirror(L).  Mirroring an image permutes every descriptor's
+//                       bits the same way, and Hamming distance is blind to that, so the pass reads the left pass's
+//                       descriptors in mirrored order and writes its maps in natural order.
+//   k_census_refine     the three window costs C(s-2), C(s-1), C(s) of each pixel, 3 n^2 taps, and sm_cost_refine's
+//                       equiangular fit.
+
+#include "sm_internal.h"
+
+typedef unsigned long long u64;
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+
+#define SMN_TX 64          // transform: columns per workgroup
+#define SMN_TR 16          // transform: rows per workgroup (4 per lane)
+#define SMN_DS 8           // wta: shifts per lane
+#define SMN_DCHUNK 128     // wta: shifts per launch at most
+#define SMN_PFMAX 9        // wta: descriptors one lane fetches per ring row at most (checked by the host)
+#define SMN_THREADS 512    // wta: threads per workgroup at most
+
+__device__ __forceinline__ int smn_mod(int v, int m)
+{
+    int r = v % m;
+    return r < 0 ? r + m : r;
+}
+
+// ---------------------------------------------------------------------------
+// transform
+// ---------------------------------------------------------------------------
+
+// Images z < n_a come from src_a and go to dst + z * W * H; the others from src_b, to dst + dst_b + (z - n_a) * W * H
+// (in descriptors of NW dwords).  Workgroup 64 x 4 threads, a tile of 64 columns x 16 rows.
+template <int CW, int NW, bool GHOST>
+__global__ __launch_bounds__(256) void k_census_transform(const u8 *__restrict__ src_a, const u8 *__restrict__ src_b,
+                                                          int n_a, u32 *__restrict__ dst, long long dst_b, int W, int H)
+{
+    constexpr int HC = CW / 2, SW = SMN_TX + 2 * HC, SH = SMN_TR + 2 * HC;
+    __shared__ u8 tile[SH][SW + 1];
+    const int z = blockIdx.z;
+    const bool b = z >= n_a;
+    const size_t npx = (size_t)W * H;
+    const u8 *src = b ? src_b + (size_t)(z - n_a) * npx : src_a + (size_t)z * npx;
+    u32 *out = dst + (size_t)NW * ((b ? (size_t)dst_b : 0) + (size_t)(b ? z - n_a : z) * npx);
+    const int x0 = blockIdx.x * SMN_TX, y0 = blockIdx.y * SMN_TR;
+    const int tid = threadIdx.y * SMN_TX + threadIdx.x;
+    for (int i = tid; i < SH * SW; i += 256) {
+        const int r = i / SW, c = i - r * SW;
+        const int x = x0 - HC + c, y = y0 - HC + r;
+        u8 v = 0;
+        if (GHOST) {
+            if (x >= 0 && x < W && y >= 0 && y < H) v = src[(size_t)y * W + x];
+        } else {
+            v = src[(size_t)smn_mod(y, H) * W + smn_mod(x, W)];
+        }
+        tile[r][c] = v;
+    }
+    __syncthreads();
+    const int x = x0 + threadIdx.x;
+    if (x >= W) return;
+#pragma unroll
+    for (int q = 0; q < SMN_TR / 4; q++) {
+        const int ry = threadIdx.y + 4 * q;
+        const int y = y0 + ry;
+        if (y >= H) break;
+        const u32 c = tile[ry + HC][threadIdx.x + HC];
+        u32 lo = 0, hi = 0;
+        int k = 0;
+#pragma unroll
+        for (int dy = -HC; dy <= HC; dy++)
+#pragma unroll
+            for (int dx = -HC; dx <= HC; dx++) {
+                if (dy == 0 && dx == 0) continue;
+                const u32 bit = (u32)tile[ry + HC + dy][threadIdx.x + HC + dx] < c ? 1u : 0u;
+                if (k < 32) lo |= bit << k; else hi |= bit << (k - 32);
+                k++;
+            }
+        const size_t o = (size_t)y * W + x;
+        if constexpr (NW == 2) reinterpret_cast<u64 *>(out)[o] = (u64)lo | ((u64)hi << 32);
+        else out[o] = lo;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// cost, box sum, arg-min
+// ---------------------------------------------------------------------------
+
+struct CensusGeom {
+    int w, h, D;
+    int n, half;
+    int dlo, dc;            // this launch's shifts: dlo .. dlo + dc - 1
+    int nl, log2nl;         // lanes that split a column group's shift range (8 shifts each)
+    int cg, hg;             // column groups of 4 per workgroup, of which hg on each side are halo only
+    int tw, th;             // output columns / rows per workgroup (tw = 4 (cg - 2 hg))
+    int tiles_x, tiles_y;
+    int lw, rw;             // descriptors per ring row, left / right
+    int xs;                 // u32 per exchange row (4 cg + 4: rows of consecutive shift lanes start 4 banks apart)
+    int first, last;        // the launch's place in the shift range (keys are merged through the web map)
+    int vec_ok;             // W % 4 == 0 and 16-byte aligned maps: int4 stores
+    int pf;                 // descriptors one lane fetches per ring row
+    long long side;         // descriptors from side 0 (left) to side 1 (right) of the workspace
+};
+
+template <int K>
+__device__ __forceinline__ u32 smn_partner(u32 v)
+{
+    if (K == 0) return (u32)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xf, 0xf, false);
+    if (K == 1) return (u32)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xf, 0xf, false);
+    if (K == 2) return (u32)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x141, 0xf, 0xf, false);
+    return (u32)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x140, 0xf, 0xf, false);
+}
+
+// one ring row of descriptors for this lane: as many as the host counted (g.pf), NW dwords each
+template <int NW>
+struct SmnRow {
+    u32 v[SMN_PFMAX][NW];
+};
+
+template <int NW, bool GHOST, bool MIRROR>
+__global__ __launch_bounds__(SMN_THREADS) void k_census_wta(const u32 *__restrict__ desc, i32 *web, i32 *best,
+                                                            const CensusGeom g)
+{
+    extern __shared__ __attribute__((aligned(16))) u32 lds[];
+    const int n = g.n, half = g.half;
+    const int ringw = (g.lw + g.rw) * NW;                 // dwords per ring row
+    u32 *ring = lds;                                      // [n + 1][lw + rw] descriptors
+    u32 *X = lds + (size_t)(n + 1) * ringw;               // [4][nl][xs]: packed column sums of shifts 2k | 2k + 1
+    const int tid = threadIdx.x, T = g.cg * g.nl;
+    const int pair = blockIdx.z;
+    int tx, ty;
+    sm_xcd_tile(g.tiles_x, g.tiles_y, tx, ty);
+    const int tx0 = tx * g.tw, ty0 = ty * g.th;
+    const int cx0 = tx0 - 4 * g.hg;                       // image column (of the pass) of computed column 0
+    const int W = g.w, H = g.h;
+    const size_t npx = (size_t)W * H;
+    // MIRROR: the pass's left image is mirror(R), its right image mirror(L)
+    const u32 *dL = desc + (size_t)NW * ((MIRROR ? (size_t)g.side : 0) + (size_t)pair * npx);
+    const u32 *dR = desc + (size_t)NW * ((MIRROR ? 0 : (size_t)g.side) + (size_t)pair * npx);
+
+    // ---- this lane's share of a ring row: descriptor i < lw is left column cx0 + i, the others right column
+    // cx0 + dlo + i - lw (columns of the pass: read mirrored under MIRROR), the border applied
+    int src_col[SMN_PFMAX];
+    bool src_on[SMN_PFMAX], src_r[SMN_PFMAX];
+#pragma unroll
+    for (int q = 0; q < SMN_PFMAX; q++) {
+        const int i = tid + q * T;
+        const bool is_r = i >= g.lw;
+        int c = is_r ? cx0 + g.dlo + (i - g.lw) : cx0 + i;
+        bool on = q < g.pf && i < g.lw + g.rw;
+        if (GHOST) on = on && c >= 0 && c < W;
+        else c = smn_mod(c, W);
+        if (MIRROR) c = W - 1 - c;
+        src_on[q] = on;
+        src_r[q] = is_r;
+        src_col[q] = on ? c : 0;
+    }
+    auto fetch = [&](int e, SmnRow<NW> &v) {
+        const int y = ty0 - half + e;
+        const bool vy = !GHOST || (y >= 0 && y < H);
+        const int ys = GHOST ? (vy ? y : 0) : smn_mod(y, H);
+#pragma unroll
+        for (int q = 0; q < SMN_PFMAX; q++) {
+#pragma unroll
+            for (int k = 0; k < NW; k++) v.v[q][k] = 0;
+            if (src_on[q] && vy) {
+                const u32 *p = (src_r[q] ? dR : dL) + (size_t)NW * ((size_t)ys * W + src_col[q]);
+                if constexpr (NW == 2) {
+                    const uint2 t = *reinterpret_cast<const uint2 *>(p);
+                    v.v[q][0] = t.x;
+                    v.v[q][NW - 1] = t.y;
+                } else {
+                    v.v[q][0] = p[0];
+                }
+            }
+        }
+    };
+    auto store = [&](int e, const SmnRow<NW> &v) {
+        u32 *row = ring + (size_t)(e % (n + 1)) * ringw;
+#pragma unroll
+        for (int q = 0; q < SMN_PFMAX; q++) {
+            const int i = tid + q * T;
+            if (q < g.pf && i < g.lw + g.rw) {
+                if constexpr (NW == 2) reinterpret_cast<uint2 *>(row)[i] = make_uint2(v.v[q][0], v.v[q][NW - 1]);
+                else row[i] = v.v[q][0];
+            }
+        }
+    };
+
+    // ---- lane role: column group grp (computed columns 4 grp .. 4 grp + 3), shifts dlo + d0 .. + 7
+    const int s = tid & (g.nl - 1), grp = tid >> g.log2nl;
+    const int d0 = s * SMN_DS;
+    const int dlim = g.dc - d0;                           // shifts of this lane inside the launch's range
+    const bool out_grp = grp >= g.hg && grp < g.cg - g.hg;
+    bool cin[4];                                          // ghost: computed columns outside the image sum to 0
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int c = cx0 + 4 * grp + j;
+        cin[j] = !GHOST || (c >= 0 && c < W);
+    }
+
+    u32 P[4][SMN_DS], Q[4][SMN_DS];                       // column sums: P of the rows added, Q of the rows removed
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int dd = 0; dd < SMN_DS; dd++) { P[j][dd] = 0; Q[j][dd] = 0; }
+
+    // Hamming costs of ring row e, added into acc: left columns 4 grp + j against right columns 4 grp + j + d0 + dd
+    auto slide = [&](int e, u32 (&acc)[4][SMN_DS]) {
+        const u32 *row = ring + (size_t)(e % (n + 1)) * ringw;
+        const uint4 *rl = reinterpret_cast<const uint4 *>(row + (size_t)NW * 4 * grp);
+        const uint4 *rr = reinterpret_cast<const uint4 *>(row + (size_t)NW * (g.lw + 4 * grp + d0));
+        u32 l[4][NW], r[12][NW];
+        if constexpr (NW == 2) {
+#pragma unroll
+            for (int m = 0; m < 2; m++) {
+                const uint4 t = rl[m];
+                l[2 * m][0] = t.x; l[2 * m][NW - 1] = t.y; l[2 * m + 1][0] = t.z; l[2 * m + 1][NW - 1] = t.w;
+            }
+#pragma unroll
+            for (int m = 0; m < 6; m++) {
+                const uint4 t = rr[m];
+                r[2 * m][0] = t.x; r[2 * m][NW - 1] = t.y; r[2 * m + 1][0] = t.z; r[2 * m + 1][NW - 1] = t.w;
+            }
+        } else {
+            const uint4 t = rl[0];
+            l[0][0] = t.x; l[1][0] = t.y; l[2][0] = t.z; l[3][0] = t.w;
+#pragma unroll
+            for (int m = 0; m < 3; m++) {
+                const uint4 u = rr[m];
+                r[4 * m][0] = u.x; r[4 * m + 1][0] = u.y; r[4 * m + 2][0] = u.z; r[4 * m + 3][0] = u.w;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int dd = 0; dd < SMN_DS; dd++) {
+                u32 a = acc[j][dd];
+#pragma unroll
+                for (int k = 0; k < NW; k++) a += (u32)__builtin_popcount(l[j][k] ^ r[j + dd][k]);   // v_bcnt_u32_b32
+                acc[j][dd] = a;
+            }
+    };
+
+    // ---- the march: step e brings ring row e in (rows ty0 - half + e), and row e - n leaves; from e = n - 1 on,
+    // output row ty0 + e - (n - 1) is complete.  Row e + 1 is fetched at the top of step e and stored after the first
+    // barrier (its ring slot held row e - n, which every lane has read by then); the second barrier publishes it and
+    // the exchange rows.
+    const int rows_out = min(g.th, H - ty0);
+    const int steps = rows_out + n - 1;
+    {
+        SmnRow<NW> v0;
+        fetch(0, v0);
+        store(0, v0);
+    }
+    __syncthreads();
+    for (int e = 0; e < steps; e++) {
+        SmnRow<NW> nx;
+        if (e + 1 < steps) fetch(e + 1, nx);
+        const int y_new = ty0 - half + e;
+        if (!GHOST || (y_new >= 0 && y_new < H)) slide(e, P);
+        if (e >= n) {
+            const int y_old = y_new - n;
+            if (!GHOST || (y_old >= 0 && y_old < H)) slide(e - n, Q);
+        }
+        const bool emit = e >= n - 1;
+        __syncthreads();
+        if (emit) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                u32 w4[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const u32 a = P[j][2 * k] - Q[j][2 * k], b = P[j][2 * k + 1] - Q[j][2 * k + 1];
+                    w4[j] = cin[j] ? (a | (b << 16)) : 0u;
+                }
+                *reinterpret_cast<uint4 *>(X + (size_t)(k * g.nl + s) * g.xs + 4 * grp) =
+                    make_uint4(w4[0], w4[1], w4[2], w4[3]);
+            }
+        }
+        if (e + 1 < steps) store(e + 1, nx);
+        __syncthreads();
+        if (!emit) continue;
+
+        // ---- horizontal window sums (packed u16: shifts 2k | 2k + 1), first-wins keys A << 16 | d, merge over the nl
+        // lanes.  A shift outside the launch's range gets 0x8000 added to its sum (A <= 30000: the field cannot wrap,
+        // and the key loses to every real one).
+        u32 key[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+        if (out_grp) {
+            for (int k = 0; k < 4; k++) {
+                const u32 *xr = X + (size_t)(k * g.nl + s) * g.xs + 4 * (grp - g.hg);
+                // column 4 grp + j + t of the tile is xr[4 hg + j + t], t = -half .. half
+                const int c0 = 4 * g.hg;
+                const u16x2 inv = {(unsigned short)(2 * k < dlim ? 0 : 0x8000),
+                                   (unsigned short)(2 * k + 1 < dlim ? 0 : 0x8000)};
+                u16x2 S = inv;
+                for (int t = -half; t <= half; t++) S += __builtin_bit_cast(u16x2, xr[c0 + t]);
+                const u32 da = (u32)(g.dlo + d0 + 2 * k), db = da + 1;
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    if (j > 0) {
+                        S += __builtin_bit_cast(u16x2, xr[c0 + j + half]);
+                        S -= __builtin_bit_cast(u16x2, xr[c0 + j - 1 - half]);
+                    }
+                    const u32 v = __builtin_bit_cast(u32, S);
+                    key[j] = min(key[j], min((v << 16) | da, (v & 0xffff0000u) | db));
+                }
+            }
+        }
+#define SMN_MERGE(K)                                                                       \
+        if (g.nl > (1 << K)) {                                                             \
+            _Pragma("unroll") for (int j = 0; j < 4; j++) key[j] = min(key[j], smn_partner<K>(key[j])); \
+        }
+        SMN_MERGE(0) SMN_MERGE(1) SMN_MERGE(2) SMN_MERGE(3)
+#undef SMN_MERGE
+        if (!out_grp || s != 0) continue;
+        const int y = ty0 + e - (n - 1);
+        const int x = cx0 + 4 * grp;                      // first output column of the lane (pass coordinates)
+        const size_t orow = ((size_t)pair * H + y) * W;
+        if (g.vec_ok && x + 3 < W) {
+            // natural columns x .. x + 3, or under MIRROR W - 4 - x .. W - 1 - x (reversed); both 16-byte aligned
+            const size_t o = orow + (MIRROR ? (size_t)(W - 4 - x) : (size_t)x);
+            u32 kk[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) kk[j] = key[MIRROR ? 3 - j : j];
+            if (!g.first) {
+                const int4 p = *reinterpret_cast<const int4 *>(web + o);
+                kk[0] = min(kk[0], (u32)p.x); kk[1] = min(kk[1], (u32)p.y);
+                kk[2] = min(kk[2], (u32)p.z); kk[3] = min(kk[3], (u32)p.w);
+            }
+            if (g.last) {
+                *reinterpret_cast<int4 *>(web + o) = make_int4((i32)(kk[0] & 0xffff) + 1, (i32)(kk[1] & 0xffff) + 1,
+                                                               (i32)(kk[2] & 0xffff) + 1, (i32)(kk[3] & 0xffff) + 1);
+                if (best)
+                    *reinterpret_cast<int4 *>(best + o) =
+                        make_int4((i32)(kk[0] >> 16), (i32)(kk[1] >> 16), (i32)(kk[2] >> 16), (i32)(kk[3] >> 16));
+            } else {
+                *reinterpret_cast<int4 *>(web + o) = make_int4((i32)kk[0], (i32)kk[1], (i32)kk[2], (i32)kk[3]);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (x + j >= W) break;
+                const size_t o = orow + (MIRROR ? (size_t)(W - 1 - x - j) : (size_t)(x + j));
+                u32 kj = key[j];
+                if (!g.first) kj = min(kj, (u32)web[o]);
+                if (g.last) {
+                    web[o] = (i32)(kj & 0xffff) + 1;
+                    if (best) best[o] = (i32)(kj >> 16);
+                } else {
+                    web[o] = (i32)kj;
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// subpixel refinement
+// ---------------------------------------------------------------------------
+
+struct CensusRefineGeom {
+    int w, h, D, n, half;
+    int want_costs;
+    long long side;
+};
+
+__device__ __forceinline__ int smn_floordiv(int num, int den)      // den > 0
+{
+    const int q = num / den;
+    return (num % den != 0 && num < 0) ? q - 1 : q;
+}
+
+template <int NW>
+__device__ __forceinline__ u32 smn_load(const u32 *img, size_t i)
+{
+    return img[NW * i];
+}
+
+template <int NW>
+__device__ __forceinline__ u32 smn_load_hi(const u32 *img, size_t i)
+{
+    return NW == 2 ? img[NW * i + 1] : 0u;
+}
+
+// One lane per pixel: s = web(x, y); for s in 1..D the window costs C(s-2), C(s-1), C(s) summed tap by tap (each tap
+// one left descriptor and one right one: the three right descriptors of a tap slide along the window row).
+template <int NW, bool GHOST>
+__global__ __launch_bounds__(256) void k_census_refine(const u32 *__restrict__ desc, const i32 *__restrict__ web,
+                                                       int16_t *__restrict__ sub, i32 *__restrict__ costs,
+                                                       const CensusRefineGeom g)
+{
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    const int pair = blockIdx.z;
+    if (x >= g.w || y >= g.h) return;
+    const int W = g.w, H = g.h;
+    const size_t npx = (size_t)W * H;
+    const u32 *dL = desc + (size_t)NW * ((size_t)pair * npx);
+    const u32 *dR = desc + (size_t)NW * ((size_t)g.side + (size_t)pair * npx);
+    const size_t o = (size_t)pair * npx + (size_t)y * W + x;
+    const int s = web[o];
+    i32 c[3] = {-1, -1, -1};
+    int16_t out = 0;
+    if (s >= 1 && s <= g.D) {
+        u32 acc[3] = {0, 0, 0};
+        for (int ty = -g.half; ty <= g.half; ty++) {
+            int yy = y + ty;
+            if (GHOST) { if (yy < 0 || yy >= H) continue; }
+            else yy = smn_mod(yy, H);
+            const size_t rowo = (size_t)yy * W;
+            // right columns xx + s - 2 + i of the taps xx = x - half ..: r[i] slides one column per tap
+            auto rload = [&](int xr, u32 &lo, u32 &hi) {
+                lo = hi = 0;
+                if (GHOST) { if (xr < 0 || xr >= W) return; }
+                else xr = smn_mod(xr, W);
+                lo = smn_load<NW>(dR, rowo + xr);
+                hi = smn_load_hi<NW>(dR, rowo + xr);
+            };
+            const int xs0 = x - g.half;
+            u32 r0l, r0h, r1l, r1h, r2l, r2h;
+            rload(xs0 + s - 2, r0l, r0h);
+            rload(xs0 + s - 1, r1l, r1h);
+            for (int tx = 0; tx < g.n; tx++) {
+                rload(xs0 + tx + s, r2l, r2h);
+                int xx = xs0 + tx;
+                bool on = true;
+                if (GHOST) on = xx >= 0 && xx < W;
+                else xx = smn_mod(xx, W);
+                if (on) {
+                    const u32 ll = smn_load<NW>(dL, rowo + xx), lh = smn_load_hi<NW>(dL, rowo + xx);
+                    acc[0] += (u32)__builtin_popcount(ll ^ r0l) + (u32)__builtin_popcount(lh ^ r0h);
+                    acc[1] += (u32)__builtin_popcount(ll ^ r1l) + (u32)__builtin_popcount(lh ^ r1h);
+                    acc[2] += (u32)__builtin_popcount(ll ^ r2l) + (u32)__builtin_popcount(lh ^ r2h);
+                }
+                r0l = r1l; r0h = r1h; r1l = r2l; r1h = r2h;
+            }
+        }
+        c[1] = (i32)acc[1];
+        if (s >= 2) c[0] = (i32)acc[0];
+        if (s <= g.D - 1) c[2] = (i32)acc[2];
+        int q = 0;
+        if (s >= 2 && s <= g.D - 1) {
+            const int a = c[0] - c[1], b = c[2] - c[1];
+            const int den = max(a, b);
+            if (den > 0) q = min(8, max(-8, smn_floordiv(16 * (a - b) + den, 2 * den)));
+        }
+        out = (int16_t)(16 * s + q);
+    }
+    sub[o] = out;
+    if (g.want_costs) {
+        const size_t oc = (size_t)pair * 3 * npx + (size_t)y * W + x;
+        costs[oc] = c[0];
+        costs[oc + npx] = c[1];
+        costs[oc + 2 * npx] = c[2];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------
+
+static size_t census_desc_bytes(const sm_plan *plan)
+{
+    return (size_t)2 * plan->max_pairs * plan->width * plan->height * sizeof(u64);
+}
+
+size_t sm_census_workspace_bytes(const sm_plan *plan)
+{
+    return plan->d_census ? census_desc_bytes(plan) : 0;
+}
+
+void sm_census_free(sm_plan *plan)
+{
+    if (plan->d_census) (void)hipFree(plan->d_census);
+    plan->d_census = nullptr;
+}
+
+// the descriptors of both images of max_pairs pairs, and the mirrored-order map the consistency checks share (if the
+// plan has none yet); on failure neither is kept
+static int reserve_census(sm_plan *plan, const char *me)
+{
+    if (plan->d_census && plan->d_web_lr) return SM_OK;
+    if (!plan->d_census) {
+        void *b = nullptr;
+        const hipError_t e = hipMalloc(&b, census_desc_bytes(plan));
+        if (e != hipSuccess)
+            return sm_fail(e == hipErrorOutOfMemory ? SM_ERR_NOMEM : SM_ERR_HIP, "%s: %zu bytes for the census "
+                           "descriptors: %s", me, census_desc_bytes(plan), hipGetErrorString(e));
+        const int rc = sm_lr_reserve_map(plan, me);
+        if (rc) {
+            (void)hipFree(b);
+            return rc;
+        }
+        plan->d_census = (u32 *)b;
+        return SM_OK;
+    }
+    return sm_lr_reserve_map(plan, me);
+}
+
+extern "C" int sm_plan_reserve_census(sm_plan *plan)
+{
+    if (!plan) return sm_fail(SM_ERR_ARG, "sm_plan_reserve_census: plan is NULL");
+    SM_TRY(sm_use_device(plan->device));
+    return reserve_census(plan, "sm_plan_reserve_census");
+}
+
+static int need_census(sm_plan *plan, hipStream_t st, const char *me)
+{
+    if (plan->d_census && plan->d_web_lr) return SM_OK;
+    if (sm_stream_capturing(st))
+        return sm_fail(SM_ERR_ARG, "%s: the census workspace is not allocated and the stream is capturing (an allocation "
+                       "cannot be captured): call sm_plan_reserve_census(plan) first", me);
+    return reserve_census(plan, me);
+}
+
+// what every census entry checks besides its pointers (before any device call)
+static int census_args(const sm_plan *plan, int census_width, int pairs, bool window, const char *me)
+{
+    if (census_width != 3 && census_width != 5 && census_width != 7)
+        return sm_fail(SM_ERR_ARG, "%s: census_width %d is not 3, 5 or 7", me, census_width);
+    if (!plan) return sm_fail(SM_ERR_ARG, "%s: plan is NULL", me);
+    if (pairs < 1 || pairs > plan->max_pairs)
+        return sm_fail(SM_ERR_ARG, "%s: pairs %d outside 1..%d (max_pairs of the plan)", me, pairs, plan->max_pairs);
+    const int n = 2 * (plan->square_width / 2) + 1;
+    if (window && (n > 25 || plan->num_shifts > 512))
+        return sm_fail(SM_ERR_ARG, "%s: built for windows up to 25x25 and at most 512 shifts (got %dx%d, %d)", me, n, n,
+                       plan->num_shifts);
+    return SM_OK;
+}
+
+static bool overlap(const void *a, const void *b, size_t a_bytes, size_t b_bytes = 0)
+{
+    return (uintptr_t)a < (uintptr_t)b + (b_bytes ? b_bytes : a_bytes) && (uintptr_t)b < (uintptr_t)a + a_bytes;
+}
+
+template <int CW, int NW>
+static const void *transform_ptr(bool ghost)
+{
+    return ghost ? (const void *)k_census_transform<CW, NW, true> : (const void *)k_census_transform<CW, NW, false>;
+}
+
+// descriptors of images_a images at src_a (to dst) and images_b at src_b (to dst + dst_b descriptors), NW dwords each
+static int transform_launch(const sm_plan *plan, int cw, int nw, const uint8_t *src_a, int images_a,
+                            const uint8_t *src_b, int images_b, u32 *dst, long long dst_b, hipStream_t st)
+{
+    const bool ghost = plan->border == SM_GHOST;
+    const void *fn;
+    if (nw == 2) fn = cw == 3 ? transform_ptr<3, 2>(ghost) : cw == 5 ? transform_ptr<5, 2>(ghost) : transform_ptr<7, 2>(ghost);
+    else fn = cw == 3 ? transform_ptr<3, 1>(ghost) : transform_ptr<5, 1>(ghost);
+    int W = plan->width, H = plan->height;
+    if (!src_b) src_b = src_a;
+    void *args[] = {(void *)&src_a, (void *)&src_b, (void *)&images_a, (void *)&dst, (void *)&dst_b, (void *)&W,
+                    (void *)&H};
+    const dim3 grid((W + SMN_TX - 1) / SMN_TX, (H + SMN_TR - 1) / SMN_TR, images_a + images_b), block(SMN_TX, 4);
+    const hipError_t e = hipLaunchKernel(fn, grid, block, args, 0, st);
+    if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_census_transform failed: %s", hipGetErrorString(e));
+    return SM_OK;
+}
+
+// both images of `pairs` pairs into the workspace: 4-byte descriptors for c <= 5, 8-byte for c = 7
+static int census_descriptors(sm_plan *plan, int cw, const uint8_t *left, const uint8_t *right, int pairs,
+                              hipStream_t st)
+{
+    const long long side = (long long)plan->max_pairs * plan->width * plan->height;
+    return transform_launch(plan, cw, cw == 7 ? 2 : 1, left, pairs, right, pairs, plan->d_census, side, st);
+}
+
+template <int NW>
+static const void *wta_ptr(bool ghost, bool mirror)
+{
+    return ghost ? (mirror ? (const void *)k_census_wta<NW, true, true> : (const void *)k_census_wta<NW, true, false>)
+                 : (mirror ? (const void *)k_census_wta<NW, false, true> : (const void *)k_census_wta<NW, false, false>);
+}
+
+// the arg-min over the plan's shifts from the workspace's descriptors, in launches of at most SMN_DCHUNK shifts
+static int wta_launch(const sm_plan *plan, int cw, bool mirror, int pairs, i32 *d_web, i32 *d_best, hipStream_t st)
+{
+    const int nw = cw == 7 ? 2 : 1;
+    CensusGeom g;
+    g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts;
+    g.half = plan->square_width / 2; g.n = 2 * g.half + 1;
+    g.hg = (g.half + 3) / 4;
+    g.side = (long long)plan->max_pairs * g.w * g.h;
+    g.vec_ok = g.w % 4 == 0 && (((uintptr_t)d_web | (uintptr_t)d_best) & 15) == 0;
+    const void *fn = nw == 2 ? wta_ptr<2>(plan->border == SM_GHOST, mirror) : wta_ptr<1>(plan->border == SM_GHOST, mirror);
+    for (int dlo = 0; dlo < g.D; dlo += SMN_DCHUNK) {
+        g.dlo = dlo;
+        g.dc = min(SMN_DCHUNK, g.D - dlo);
+        g.first = dlo == 0;
+        g.last = dlo + g.dc >= g.D;
+        g.nl = 1; g.log2nl = 0;
+        while (g.nl * SMN_DS < g.dc) { g.nl <<= 1; g.log2nl++; }
+        // column groups: up to 64 (256 columns) and 512 threads, fewer while the LDS request exceeds 64 KiB; at least one
+        // output group between the halo groups
+        g.cg = min(64, SMN_THREADS / g.nl);
+        size_t lds;
+        for (;;) {
+            g.lw = 4 * g.cg;
+            g.rw = 4 * g.cg + SMN_DS * g.nl;
+            g.xs = 4 * g.cg + 4;
+            lds = 4 * ((size_t)(g.n + 1) * (g.lw + g.rw) * nw + (size_t)4 * g.nl * g.xs);
+            if (lds <= 64 * 1024 || g.cg <= 2 * g.hg + 1) break;
+            g.cg = max(2 * g.hg + 1, g.cg / 2);
+        }
+        if (g.cg <= 2 * g.hg) g.cg = 2 * g.hg + 1;
+        const int T = g.cg * g.nl;
+        g.pf = (g.lw + g.rw + T - 1) / T;
+        if (g.pf > SMN_PFMAX || lds > 64 * 1024)
+            return sm_fail(SM_ERR_HIP, "census: internal tiling error (pf %d, %zu bytes of LDS)", g.pf, lds);
+        g.tw = 4 * (g.cg - 2 * g.hg);
+        g.tiles_x = (g.w + g.tw - 1) / g.tw;
+        int th = 64;
+        while (th > 8 && (long long)g.tiles_x * ((g.h + th - 1) / th) * pairs < 1024) th >>= 1;
+        g.th = min(th, g.h);
+        g.tiles_y = (g.h + g.th - 1) / g.th;
+        void *args[] = {(void *)&plan->d_census, (void *)&d_web, (void *)&d_best, (void *)&g};
+        const hipError_t e = hipLaunchKernel(fn, dim3(g.tiles_x, g.tiles_y, pairs), dim3(T), args, lds, st);
+        if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_census_wta failed: %s", hipGetErrorString(e));
+    }
+    return SM_OK;
+}
+
+extern "C" int sm_census_transform(sm_plan *plan, const uint8_t *d_gray, int census_width, int images, uint64_t *d_desc,
+                                   void *stream)
+{
+    const char *me = "sm_census_transform";
+    if (!d_gray || !d_desc) return sm_fail(SM_ERR_ARG, "%s: NULL argument", me);
+    if (census_width != 3 && census_width != 5 && census_width != 7)
+        return sm_fail(SM_ERR_ARG, "%s: census_width %d is not 3, 5 or 7", me, census_width);
+    if (!plan) return sm_fail(SM_ERR_ARG, "%s: plan is NULL", me);
+    if (images < 1 || images > 2 * plan->max_pairs)
+        return sm_fail(SM_ERR_ARG, "%s: images %d outside 1..%d (2 * max_pairs of the plan)", me, images,
+                       2 * plan->max_pairs);
+    SM_TRY(sm_use_device(plan->device));
+    return transform_launch(plan, census_width, 2, d_gray, images, nullptr, 0, (u32 *)d_desc, 0, (hipStream_t)stream);
+}
+
+extern "C" int sm_census_wta(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+                             int pairs, int32_t *d_web, int32_t *d_best, void *stream)
+{
+    const char *me = "sm_census_wta";
+    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
+    if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
+    SM_TRY(census_args(plan, census_width, pairs, true, me));
+    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
+    if (d_best && overlap(d_web, d_best, map)) return sm_fail(SM_ERR_ARG, "%s: d_web and d_best overlap", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    SM_TRY(need_census(plan, st, me));
+    SM_TRY(census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
+    return wta_launch(plan, census_width, false, pairs, d_web, d_best, st);
+}
+
+extern "C" int sm_census_wta_right(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right,
+                                   int census_width, int pairs, int32_t *d_web_right, int32_t *d_best_right, void *stream)
+{
+    const char *me = "sm_census_wta_right";
+    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
+    if (!d_web_right) return sm_fail(SM_ERR_ARG, "%s: d_web_right is NULL", me);
+    SM_TRY(census_args(plan, census_width, pairs, true, me));
+    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
+    if (d_best_right && overlap(d_web_right, d_best_right, map))
+        return sm_fail(SM_ERR_ARG, "%s: d_web_right and d_best_right overlap", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    SM_TRY(need_census(plan, st, me));
+    SM_TRY(census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
+    return wta_launch(plan, census_width, true, pairs, d_web_right, d_best_right, st);
+}
+
+extern "C" int sm_census_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+                            int pairs, int max_diff, int32_t *d_web, int32_t *d_best, int32_t *d_web_right,
+                            int32_t *d_rejected, void *stream)
+{
+    const char *me = "sm_census_lr";
+    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
+    if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
+    if (max_diff < 0) return sm_fail(SM_ERR_ARG, "%s: max_diff %d is negative", me, max_diff);
+    SM_TRY(census_args(plan, census_width, pairs, true, me));
+    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
+    if ((d_best && overlap(d_best, d_web, map)) || (d_web_right && overlap(d_web_right, d_web, map)) ||
+        (d_best && d_web_right && overlap(d_best, d_web_right, map)))
+        return sm_fail(SM_ERR_ARG, "%s: result maps overlap", me);
+    const size_t counts = (size_t)pairs * sizeof(i32);
+    if (d_rejected && (overlap(d_rejected, d_web, counts, map) || (d_best && overlap(d_rejected, d_best, counts, map)) ||
+                       (d_web_right && overlap(d_rejected, d_web_right, counts, map))))
+        return sm_fail(SM_ERR_ARG, "%s: d_rejected overlaps a map", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    SM_TRY(need_census(plan, st, me));
+    // the descriptors once for both directions; the right-reference map in natural order (the caller's, or the
+    // plan's mirrored-order map used as scratch), then the check, which gathers from it
+    i32 *right = d_web_right ? d_web_right : plan->d_web_lr;
+    SM_TRY(census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
+    SM_TRY(wta_launch(plan, census_width, false, pairs, d_web, d_best, st));
+    SM_TRY(wta_launch(plan, census_width, true, pairs, right, nullptr, st));
+    return sm_lr_check_natural(plan, d_web, right, d_web, d_rejected, max_diff, pairs, st);
+}
+
+extern "C" int sm_census_refine(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right,
+                                int census_width, int pairs, const int32_t *d_web, int16_t *d_sub, int32_t *d_costs,
+                                void *stream)
+{
+    const char *me = "sm_census_refine";
+    if (!d_gray_left || !d_gray_right || !d_web || !d_sub) return sm_fail(SM_ERR_ARG, "%s: NULL argument", me);
+    SM_TRY(census_args(plan, census_width, pairs, true, me));
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    SM_TRY(need_census(plan, st, me));
+    SM_TRY(census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
+    CensusRefineGeom g;
+    g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts;
+    g.half = plan->square_width / 2; g.n = 2 * g.half + 1;
+    g.want_costs = d_costs != nullptr;
+    g.side = (long long)plan->max_pairs * g.w * g.h;
+    const bool ghost = plan->border == SM_GHOST;
+    const void *fn = census_width == 7 ? (ghost ? (const void *)k_census_refine<2, true> : (const void *)k_census_refine<2, false>)
+                                       : (ghost ? (const void *)k_census_refine<1, true> : (const void *)k_census_refine<1, false>);
+    void *args[] = {(void *)&plan->d_census, (void *)&d_web, (void *)&d_sub, (void *)&d_costs, (void *)&g};
+    const hipError_t e = hipLaunchKernel(fn, dim3((g.w + 63) / 64, (g.h + 3) / 4, pairs), dim3(64, 4), args, 0, st);
+    if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_census_refine failed: %s", hipGetErrorString(e));
+    return SM_OK;
+}

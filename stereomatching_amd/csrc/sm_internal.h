@@ -113,6 +113,9 @@ struct sm_plan {
                          // each of max_pairs * W * H bytes starting 256-byte aligned (sm_plan_reserve_cost_lr)
     int cost_lds_raised; // sm_cost_wta: the LDS limit of this plan's four-wave SAD kernel is raised (on `device`)
     char describe[512];
+    // census cost mode (sm_census.hip): NOT allocated with the plan, but by sm_plan_reserve_census or the first call
+    // that needs it; part of the workspace from then on (with d_web_lr, which it allocates if the plan has none yet)
+    u32 *d_census;       // descriptors [side: 0 = left, 1 = right][max_pairs][H][W], 8 bytes each (4 for c <= 5)
 };
 
 // XCD-aware tile order (device side).  Workgroups are dealt round-robin to the 8
@@ -161,6 +164,13 @@ int sm_use_device(int device);                    // hipSetDevice, failure as SM
 bool sm_stream_capturing(hipStream_t st);         // is `st` recording into a graph?
 size_t sm_lr_workspace_bytes(const sm_plan *plan);    // sm_lr.hip: 0 until sm_plan_reserve_lr / _cost_lr
 void sm_lr_free(sm_plan *plan);                       // sm_lr.hip: sm_plan_destroy
+// sm_lr.hip, for the census mode: the mirrored-order map alone (if the plan has none yet), and k_lr_check on a
+// right-reference map in natural order (the rejection counts zeroed by a kernel first)
+int sm_lr_reserve_map(sm_plan *plan, const char *me);
+int sm_lr_check_natural(const sm_plan *plan, const i32 *web, const i32 *right, i32 *out, i32 *rejected, int max_diff,
+                        int pairs, hipStream_t st);
+size_t sm_census_workspace_bytes(const sm_plan *plan);   // sm_census.hip: 0 until sm_plan_reserve_census
+void sm_census_free(sm_plan *plan);                      // sm_census.hip: sm_plan_destroy
 
 // sm_match_bs.hip (bit-sliced kernel; nullptr if not built for this window)
 const void *sm_bs_kernel_ptr(int n, int ds, bool fulld, bool ghost, bool cap2, bool duo = false);

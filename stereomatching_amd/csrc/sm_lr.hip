@@ -564,3 +564,25 @@ extern "C" int sm_cost_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8
     SM_TRY(sm_cost_wta(plan, ml, mr, cost, pairs, plan->d_web_lr, nullptr, stream));
     return lr_check_launch(plan, true, d_web, plan->d_web_lr, d_web, d_web_right, d_rejected, max_diff, pairs, st);
 }
+
+// ---------------------------------------------------------------------------
+// for the census mode (sm_census.hip)
+// ---------------------------------------------------------------------------
+
+int sm_lr_reserve_map(sm_plan *plan, const char *me)
+{
+    if (plan->d_web_lr) return SM_OK;
+    void *map = nullptr;
+    const hipError_t e = hipMalloc(&map, lr_map_bytes(plan));
+    if (e != hipSuccess)
+        return sm_fail(e == hipErrorOutOfMemory ? SM_ERR_NOMEM : SM_ERR_HIP, "%s: %zu bytes for the map of the "
+                       "consistency check: %s", me, lr_map_bytes(plan), hipGetErrorString(e));
+    plan->d_web_lr = (i32 *)map;
+    return SM_OK;
+}
+
+int sm_lr_check_natural(const sm_plan *plan, const i32 *web, const i32 *right, i32 *out, i32 *rejected, int max_diff,
+                        int pairs, hipStream_t st)
+{
+    return lr_check_launch(plan, false, web, right, out, nullptr, rejected, max_diff, pairs, st);
+}

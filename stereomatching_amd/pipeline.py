@@ -379,6 +379,82 @@ class StereoPlan:
                                  _ptr(out), _ptr(costs), self._stream()))
         return out, costs
 
+    # ---- census cost mode ----------------------------------------------------
+    def reserve_census(self):
+        """The census mode's workspace (the descriptors of max_pairs pairs, and the mirrored-order map if the plan has
+        none yet), allocated now: keeps the allocation out of timed paths and out of stream captures."""
+        check(lib.sm_plan_reserve_census(self._h))
+
+    def _census_pair(self, left, right):
+        left = self._images(left, torch.uint8, "left")
+        right = self._images(right, torch.uint8, "right")
+        if right.shape[0] != left.shape[0]:
+            raise ValueError(f"right: {right.shape[0]} images for {left.shape[0]} pairs")
+        return left, right, left.shape[0]
+
+    def census_transform(self, images, census=7, out=None):
+        """Census descriptors of uint8 gray images (sm_census_transform) -> int64 tensor of their bits, same shape:
+        bit k = the k-th neighbour of the census x census window (row-major, centre skipped) is darker than the pixel."""
+        images = self._images(images, torch.uint8, "images")
+        n = images.shape[0]
+        if out is None:
+            out = self._new(n, torch.int64)
+        else:
+            out = self._images(out, torch.int64, "out")
+            if out.shape[0] < n:
+                raise ValueError(f"out: room for {out.shape[0]} images, {n} given")
+        check(lib.sm_census_transform(self._h, _ptr(images), int(census), n, _ptr(out), self._stream()))
+        return out
+
+    def census_wta(self, left, right, census=7, want_best=True, web=None, best=None):
+        """Census cost mode (parity unpinned) -> (web, best): Hamming cost of census descriptors, n x n box sum,
+        arg-min over the shifts, first shift wins."""
+        left, right, pairs = self._census_pair(left, right)
+        web = self._out(web, pairs, "web")
+        best = self._out(best, pairs, "best") if want_best else None
+        check(lib.sm_census_wta(self._h, _ptr(left), _ptr(right), int(census), pairs, _ptr(web), _ptr(best),
+                                self._stream()))
+        return web, best
+
+    def census_wta_right(self, left, right, census=7, want_best=True, web_right=None, best_right=None):
+        """The census mode's right-reference map (sm_census_wta_right) -> (web_right, best_right): web_right(u, y) = s'
+        means right pixel u matched left pixel u - (s' - 1)."""
+        left, right, pairs = self._census_pair(left, right)
+        web_right = self._out(web_right, pairs, "web_right")
+        best_right = self._out(best_right, pairs, "best_right") if want_best else None
+        check(lib.sm_census_wta_right(self._h, _ptr(left), _ptr(right), int(census), pairs, _ptr(web_right),
+                                      _ptr(best_right), self._stream()))
+        return web_right, best_right
+
+    def census_lr(self, left, right, census=7, max_diff=0, want_right=False, want_best=False, web=None,
+                  web_right=None, best=None) -> LRResult:
+        """Left and right census arg-min and the check in one call (sm_census_lr) -> LRResult(web, rejected, web_right,
+        best); web is the checked map (0 = rejected), best the left window costs as census_wta gives them."""
+        left, right, pairs = self._census_pair(left, right)
+        web = self._out(web, pairs, "web")
+        web_right = self._out(web_right, pairs, "web_right") if want_right else None
+        best = self._out(best, pairs, "best") if want_best else None
+        rejected = torch.empty(pairs, dtype=torch.int32, device=self._dev)
+        check(lib.sm_census_lr(self._h, _ptr(left), _ptr(right), int(census), pairs, int(max_diff), _ptr(web),
+                               _ptr(best), _ptr(web_right), _ptr(rejected), self._stream()))
+        return LRResult(web, rejected, web_right, best)
+
+    def census_refine(self, left, right, web, census=7, want_costs=False, out=None):
+        """Subpixel refinement of a census map (sm_census_refine) -> (sub, costs): sub int16 in 1/16 of a shift by the
+        equiangular fit over C(s-2), C(s-1), C(s) (0 where web is outside 1..D), costs (pairs, 3, H, W) int32 with -1
+        where a shift has none, if wanted."""
+        left, right, pairs = self._census_pair(left, right)
+        web = self._images(web, torch.int32, "web")
+        if web.shape[0] != pairs:
+            raise ValueError(f"web: {web.shape[0]} maps for {pairs} pairs")
+        out = self._out(out, pairs, "out", torch.int16)
+        costs = None
+        if want_costs:
+            costs = torch.empty((pairs, 3, self.height, self.width), dtype=torch.int32, device=self._dev)
+        check(lib.sm_census_refine(self._h, _ptr(left), _ptr(right), int(census), pairs, _ptr(web), _ptr(out),
+                                   _ptr(costs), self._stream()))
+        return out, costs
+
     def debug_planes(self, pair: int, shift: int):
         """matches-i, score_all-i, scores-i of the reference's debug build."""
         m = torch.empty((self.height, self.width), dtype=torch.uint8, device=self._dev)
