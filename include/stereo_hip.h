@@ -496,6 +496,45 @@ int sm_census_refine(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d
 /* adds: allocates the census workspace now; idempotent */
 int sm_plan_reserve_census(sm_plan *plan);
 
+/* ---- semi-global matching over the census data term: PARITY UNPINNED ------ *
+ * New work (no reference counterpart).  The census window cost aggregated along 4 or 8 image lines
+ * instead of arg-minned directly, so depth follows the image across flat regions and stops at object boundaries.
+ * Arguments: census_width c in {3, 5, 7}, penalties 0 <= p1 <= p2 <= 32767, paths in {4, 8}.  Definition:
+ *   A(p, d)   = sm_census_wta's window cost (the plan's n x n box sum and border rules), d = 0 .. D - 1;
+ *   directions r: (1,0) (-1,0) (0,1) (0,-1), and for 8 paths also (1,1) (-1,1) (1,-1) (-1,-1);
+ *   L_r(p, d) = A(p, d) if q = p - r lies outside the image (paths never wrap, in either border mode), else
+ *               A(p, d) + min(L_r(q, d), L_r(q, d-1) + p1, L_r(q, d+1) + p1, m_q + p2) - m_q, m_q = min_k L_r(q, k),
+ *               terms with d-1 or d+1 outside 0 .. D - 1 dropped;  A <= L_r <= A + p2 (a u16 at every window size);
+ *   S(p, d)   = sum over r of L_r(p, d); best = min_d S, web = 1 + the FIRST d reaching it;
+ *   sub       = 16 s at s = web = 1 or D, else a = S(s-2) - S(s-1), b = S(s) - S(s-1), den = a + b,
+ *               q = floor((16 (a - b) + den) / (2 den)) (0 if den <= 0), clamped to -8 .. 8, sub = 16 s + q
+ *               (int16, 1/16 of a shift; sm_cost_refine's SSD rule on S);
+ *   right reference: (best_right, web_right) = mirror(sgm(mirror(R), mirror(L))); the check is sm_lr_check's.
+ * With p1 = p2 = 0, web is sm_census_wta's and best = paths * its best.  Windows up to 25 x 25 and at most 256
+ * shifts.  Arguments are checked before any device call; a refusal names the function.  Workspace: the census
+ * workspace (sm_plan_reserve_census: 16 * max_pairs * W * H bytes of descriptors, and the mirrored-order map,
+ * 4 * max_pairs * W * H bytes, if the plan has none yet) and the volumes of ONE pair, 6 * W * H * Dp bytes with Dp =
+ * the least of 64, 128 and 256 that holds num_shifts (12.7 GB at 3840 x 2160 and 256 shifts); a call of `pairs` pairs works
+ * through them in turn, in stream order.  Allocated by sm_plan_reserve_sgm or, without it, by the first call that
+ * needs it (a hipMalloc, which synchronises the device; SM_ERR_NOMEM if the device has not the room), counted in
+ * sm_plan_workspace_bytes from then on, freed by sm_plan_destroy.  A plan that never calls these allocates none of
+ * it.  All calls run in `stream` order and use nothing the pipelined lanes use.  STREAM CAPTURE: once
+ * sm_plan_reserve_sgm has been called; before, the call is refused with SM_ERR_ARG, a message naming it, and the
+ * capture valid.                                                                                                  */
+/* adds: SGM arg-min -> d_web; d_best (min_d S) and d_sub (int16, 1/16 shift) may be NULL */
+int sm_sgm_wta(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+               int p1, int p2, int paths, int pairs, int32_t *d_web, int32_t *d_best, int16_t *d_sub, void *stream);
+/* adds: the right-reference map (and, non-NULL, its minima), natural order */
+int sm_sgm_wta_right(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+                     int p1, int p2, int paths, int pairs, int32_t *d_web_right, int32_t *d_best_right, void *stream);
+/* adds: descriptors once, left + right aggregation, check; d_web = checked map (0 = rejected); d_sub = the left
+ * pass's subpixel map with 0 where rejected; d_best / d_web_right / d_rejected / d_sub may be NULL */
+int sm_sgm_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+              int p1, int p2, int paths, int pairs, int max_diff, int32_t *d_web, int32_t *d_best,
+              int32_t *d_web_right, int32_t *d_rejected, int16_t *d_sub, void *stream);
+/* adds: allocates the SGM workspace now; idempotent */
+int sm_plan_reserve_sgm(sm_plan *plan);
+
 /* ---- step 3 -------------------------------------------------------------- *
  * fill_web_holes (src/stereo.cu:235-256): every pixel that is 0 becomes the
  * truncated mean of its four flat-index neighbours.  The reference's pointer

@@ -116,6 +116,9 @@ struct sm_plan {
     // census cost mode (sm_census.hip): NOT allocated with the plan, but by sm_plan_reserve_census or the first call
     // that needs it; part of the workspace from then on (with d_web_lr, which it allocates if the plan has none yet)
     u32 *d_census;       // descriptors [side: 0 = left, 1 = right][max_pairs][H][W], 8 bytes each (4 for c <= 5)
+    // SGM over the census data term (sm_census.hip, sm_sgm.h): NOT allocated with the plan, but by sm_plan_reserve_sgm or
+    // the first call that needs it (with the census workspace); part of the workspace from then on
+    void *d_sgm;         // one pair's volumes: A [H][W][Dp] u16, then S [H][W][Dp] i32 (Dp = 64, 128 or 256 >= num_shifts)
 };
 
 // XCD-aware tile order (device side).  Workgroups are dealt round-robin to the 8

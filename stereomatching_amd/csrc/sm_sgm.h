@@ -1,0 +1,316 @@
+// sm_sgm.h -- semi-global matching over the census data term (include/stereo_hip.h).  Included by
+// sm_census.hip only: the kernels read its descriptors, and its entry points launch them.
+//
+// PARITY UNPINNED, like census: the reference has no SGM.  Definition (tests/sgm_reference.py is its executable form):
+//   A(p, d)   = the census window cost of sm_census_wta (d = 0 .. D - 1), A <= 48 * 625
+//   L_r(p, d) = A(p, d) where q = p - r lies outside the image (paths never wrap, in either border mode), else
+//               A(p, d) + min(L_r(q, d), L_r(q, d -+ 1) + P1, m_q + P2) - m_q,  m_q = min_k L_r(q, k);
+//               terms with d -+ 1 outside 0 .. D - 1 dropped.  A <= L_r <= A + P2 <= 62767 (u16 bound).
+//   S(p, d)   = sum of L_r over the 4 or 8 directions r; best = min_d S, web = 1 + the first d reaching it;
+//   sub       = sm_cost_refine's SSD (parabola) rule on S(s-2), S(s-1), S(s), s = web.
+//
+// Volumes (the plan's SGM workspace, one pair at a time): A [H][W][Dp] u16 and S [H][W][Dp] i32, Dp = 64, 128 or 256 (the
+// least that holds D), d innermost.  The path kernels give a line to a wave, lane l holding shifts K l .. K l + K - 1
+// (K = Dp / 64), so that every step reads and writes Dp contiguous entries; entries d >= D are never read as costs.
+//
+// Kernels:
+//   k_sgm_cost_h   the horizontal window sums of the Hamming costs of one row (n = 1: A itself): a lane owns one shift
+//                  and slides an n-wide window along a run of columns (two v_bcnt per output after the first).
+//                  MIRROR: the right-reference data term, the descriptors read in mirrored order (as k_census_wta).
+//   k_sgm_cost_v   the vertical window sums of those (n > 1), a lane per (column, shift) sliding down a run of rows.
+//   k_sgm_path     one direction of the recurrence.  FIRST writes S = L_r, MID adds L_r into S, LAST adds it in
+//                  registers and emits web / best / sub, so the final S is never stored.  The data term (and S) of
+//                  step i + SGP_PF is loaded while step i is computed: the chain of a line is thousands of steps long,
+//                  and without that it waits on memory at every one.  d -+ 1 are ds_bpermute shifts of one lane's end
+//                  values; m_q is an in-lane min, four DPP min steps within each row of 16 lanes and four readlanes.
+//   k_sgm_sub_mask sub = 0 where the checked map is 0 (sm_sgm_lr).
+
+#pragma once
+
+typedef unsigned short u16;
+
+#define SGM_MAX_SHIFTS 256
+#define SGM_INF 0x3fffffff        // L of a shift outside 0 .. D - 1: never a minimum, + P1 cannot wrap
+#define SGP_PF 8                  // path kernel: steps loaded ahead
+#define SGC_XR 32                 // k_sgm_cost_h: columns per lane
+#define SGC_YR 64                 // k_sgm_cost_v: rows per lane
+
+struct SgmCostGeom {
+    int w, h, D, Dp, half;
+    long long side;               // descriptors from side 0 (left) to side 1 (right) of the census workspace
+    long long pair;               // descriptors of the pair's left image from the start of its side
+};
+
+// descriptor of column c (pass coordinates; MIRROR: natural column W - 1 - c) of row y of an image
+template <int NW, bool MIRROR>
+__device__ __forceinline__ u64 sgm_desc(const u32 *img, int W, int y, int c)
+{
+    const size_t i = (size_t)y * W + (MIRROR ? W - 1 - c : c);
+    if constexpr (NW == 2) return reinterpret_cast<const u64 *>(img)[i];
+    else return img[i];
+}
+
+// grid (ceil(W / SGC_XR), ceil(H / 4), Dp / 64), block (64, 4): lane = shift, threadIdx.y = row
+template <int NW, bool GHOST, bool MIRROR>
+__global__ __launch_bounds__(256) void k_sgm_cost_h(const u32 *__restrict__ desc, u16 *__restrict__ out,
+                                                    const SgmCostGeom g)
+{
+    const int d = blockIdx.z * 64 + threadIdx.x;
+    const int y = blockIdx.y * 4 + threadIdx.y;
+    const int x0 = blockIdx.x * SGC_XR;
+    const int W = g.w;
+    if (y >= g.h) return;
+    const int x1 = min(x0 + SGC_XR, W);
+    u16 *o = out + ((size_t)y * W) * g.Dp + d;
+    if (d >= g.D) {
+        for (int x = x0; x < x1; x++) o[(size_t)x * g.Dp] = 0;
+        return;
+    }
+    // MIRROR: the pass's left image is mirror(R), its right image mirror(L)
+    const u32 *dL = desc + (size_t)NW * ((MIRROR ? (size_t)g.side : 0) + (size_t)g.pair);
+    const u32 *dR = desc + (size_t)NW * ((MIRROR ? 0 : (size_t)g.side) + (size_t)g.pair);
+    // the Hamming cost of tap column xx (pass coordinates) at shift d
+    auto cost = [&](int xx) -> u32 {
+        u64 l, r = 0;
+        if (GHOST) {
+            if (xx < 0 || xx >= W) return 0u;
+            l = sgm_desc<NW, MIRROR>(dL, W, y, xx);
+            if (xx + d < W) r = sgm_desc<NW, MIRROR>(dR, W, y, xx + d);
+        } else {
+            xx = smn_mod(xx, W);
+            l = sgm_desc<NW, MIRROR>(dL, W, y, xx);
+            r = sgm_desc<NW, MIRROR>(dR, W, y, smn_mod(xx + d, W));
+        }
+        return (u32)__builtin_popcountll(l ^ r);
+    };
+    u32 s = 0;
+    for (int t = -g.half; t <= g.half; t++) s += cost(x0 + t);
+    o[(size_t)x0 * g.Dp] = (u16)s;
+    for (int x = x0 + 1; x < x1; x++) {
+        s += cost(x + g.half);
+        s -= cost(x - 1 - g.half);
+        o[(size_t)x * g.Dp] = (u16)s;
+    }
+}
+
+// grid (ceil(W / 4), ceil(H / SGC_YR), Dp / 64), block (64, 4): lane = shift, threadIdx.y = column
+template <bool GHOST>
+__global__ __launch_bounds__(256) void k_sgm_cost_v(const u16 *__restrict__ hs, u16 *__restrict__ out,
+                                                    const SgmCostGeom g)
+{
+    const int d = blockIdx.z * 64 + threadIdx.x;
+    const int x = blockIdx.x * 4 + threadIdx.y;
+    const int y0 = blockIdx.y * SGC_YR;
+    const int W = g.w, H = g.h;
+    if (x >= W) return;
+    const int y1 = min(y0 + SGC_YR, H);
+    const size_t col = (size_t)x * g.Dp + d, row = (size_t)W * g.Dp;
+    auto tap = [&](int yy) -> u32 {
+        if (GHOST) {
+            if (yy < 0 || yy >= H) return 0u;
+        } else {
+            yy = smn_mod(yy, H);
+        }
+        return hs[(size_t)yy * row + col];
+    };
+    u32 s = 0;
+    for (int t = -g.half; t <= g.half; t++) s += tap(y0 + t);
+    out[(size_t)y0 * row + col] = (u16)s;
+    for (int y = y0 + 1; y < y1; y++) {
+        s += tap(y + g.half);
+        s -= tap(y - 1 - g.half);
+        out[(size_t)y * row + col] = (u16)s;
+    }
+}
+
+struct SgmPathGeom {
+    int w, h, D, Dp;
+    int p1, p2;
+    int dx, dy;                   // the direction r
+    int lines;
+    int mirror;                   // LAST: the pass is the right-reference one: map column x is natural W - 1 - x
+    long long map;                // LAST: element offset of the pair's maps
+};
+
+enum { SGM_FIRST = 0, SGM_MID = 1, SGM_LAST = 2 };
+
+template <int K> struct SgmVec;
+template <> struct SgmVec<1> {
+    static __device__ __forceinline__ void load_a(const u16 *p, i32 (&v)[1]) { v[0] = p[0]; }
+    static __device__ __forceinline__ void load_s(const i32 *p, i32 (&v)[1]) { v[0] = p[0]; }
+    static __device__ __forceinline__ void store_s(i32 *p, const i32 (&v)[1]) { p[0] = v[0]; }
+};
+template <> struct SgmVec<2> {
+    static __device__ __forceinline__ void load_a(const u16 *p, i32 (&v)[2])
+    {
+        const u32 t = *reinterpret_cast<const u32 *>(p);
+        v[0] = (i32)(t & 0xffff); v[1] = (i32)(t >> 16);
+    }
+    static __device__ __forceinline__ void load_s(const i32 *p, i32 (&v)[2])
+    {
+        const int2 t = *reinterpret_cast<const int2 *>(p);
+        v[0] = t.x; v[1] = t.y;
+    }
+    static __device__ __forceinline__ void store_s(i32 *p, const i32 (&v)[2])
+    {
+        *reinterpret_cast<int2 *>(p) = make_int2(v[0], v[1]);
+    }
+};
+template <> struct SgmVec<4> {
+    static __device__ __forceinline__ void load_a(const u16 *p, i32 (&v)[4])
+    {
+        const uint2 t = *reinterpret_cast<const uint2 *>(p);
+        v[0] = (i32)(t.x & 0xffff); v[1] = (i32)(t.x >> 16); v[2] = (i32)(t.y & 0xffff); v[3] = (i32)(t.y >> 16);
+    }
+    static __device__ __forceinline__ void load_s(const i32 *p, i32 (&v)[4])
+    {
+        const int4 t = *reinterpret_cast<const int4 *>(p);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    }
+    static __device__ __forceinline__ void store_s(i32 *p, const i32 (&v)[4])
+    {
+        *reinterpret_cast<int4 *>(p) = make_int4(v[0], v[1], v[2], v[3]);
+    }
+};
+
+// the minimum over the wave (uniform): in-lane values already merged into v
+__device__ __forceinline__ i32 sgm_wave_min(i32 v)
+{
+    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xf, 0xf, false));     // quad_perm [1, 0, 3, 2]
+    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xf, 0xf, false));     // quad_perm [2, 3, 0, 1]
+    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xf, 0xf, false));    // row_half_mirror
+    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xf, 0xf, false));    // row_mirror
+    return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+               min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+
+// entry k of lane `lane` (both uniform) of a K-vector
+template <int K>
+__device__ __forceinline__ i32 sgm_pick(const i32 (&v)[K], int lane, int k)
+{
+    i32 t = v[0];
+#pragma unroll
+    for (int j = 1; j < K; j++) t = k == j ? v[j] : t;
+    return __builtin_amdgcn_readlane(t, lane);
+}
+
+// grid ceil(lines / 4), block 256: one line per wave
+template <int K, int MODE>
+__global__ __launch_bounds__(256) void k_sgm_path(const u16 *__restrict__ A, i32 *__restrict__ S, i32 *web, i32 *best,
+                                                  int16_t *sub, const SgmPathGeom g)
+{
+    const int lane = threadIdx.x & 63;
+    const int line = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (line >= g.lines) return;
+    const int W = g.w, H = g.h;
+    // the line's first pixel: its predecessor lies outside the image
+    int x0, y0;
+    if (g.dy == 0) {
+        y0 = line; x0 = g.dx > 0 ? 0 : W - 1;
+    } else if (g.dx == 0) {
+        x0 = line; y0 = g.dy > 0 ? 0 : H - 1;
+    } else if (line < W) {
+        x0 = line; y0 = g.dy > 0 ? 0 : H - 1;
+    } else {
+        const int j = line - W + 1;
+        x0 = g.dx > 0 ? 0 : W - 1; y0 = g.dy > 0 ? j : H - 1 - j;
+    }
+    const int lx = g.dx > 0 ? W - x0 : g.dx < 0 ? x0 + 1 : 0x7fffffff;
+    const int ly = g.dy > 0 ? H - y0 : g.dy < 0 ? y0 + 1 : 0x7fffffff;
+    const int len = min(lx, ly);
+    const long long pstep = (long long)g.dy * W + g.dx;          // pixels per step
+    const long long p0 = (long long)y0 * W + x0;
+    const int dl = lane * K;                                     // this lane's first shift
+    const u16 *a0 = A + (size_t)p0 * g.Dp + dl;
+    i32 *s0 = S + (size_t)p0 * g.Dp + dl;
+    const long long vstep = pstep * g.Dp;
+
+    i32 ar[SGP_PF][K], sr[SGP_PF][K];
+    auto load = [&](int i, i32 (&av)[K], i32 (&sv)[K]) {
+        SgmVec<K>::load_a(a0 + i * vstep, av);
+        if (MODE != SGM_FIRST) SgmVec<K>::load_s(s0 + i * vstep, sv);
+    };
+#pragma unroll
+    for (int j = 0; j < SGP_PF; j++)
+        if (j < len) load(j, ar[j], sr[j]);
+
+    i32 L[K];
+    i32 m = 0;
+    const i32 P1 = g.p1, P2 = g.p2;
+    for (int base = 0; base < len; base += SGP_PF) {
+#pragma unroll
+        for (int j = 0; j < SGP_PF; j++) {
+            const int i = base + j;
+            if (i >= len) break;
+            i32 av[K], sv[K];
+#pragma unroll
+            for (int k = 0; k < K; k++) { av[k] = ar[j][k]; sv[k] = sr[j][k]; }
+            if (i + SGP_PF < len) load(i + SGP_PF, ar[j], sr[j]);
+            if (i == 0) {
+#pragma unroll
+                for (int k = 0; k < K; k++) L[k] = dl + k < g.D ? av[k] : SGM_INF;
+            } else {
+                i32 lo = __shfl_up(L[K - 1], 1), hi = __shfl_down(L[0], 1);   // L(q, d - 1) of entry 0, L(q, d + 1) of K - 1
+                if (lane == 0) lo = SGM_INF;
+                if (lane == 63) hi = SGM_INF;
+                const i32 jump = m + P2;
+                i32 nl[K];
+#pragma unroll
+                for (int k = 0; k < K; k++) {
+                    const i32 dm = k == 0 ? lo : L[k - 1], dp = k == K - 1 ? hi : L[k + 1];
+                    const i32 t = min(min(L[k], min(dm, dp) + P1), jump);
+                    nl[k] = dl + k < g.D ? av[k] + t - m : SGM_INF;
+                }
+#pragma unroll
+                for (int k = 0; k < K; k++) L[k] = nl[k];
+            }
+            i32 lm = L[0];
+#pragma unroll
+            for (int k = 1; k < K; k++) lm = min(lm, L[k]);
+            m = sgm_wave_min(lm);
+
+            if (MODE == SGM_FIRST) {
+                SgmVec<K>::store_s(s0 + i * vstep, L);
+            } else if (MODE == SGM_MID) {
+                i32 t[K];
+#pragma unroll
+                for (int k = 0; k < K; k++) t[k] = sv[k] + L[k];
+                SgmVec<K>::store_s(s0 + i * vstep, t);
+            } else {
+                // S <= 8 * 62767 < 2^19: keys S << 8 | d, the first d wins a tie; entries d >= D lose to every real one
+                i32 tot[K], key = 0x7fffffff;
+#pragma unroll
+                for (int k = 0; k < K; k++) {
+                    tot[k] = sv[k] + L[k];
+                    if (dl + k < g.D) key = min(key, (tot[k] << 8) | (dl + k));
+                }
+                key = sgm_wave_min(key);
+                const int s = (key & 0xff) + 1;
+                const i32 b = key >> 8;
+                int16_t q16 = (int16_t)(16 * s);
+                if (sub && s > 1 && s < g.D) {
+                    const i32 sm2 = sgm_pick<K>(tot, (s - 2) / K, (s - 2) % K);
+                    const i32 sp = sgm_pick<K>(tot, s / K, s % K);
+                    const i32 a = sm2 - b, c = sp - b, den = a + c;
+                    int q = 0;
+                    if (den > 0) q = min(8, max(-8, smn_floordiv(16 * (a - c) + den, 2 * den)));
+                    q16 = (int16_t)(16 * s + q);
+                }
+                if (lane == 0) {
+                    const int x = x0 + i * g.dx, y = y0 + i * g.dy;
+                    const size_t o = (size_t)g.map + (size_t)y * W + (g.mirror ? W - 1 - x : x);
+                    web[o] = s;
+                    if (best) best[o] = b;
+                    if (sub) sub[o] = q16;
+                }
+            }
+        }
+    }
+}
+
+// sub = 0 where the checked map is 0
+__global__ __launch_bounds__(256) void k_sgm_sub_mask(const i32 *__restrict__ web, int16_t *__restrict__ sub, long long n)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n && web[i] == 0) sub[i] = 0;
+}

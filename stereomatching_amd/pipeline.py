@@ -42,6 +42,15 @@ class LRResult(NamedTuple):
     best: Optional[torch.Tensor]
 
 
+class SGMLRResult(NamedTuple):
+    """StereoPlan.sgm_lr: LRResult's maps and the left pass's subpixel map (0 where rejected)"""
+    web: torch.Tensor
+    rejected: torch.Tensor
+    web_right: Optional[torch.Tensor]
+    best: Optional[torch.Tensor]
+    sub: Optional[torch.Tensor]
+
+
 WEB_TYPES = {torch.int32: capi.SM_WEB_I32, torch.uint16: capi.SM_WEB_U16, torch.uint8: capi.SM_WEB_U8}
 
 
@@ -454,6 +463,54 @@ class StereoPlan:
         check(lib.sm_census_refine(self._h, _ptr(left), _ptr(right), int(census), pairs, _ptr(web), _ptr(out),
                                    _ptr(costs), self._stream()))
         return out, costs
+
+    # ---- semi-global matching over the census data term ------------------------
+    def reserve_sgm(self):
+        """The SGM workspace (the census workspace, and the data-term and aggregate volumes of one pair), allocated now:
+        keeps the allocation out of timed paths and out of stream captures."""
+        check(lib.sm_plan_reserve_sgm(self._h))
+
+    def sgm_wta(self, left, right, census=7, p1=10, p2=120, paths=8, want_best=True, want_sub=False, web=None,
+                best=None, sub=None):
+        """Semi-global matching over the census cost (sm_sgm_wta, parity unpinned) -> (web, best, sub): the census
+        window cost aggregated along `paths` (4 or 8) image lines with penalty p1 for a one-shift step and p2 for a
+        larger jump, arg-min over the shifts (first shift wins), best = the minimum aggregate, sub int16 in 1/16 of a
+        shift (parabola fit on the aggregates).  Outputs not wanted are None.  The default penalties suit a 1 x 1
+        window (the pixelwise census cost, at most 48); window costs grow with n^2, so scale p1 and p2 with it."""
+        left, right, pairs = self._census_pair(left, right)
+        web = self._out(web, pairs, "web")
+        best = self._out(best, pairs, "best") if want_best else None
+        sub = self._out(sub, pairs, "sub", torch.int16) if want_sub else None
+        check(lib.sm_sgm_wta(self._h, _ptr(left), _ptr(right), int(census), int(p1), int(p2), int(paths), pairs,
+                             _ptr(web), _ptr(best), _ptr(sub), self._stream()))
+        return web, best, sub
+
+    def sgm_wta_right(self, left, right, census=7, p1=10, p2=120, paths=8, want_best=True, web_right=None,
+                      best_right=None):
+        """The SGM right-reference map (sm_sgm_wta_right) -> (web_right, best_right): web_right(u, y) = s' means right
+        pixel u matched left pixel u - (s' - 1)."""
+        left, right, pairs = self._census_pair(left, right)
+        web_right = self._out(web_right, pairs, "web_right")
+        best_right = self._out(best_right, pairs, "best_right") if want_best else None
+        check(lib.sm_sgm_wta_right(self._h, _ptr(left), _ptr(right), int(census), int(p1), int(p2), int(paths), pairs,
+                                   _ptr(web_right), _ptr(best_right), self._stream()))
+        return web_right, best_right
+
+    def sgm_lr(self, left, right, census=7, p1=10, p2=120, paths=8, max_diff=0, want_right=False, want_best=False,
+               want_sub=False, web=None, web_right=None, best=None, sub=None) -> SGMLRResult:
+        """Left and right SGM and the check in one call (sm_sgm_lr) -> SGMLRResult(web, rejected, web_right, best,
+        sub); web is the checked map (0 = rejected), best the left minima, sub the left subpixel map with 0 where
+        rejected."""
+        left, right, pairs = self._census_pair(left, right)
+        web = self._out(web, pairs, "web")
+        web_right = self._out(web_right, pairs, "web_right") if want_right else None
+        best = self._out(best, pairs, "best") if want_best else None
+        sub = self._out(sub, pairs, "sub", torch.int16) if want_sub else None
+        rejected = torch.empty(pairs, dtype=torch.int32, device=self._dev)
+        check(lib.sm_sgm_lr(self._h, _ptr(left), _ptr(right), int(census), int(p1), int(p2), int(paths), pairs,
+                            int(max_diff), _ptr(web), _ptr(best), _ptr(web_right), _ptr(rejected), _ptr(sub),
+                            self._stream()))
+        return SGMLRResult(web, rejected, web_right, best, sub)
 
     def debug_planes(self, pair: int, shift: int):
         """matches-i, score_all-i, scores-i of the reference's debug build."""
