@@ -535,6 +535,42 @@ int sm_sgm_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_r
 /* adds: allocates the SGM workspace now; idempotent */
 int sm_plan_reserve_sgm(sm_plan *plan);
 
+/* ---- disparity post-filters: PARITY UNPINNED ------------------------------ *
+ * New work (no reference counterpart).  Two filters on the maps the calls above produce, between the
+ * consistency check and step 3: cost -> check -> speckle / median -> hole filling.  Maps are [pairs][H][W] of type
+ * SM_MAP_I32 (a web map) or SM_MAP_I16 (a sub map); a pixel is VALID iff its value != 0 (the check's convention).
+ * Neighbourhoods never wrap, in either border mode: a tap outside the image does not exist.  Pairs are independent.
+ *   median, window k in {3, 5}: out(p) = 0 where in(p) = 0 (holes are step 3's to fill); else, with v_0 <= ... <=
+ *     v_(m-1) the valid values of the k x k window around p that lie in the image (m >= 1: the centre is one),
+ *     out(p) = v_((m-1)/2), integer division: the lower median.  Negative values are valid and order as signed
+ *     integers.  d_in and d_out must not overlap.
+ *   speckle removal, max_size >= 0, max_diff >= 0: the valid pixels form a graph in which two 4-neighbours a, b are
+ *     joined iff |in(a) - in(b)| <= max_diff; out(p) = in(p) if p is valid and its connected component has more
+ *     than max_size pixels, else 0.  d_removed: NULL or one int32 per pair, the number of valid pixels set to 0.
+ *     (OpenCV's filterSpeckles with newVal = 0 and 0 as "already invalid".)  The result does not depend on the
+ *     order in which the graph is explored.  d_out may equal d_in (the labels are complete before anything is
+ *     written); any other overlap is refused.
+ *   sub mask: d_sub = 0 where d_web = 0, so that a sub map follows a web map the speckle filter has thinned.
+ * Arguments are checked before any device call; a refusal names the function.  All calls run in `stream` order and
+ * use nothing the pipelined lanes use.  sm_median_filter and sm_sub_mask need no workspace and can always be
+ * captured.  sm_speckle_filter's workspace is one int32 label and one int32 component size per pixel,
+ * 8 * max_pairs * W * H bytes; allocated by sm_plan_reserve_filter or, without it, by the first sm_speckle_filter (a
+ * hipMalloc, which synchronises the device), counted in sm_plan_workspace_bytes from then on, freed by
+ * sm_plan_destroy; a plan that never filters allocates nothing.  STREAM CAPTURE: sm_speckle_filter once
+ * sm_plan_reserve_filter has been called; before, it is refused with SM_ERR_ARG, a message naming it, and the
+ * capture valid.                                                                                              */
+#define SM_MAP_I32 0
+#define SM_MAP_I16 1
+/* adds: the validity-aware k x k median of d_in -> d_out (same type) */
+int sm_median_filter(sm_plan *plan, const void *d_in, int map_type, int k, int pairs, void *d_out, void *stream);
+/* adds: speckle removal of d_in -> d_out (same type; in place allowed) */
+int sm_speckle_filter(sm_plan *plan, const void *d_in, int map_type, int max_size, int max_diff, int pairs,
+                      void *d_out, int32_t *d_removed, void *stream);
+/* adds: d_sub = 0 where d_web = 0 */
+int sm_sub_mask(sm_plan *plan, const int32_t *d_web, int16_t *d_sub, int pairs, void *stream);
+/* adds: allocates the speckle filter's workspace now; idempotent */
+int sm_plan_reserve_filter(sm_plan *plan);
+
 /* ---- step 3 -------------------------------------------------------------- *
  * fill_web_holes (src/stereo.cu:235-256): every pixel that is 0 becomes the
  * truncated mean of its four flat-index neighbours.  The reference's pointer

@@ -19,6 +19,7 @@ HEADER = PKG.parent / "include" / "stereo_hip.h"
 SM_OK, SM_ERR_ARG, SM_ERR_HIP, SM_ERR_NOMEM, SM_ERR_ZERO_DIV = range(5)
 SM_TOROIDAL, SM_GHOST = 0, 1
 SM_WEB_I32, SM_WEB_U16, SM_WEB_U8 = 0, 1, 2
+SM_MAP_I32, SM_MAP_I16 = 0, 1
 BORDERS = {"toroidal": SM_TOROIDAL, "ghost": SM_GHOST}
 
 
@@ -135,6 +136,10 @@ _SIGNATURES = {
     "sm_sgm_wta_right": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sm_sgm_lr": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sm_plan_reserve_sgm": (_int, [_vp]),
+    "sm_median_filter": (_int, [_vp, _vp, _int, _int, _int, _vp, _vp]),
+    "sm_speckle_filter": (_int, [_vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp]),
+    "sm_sub_mask": (_int, [_vp, _vp, _vp, _int, _vp]),
+    "sm_plan_reserve_filter": (_int, [_vp]),
 }
 
 

@@ -963,3 +963,23 @@ extern "C" int sm_sgm_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_
     if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_sgm_sub_mask failed: %s", hipGetErrorString(e));
     return SM_OK;
 }
+
+// sub = 0 where web = 0, for maps of the caller's: k_sgm_sub_mask as sm_sgm_lr launches it (a sub map follows a web map
+// that sm_speckle_filter has thinned)
+extern "C" int sm_sub_mask(sm_plan *plan, const int32_t *d_web, int16_t *d_sub, int pairs, void *stream)
+{
+    const char *me = "sm_sub_mask";
+    if (!d_web || !d_sub) return sm_fail(SM_ERR_ARG, "%s: a map pointer is NULL", me);
+    if (!plan) return sm_fail(SM_ERR_ARG, "%s: plan is NULL", me);
+    if (pairs < 1 || pairs > plan->max_pairs)
+        return sm_fail(SM_ERR_ARG, "%s: pairs %d outside 1..%d (max_pairs of the plan)", me, pairs, plan->max_pairs);
+    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
+    if (overlap(d_sub, d_web, map / 2, map)) return sm_fail(SM_ERR_ARG, "%s: maps overlap", me);
+    SM_TRY(sm_use_device(plan->device));
+    const long long n = (long long)pairs * plan->width * plan->height;
+    void *args[] = {(void *)&d_web, (void *)&d_sub, (void *)&n};
+    const hipError_t e = hipLaunchKernel((const void *)k_sgm_sub_mask, dim3((unsigned)((n + 255) / 256)), dim3(256), args,
+                                         0, (hipStream_t)stream);
+    if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_sgm_sub_mask failed: %s", hipGetErrorString(e));
+    return SM_OK;
+}

@@ -119,6 +119,9 @@ struct sm_plan {
     // SGM over the census data term (sm_census.hip, sm_sgm.h): NOT allocated with the plan, but by sm_plan_reserve_sgm or
     // the first call that needs it (with the census workspace); part of the workspace from then on
     void *d_sgm;         // one pair's volumes: A [H][W][Dp] u16, then S [H][W][Dp] i32 (Dp = 64, 128 or 256 >= num_shifts)
+    // speckle filter (sm_filter.h, launched by sm_lr.hip): NOT allocated with the plan, but by sm_plan_reserve_filter or
+    // the first sm_speckle_filter; part of the workspace from then on
+    i32 *d_filter;       // labels [max_pairs][H][W] int32, then component sizes [max_pairs][H][W] int32
 };
 
 // XCD-aware tile order (device side).  Workgroups are dealt round-robin to the 8

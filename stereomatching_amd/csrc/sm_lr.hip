@@ -213,6 +213,9 @@ __global__ __launch_bounds__(256) void k_mirror_gray(const u8 *__restrict__ left
     }
 }
 
+// the post-filters (median, speckle removal): kernels; their entry points are at the end of this file
+#include "sm_filter.h"
+
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
@@ -231,7 +234,7 @@ static size_t lr_gray_batch_bytes(const sm_plan *plan)
 size_t sm_lr_workspace_bytes(const sm_plan *plan)
 {
     return (plan->d_ext_lr ? plan->ext_bytes : 0) + (plan->d_web_lr ? lr_map_bytes(plan) : 0) +
-           (plan->d_gray_lr ? 2 * lr_gray_batch_bytes(plan) : 0);
+           (plan->d_gray_lr ? 2 * lr_gray_batch_bytes(plan) : 0) + (plan->d_filter ? 2 * lr_map_bytes(plan) : 0);
 }
 
 void sm_lr_free(sm_plan *plan)
@@ -242,6 +245,8 @@ void sm_lr_free(sm_plan *plan)
     plan->d_ext_lr = nullptr;
     plan->d_web_lr = nullptr;
     plan->d_gray_lr = nullptr;
+    if (plan->d_filter) (void)hipFree(plan->d_filter);
+    plan->d_filter = nullptr;
 }
 
 // `*buf` (bytes long) and, if the plan has none yet, the mirrored-order map shared by both checks; on failure
@@ -585,4 +590,116 @@ int sm_lr_check_natural(const sm_plan *plan, const i32 *web, const i32 *right, i
                         int pairs, hipStream_t st)
 {
     return lr_check_launch(plan, false, web, right, out, nullptr, rejected, max_diff, pairs, st);
+}
+
+// ---------------------------------------------------------------------------
+// post-filters (sm_filter.h): validity-aware median, speckle removal
+// ---------------------------------------------------------------------------
+
+static int filter_map_type(int map_type, const char *me, size_t *elem)
+{
+    if (map_type != SM_MAP_I32 && map_type != SM_MAP_I16)
+        return sm_fail(SM_ERR_ARG, "%s: map_type %d is neither SM_MAP_I32 nor SM_MAP_I16", me, map_type);
+    *elem = map_type == SM_MAP_I32 ? sizeof(i32) : sizeof(int16_t);
+    return SM_OK;
+}
+
+extern "C" int sm_median_filter(sm_plan *plan, const void *d_in, int map_type, int k, int pairs, void *d_out, void *stream)
+{
+    const char *me = "sm_median_filter";
+    size_t elem;
+    if (!d_in || !d_out) return sm_fail(SM_ERR_ARG, "%s: a map pointer is NULL", me);
+    SM_TRY(filter_map_type(map_type, me, &elem));
+    if (k != 3 && k != 5) return sm_fail(SM_ERR_ARG, "%s: k %d is not 3 or 5", me, k);
+    SM_TRY(check_pairs(plan, pairs, me));
+    const int W = plan->width, H = plan->height;
+    if (overlap(d_in, d_out, (size_t)pairs * W * H * elem))
+        return sm_fail(SM_ERR_ARG, "%s: maps overlap (every output pixel reads its neighbours' inputs)", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((W + FLT_TW - 1) / FLT_TW, (H + FLT_TH - 1) / FLT_TH, pairs), block(256);
+#define SM_MED_GO(T, K) hipLaunchKernelGGL((k_median<T, K>), grid, block, 0, st, (const T *)d_in, (T *)d_out, W, H)
+    if (map_type == SM_MAP_I32) { if (k == 3) SM_MED_GO(i32, 3); else SM_MED_GO(i32, 5); }
+    else                        { if (k == 3) SM_MED_GO(int16_t, 3); else SM_MED_GO(int16_t, 5); }
+#undef SM_MED_GO
+    SM_LAUNCH_CHECK("k_median");
+    return SM_OK;
+}
+
+// labels and component sizes, one int32 each per pixel of max_pairs maps (every word a call reads is written by
+// k_spk_local first)
+static int reserve_filter(sm_plan *plan, const char *me)
+{
+    if (plan->d_filter) return SM_OK;
+    void *b = nullptr;
+    const hipError_t e = hipMalloc(&b, 2 * lr_map_bytes(plan));
+    if (e != hipSuccess)
+        return sm_fail(e == hipErrorOutOfMemory ? SM_ERR_NOMEM : SM_ERR_HIP, "%s: %zu bytes for the labels and sizes of the "
+                       "speckle filter: %s", me, 2 * lr_map_bytes(plan), hipGetErrorString(e));
+    plan->d_filter = (i32 *)b;
+    return SM_OK;
+}
+
+extern "C" int sm_plan_reserve_filter(sm_plan *plan)
+{
+    if (!plan) return sm_fail(SM_ERR_ARG, "sm_plan_reserve_filter: plan is NULL");
+    SM_TRY(sm_use_device(plan->device));
+    return reserve_filter(plan, "sm_plan_reserve_filter");
+}
+
+template <typename T>
+static int speckle_launch(const sm_plan *plan, const T *in, T *out, int max_size, int max_diff, int pairs, i32 *removed,
+                          hipStream_t st)
+{
+    const int W = plan->width, H = plan->height;
+    const unsigned npx = (unsigned)W * H;
+    i32 *labels = plan->d_filter, *sizes = plan->d_filter + (size_t)plan->max_pairs * npx;
+    const unsigned tiles_x = (W + FLT_TW - 1) / FLT_TW, tiles_y = (H + FLT_TH - 1) / FLT_TH;
+    if (removed) {
+        hipLaunchKernelGGL(k_lr_zero_counts, dim3((pairs + 63) / 64), dim3(64), 0, st, removed, pairs);
+        SM_LAUNCH_CHECK("k_lr_zero_counts");
+    }
+    hipLaunchKernelGGL(k_spk_local<T>, dim3(tiles_x, tiles_y, pairs), dim3(256), 0, st, in, labels, sizes, W, H, max_diff);
+    SM_LAUNCH_CHECK("k_spk_local");
+    const unsigned n_h = (tiles_y - 1) * (unsigned)W, n_all = n_h + (tiles_x - 1) * (unsigned)H;
+    if (n_all) {
+        hipLaunchKernelGGL(k_spk_merge<T>, dim3((n_all + 255) / 256, pairs), dim3(256), 0, st, in, labels, W, H, max_diff,
+                           n_h, n_all);
+        SM_LAUNCH_CHECK("k_spk_merge");
+    }
+    hipLaunchKernelGGL(k_spk_count, dim3((npx + 255) / 256, pairs), dim3(256), 0, st, labels, sizes, npx);
+    SM_LAUNCH_CHECK("k_spk_count");
+    hipLaunchKernelGGL(k_spk_apply<T>, dim3(std::min((npx + 255) / 256, (unsigned)SM_LR_BLOCKS), pairs), dim3(256), 0, st,
+                       in, out, labels, sizes, removed, npx, max_size);
+    SM_LAUNCH_CHECK("k_spk_apply");
+    return SM_OK;
+}
+
+extern "C" int sm_speckle_filter(sm_plan *plan, const void *d_in, int map_type, int max_size, int max_diff, int pairs,
+                                 void *d_out, int32_t *d_removed, void *stream)
+{
+    const char *me = "sm_speckle_filter";
+    size_t elem;
+    if (!d_in || !d_out) return sm_fail(SM_ERR_ARG, "%s: a map pointer is NULL", me);
+    SM_TRY(filter_map_type(map_type, me, &elem));
+    if (max_size < 0) return sm_fail(SM_ERR_ARG, "%s: max_size %d is negative", me, max_size);
+    if (max_diff < 0) return sm_fail(SM_ERR_ARG, "%s: max_diff %d is negative", me, max_diff);
+    SM_TRY(check_pairs(plan, pairs, me));
+    const size_t map = (size_t)pairs * plan->width * plan->height * elem;
+    if (d_in != d_out && overlap(d_in, d_out, map))
+        return sm_fail(SM_ERR_ARG, "%s: maps overlap without d_out being d_in", me);
+    const size_t counts = (size_t)pairs * sizeof(i32);
+    if (d_removed && (overlap(d_removed, d_in, counts, map) || overlap(d_removed, d_out, counts, map)))
+        return sm_fail(SM_ERR_ARG, "%s: d_removed overlaps a map", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (!plan->d_filter) {
+        if (sm_stream_capturing(st))
+            return sm_fail(SM_ERR_ARG, "%s: the workspace of the speckle filter is not allocated and the stream is capturing "
+                           "(an allocation cannot be captured): call sm_plan_reserve_filter(plan) first", me);
+        SM_TRY(reserve_filter(plan, me));
+    }
+    if (map_type == SM_MAP_I32)
+        return speckle_launch<i32>(plan, (const i32 *)d_in, (i32 *)d_out, max_size, max_diff, pairs, d_removed, st);
+    return speckle_launch<int16_t>(plan, (const int16_t *)d_in, (int16_t *)d_out, max_size, max_diff, pairs, d_removed, st);
 }

@@ -52,6 +52,7 @@ class SGMLRResult(NamedTuple):
 
 
 WEB_TYPES = {torch.int32: capi.SM_WEB_I32, torch.uint16: capi.SM_WEB_U16, torch.uint8: capi.SM_WEB_U8}
+MAP_TYPES = {torch.int32: capi.SM_MAP_I32, torch.int16: capi.SM_MAP_I16}
 
 
 def _ptr(t):
@@ -511,6 +512,48 @@ class StereoPlan:
                             int(max_diff), _ptr(web), _ptr(best), _ptr(web_right), _ptr(rejected), _ptr(sub),
                             self._stream()))
         return SGMLRResult(web, rejected, web_right, best, sub)
+
+    # ---- disparity post-filters (between the check and step 3) ------------------
+    def reserve_filter(self):
+        """The speckle filter's workspace (a label and a component size per pixel of max_pairs maps), allocated now:
+        keeps the allocation out of timed paths and out of stream captures."""
+        check(lib.sm_plan_reserve_filter(self._h))
+
+    def _filter_map(self, t, name):
+        if t.dtype not in MAP_TYPES:
+            raise ValueError(f"{name}: need an int32 (web) or int16 (sub) map, got {t.dtype}")
+        return self._images(t, t.dtype, name)
+
+    def median_filter(self, map, k=3, out=None):
+        """Validity-aware k x k median (sm_median_filter) of an int32 web map or an int16 sub map -> the filtered map:
+        0 stays 0, a valid pixel becomes the lower median of the valid values of its window that lie in the image."""
+        map = self._filter_map(map, "map")
+        pairs = map.shape[0]
+        out = self._out(out, pairs, "out", map.dtype)
+        check(lib.sm_median_filter(self._h, _ptr(map), MAP_TYPES[map.dtype], int(k), pairs, _ptr(out), self._stream()))
+        return out
+
+    def speckle_filter(self, map, max_size, max_diff, out=None, want_removed=False):
+        """Speckle removal (sm_speckle_filter) of an int32 or int16 map -> the filtered map, or (map, removed pixels
+        per pair) with want_removed: valid pixels whose 4-connected component (neighbours joined where their values
+        differ by at most max_diff) has at most max_size pixels become 0.  out=map filters in place."""
+        map = self._filter_map(map, "map")
+        pairs = map.shape[0]
+        out = self._out(out, pairs, "out", map.dtype)
+        removed = torch.empty(pairs, dtype=torch.int32, device=self._dev) if want_removed else None
+        check(lib.sm_speckle_filter(self._h, _ptr(map), MAP_TYPES[map.dtype], int(max_size), int(max_diff), pairs,
+                                    _ptr(out), _ptr(removed), self._stream()))
+        return (out, removed) if want_removed else out
+
+    def sub_mask(self, web, sub):
+        """sub = 0 where web = 0, in place (sm_sub_mask) -> sub: lets a subpixel map follow a web map that
+        speckle_filter has thinned."""
+        web = self._images(web, torch.int32, "web")
+        sub = self._images(sub, torch.int16, "sub")
+        if sub.shape[0] != web.shape[0]:
+            raise ValueError(f"sub: {sub.shape[0]} maps for {web.shape[0]} pairs")
+        check(lib.sm_sub_mask(self._h, _ptr(web), _ptr(sub), web.shape[0], self._stream()))
+        return sub
 
     def debug_planes(self, pair: int, shift: int):
         """matches-i, score_all-i, scores-i of the reference's debug build."""
