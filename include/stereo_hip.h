@@ -571,6 +571,44 @@ int sm_sub_mask(sm_plan *plan, const int32_t *d_web, int16_t *d_sub, int pairs, 
 /* adds: allocates the speckle filter's workspace now; idempotent */
 int sm_plan_reserve_filter(sm_plan *plan);
 
+/* ---- occlusion-aware interpolation: PARITY UNPINNED ----------------------- *
+ * New work (no reference counterpart): Hirschmueller's discontinuity-preserving interpolation (PAMI
+ * 2008) of the 0s the check and the speckle filter leave: cost -> check -> speckle / median -> interpolate -> step 3.
+ * Maps and validity as for the post-filters; nothing wraps in the interpolation, in either border mode; pairs are
+ * independent.  web = 1 + shift: left pixel (x, y) with web = s matched right pixel u = x + s - 1, and
+ * web_right(u, y) = s' means right pixel u matched left pixel u - (s' - 1); a smaller value is farther away.
+ *   classification, from the right-reference map of the check, with the plan's W, H, D and border mode:
+ *     class(x, y) = 0 where web(x, y) != 0; else 2 (MISMATCHED) if there is a d in 0 .. D-1 with u = x + d inside the
+ *     row (toroidal: u mod W, always inside; ghost: u < W) and web_right(u, y) = d + 1; else 1 (OCCLUDED).  Values
+ *     of web_right outside 1 .. D match no d; no read leaves the row.
+ *   interpolation: out(p) = in(p) where in(p) != 0.  Else walk from p in each of the eight directions (+-1, 0),
+ *     (0, +-1), (+-1, +-1) to the first valid pixel of d_in or the image edge; the values found, c_0 <= ... <= c_(m-1)
+ *     in signed order, 0 <= m <= 8, are the candidates (always read from the input: a filled pixel is no source).
+ *     m = 0: out(p) = 0.  class(p) = 1: out(p) = c_(min(1, m-1)), the second lowest: background, robust to one
+ *     outlier.  Otherwise (class 0 or 2, or d_class NULL): out(p) = c_((m-1)/2), the lower median.  d_class is read
+ *     where in(p) = 0 only.  d_filled: NULL or one int32 per pair, the pixels that were 0 and are not any more.
+ *     d_in and d_out must not overlap.
+ * Arguments are checked before any device call; a refusal names the function.  All calls run in `stream` order and
+ * use nothing the pipelined lanes use.  sm_occlusion_classify needs no workspace and can always be captured.
+ * sm_interpolate's workspace is, with S = ceil(H / 64) and C = ceil(W / 64),
+ *     4 * max_pairs * (6 * W * H + 6 * S * (W + H - 1) + 2 * H * C) bytes
+ * (six directional maps, the carries of every line segment and of every row chunk); allocated by
+ * sm_plan_reserve_interp or, without it, by the first sm_interpolate (a hipMalloc, which synchronises the device;
+ * SM_ERR_NOMEM on failure), counted in sm_plan_workspace_bytes from then on, freed by sm_plan_destroy; a plan that
+ * never interpolates allocates nothing.  STREAM CAPTURE: sm_interpolate once sm_plan_reserve_interp has been called;
+ * before, it is refused with SM_ERR_ARG, a message naming it, and the capture valid.                              */
+#define SM_CLASS_VALID 0
+#define SM_CLASS_OCCLUDED 1
+#define SM_CLASS_MISMATCHED 2
+/* adds: 0 valid / 1 occluded / 2 mismatched for every pixel of the checked map d_web */
+int sm_occlusion_classify(sm_plan *plan, const int32_t *d_web, const int32_t *d_web_right, int pairs,
+                          uint8_t *d_class, void *stream);
+/* adds: discontinuity-preserving fill of the 0s of d_in -> d_out (same type); d_class may be NULL */
+int sm_interpolate(sm_plan *plan, const void *d_in, int map_type, const uint8_t *d_class, int pairs, void *d_out,
+                   int32_t *d_filled, void *stream);
+/* adds: allocates sm_interpolate's workspace now; idempotent */
+int sm_plan_reserve_interp(sm_plan *plan);
+
 /* ---- step 3 -------------------------------------------------------------- *
  * fill_web_holes (src/stereo.cu:235-256): every pixel that is 0 becomes the
  * truncated mean of its four flat-index neighbours.  The reference's pointer

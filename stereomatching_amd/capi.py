@@ -20,6 +20,7 @@ SM_OK, SM_ERR_ARG, SM_ERR_HIP, SM_ERR_NOMEM, SM_ERR_ZERO_DIV = range(5)
 SM_TOROIDAL, SM_GHOST = 0, 1
 SM_WEB_I32, SM_WEB_U16, SM_WEB_U8 = 0, 1, 2
 SM_MAP_I32, SM_MAP_I16 = 0, 1
+SM_CLASS_VALID, SM_CLASS_OCCLUDED, SM_CLASS_MISMATCHED = 0, 1, 2
 BORDERS = {"toroidal": SM_TOROIDAL, "ghost": SM_GHOST}
 
 
@@ -140,6 +141,9 @@ _SIGNATURES = {
     "sm_speckle_filter": (_int, [_vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sm_sub_mask": (_int, [_vp, _vp, _vp, _int, _vp]),
     "sm_plan_reserve_filter": (_int, [_vp]),
+    "sm_occlusion_classify": (_int, [_vp, _vp, _vp, _int, _vp, _vp]),
+    "sm_interpolate": (_int, [_vp, _vp, _int, _vp, _int, _vp, _vp, _vp]),
+    "sm_plan_reserve_interp": (_int, [_vp]),
 }
 
 

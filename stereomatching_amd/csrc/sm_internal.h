@@ -122,6 +122,10 @@ struct sm_plan {
     // speckle filter (sm_filter.h, launched by sm_lr.hip): NOT allocated with the plan, but by sm_plan_reserve_filter or
     // the first sm_speckle_filter; part of the workspace from then on
     i32 *d_filter;       // labels [max_pairs][H][W] int32, then component sizes [max_pairs][H][W] int32
+    // interpolation (sm_interp.h, launched by sm_lr.hip): NOT allocated with the plan, but by sm_plan_reserve_interp or
+    // the first sm_interpolate; part of the workspace from then on
+    i32 *d_interp;       // per pair: six directional maps [6][H][W], line carries [6][segments][W + H - 1], row carries
+                         // [2][H][chunks], 4 bytes an element (layout in sm_interp.h)
 };
 
 // XCD-aware tile order (device side).  Workgroups are dealt round-robin to the 8

@@ -215,6 +215,8 @@ __global__ __launch_bounds__(256) void k_mirror_gray(const u8 *__restrict__ left
 
 // the post-filters (median, speckle removal): kernels; their entry points are at the end of this file
 #include "sm_filter.h"
+// occlusion-aware interpolation: kernels; their entry points follow the post-filters'
+#include "sm_interp.h"
 
 // ---------------------------------------------------------------------------
 // host side
@@ -231,10 +233,26 @@ static size_t lr_gray_batch_bytes(const sm_plan *plan)
     return ((size_t)plan->max_pairs * plan->width * plan->height + 255) & ~(size_t)255;
 }
 
+// sm_interpolate's workspace (sm_interp.h), in 4-byte elements per pair: six directional maps, the carries of
+// W + H - 1 lines for six directions and every segment, the carries of every row chunk from either side
+static int itp_segs(const sm_plan *plan) { return (plan->height + ITP_SEG - 1) / ITP_SEG; }
+static int itp_chunks(const sm_plan *plan) { return (plan->width + ITP_CW - 1) / ITP_CW; }
+static size_t itp_loc_elems(const sm_plan *plan) { return (size_t)6 * plan->width * plan->height; }
+static size_t itp_car_elems(const sm_plan *plan)
+{
+    return (size_t)6 * itp_segs(plan) * (plan->width + plan->height - 1);
+}
+static size_t itp_row_elems(const sm_plan *plan) { return (size_t)2 * plan->height * itp_chunks(plan); }
+static size_t itp_bytes(const sm_plan *plan)
+{
+    return (size_t)plan->max_pairs * sizeof(i32) * (itp_loc_elems(plan) + itp_car_elems(plan) + itp_row_elems(plan));
+}
+
 size_t sm_lr_workspace_bytes(const sm_plan *plan)
 {
     return (plan->d_ext_lr ? plan->ext_bytes : 0) + (plan->d_web_lr ? lr_map_bytes(plan) : 0) +
-           (plan->d_gray_lr ? 2 * lr_gray_batch_bytes(plan) : 0) + (plan->d_filter ? 2 * lr_map_bytes(plan) : 0);
+           (plan->d_gray_lr ? 2 * lr_gray_batch_bytes(plan) : 0) + (plan->d_filter ? 2 * lr_map_bytes(plan) : 0) +
+           (plan->d_interp ? itp_bytes(plan) : 0);
 }
 
 void sm_lr_free(sm_plan *plan)
@@ -247,6 +265,8 @@ void sm_lr_free(sm_plan *plan)
     plan->d_gray_lr = nullptr;
     if (plan->d_filter) (void)hipFree(plan->d_filter);
     plan->d_filter = nullptr;
+    if (plan->d_interp) (void)hipFree(plan->d_interp);
+    plan->d_interp = nullptr;
 }
 
 // `*buf` (bytes long) and, if the plan has none yet, the mirrored-order map shared by both checks; on failure
@@ -702,4 +722,101 @@ extern "C" int sm_speckle_filter(sm_plan *plan, const void *d_in, int map_type, 
     if (map_type == SM_MAP_I32)
         return speckle_launch<i32>(plan, (const i32 *)d_in, (i32 *)d_out, max_size, max_diff, pairs, d_removed, st);
     return speckle_launch<int16_t>(plan, (const int16_t *)d_in, (int16_t *)d_out, max_size, max_diff, pairs, d_removed, st);
+}
+
+// ---------------------------------------------------------------------------
+// occlusion-aware interpolation (sm_interp.h): classification of the invalid pixels, discontinuity-preserving fill
+// ---------------------------------------------------------------------------
+
+extern "C" int sm_occlusion_classify(sm_plan *plan, const int32_t *d_web, const int32_t *d_web_right, int pairs,
+                                     uint8_t *d_class, void *stream)
+{
+    const char *me = "sm_occlusion_classify";
+    if (!d_web || !d_web_right || !d_class) return sm_fail(SM_ERR_ARG, "%s: a map pointer is NULL", me);
+    SM_TRY(check_pairs(plan, pairs, me));
+    const unsigned npx = (unsigned)plan->width * plan->height;
+    const size_t map = (size_t)pairs * npx * sizeof(i32);
+    if (overlap(d_class, d_web, map / 4, map) || overlap(d_class, d_web_right, map / 4, map))
+        return sm_fail(SM_ERR_ARG, "%s: d_class overlaps a map", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipLaunchKernelGGL(k_itp_classify, dim3((npx + 255) / 256, pairs), dim3(256), 0, (hipStream_t)stream, d_web,
+                       d_web_right, d_class, plan->width, npx, plan->num_shifts, plan->border == SM_GHOST ? 1 : 0);
+    SM_LAUNCH_CHECK("k_itp_classify");
+    return SM_OK;
+}
+
+// (every element a call reads is written by a kernel of the same call first)
+static int reserve_interp(sm_plan *plan, const char *me)
+{
+    if (plan->d_interp) return SM_OK;
+    void *b = nullptr;
+    const hipError_t e = hipMalloc(&b, itp_bytes(plan));
+    if (e != hipSuccess)
+        return sm_fail(e == hipErrorOutOfMemory ? SM_ERR_NOMEM : SM_ERR_HIP, "%s: %zu bytes for the directional maps and "
+                       "carries of the interpolation: %s", me, itp_bytes(plan), hipGetErrorString(e));
+    plan->d_interp = (i32 *)b;
+    return SM_OK;
+}
+
+extern "C" int sm_plan_reserve_interp(sm_plan *plan)
+{
+    if (!plan) return sm_fail(SM_ERR_ARG, "sm_plan_reserve_interp: plan is NULL");
+    SM_TRY(sm_use_device(plan->device));
+    return reserve_interp(plan, "sm_plan_reserve_interp");
+}
+
+template <typename T>
+static int interp_launch(const sm_plan *plan, const T *in, const u8 *cls, T *out, int pairs, i32 *filled, hipStream_t st)
+{
+    const int W = plan->width, H = plan->height, segs = itp_segs(plan), chunks = itp_chunks(plan);
+    T *loc = (T *)plan->d_interp;
+    i32 *car = plan->d_interp + plan->max_pairs * itp_loc_elems(plan);
+    i32 *rows = car + plan->max_pairs * itp_car_elems(plan);
+    const unsigned items = (unsigned)H * chunks, lines = W + H - 1;
+    if (filled) {
+        hipLaunchKernelGGL(k_lr_zero_counts, dim3((pairs + 63) / 64), dim3(64), 0, st, filled, pairs);
+        SM_LAUNCH_CHECK("k_lr_zero_counts");
+    }
+    hipLaunchKernelGGL(k_itp_rowsum<T>, dim3((items + 3) / 4, pairs), dim3(256), 0, st, in, rows, W, H, chunks);
+    SM_LAUNCH_CHECK("k_itp_rowsum");
+    hipLaunchKernelGGL(k_itp_rowscan, dim3((H + 3) / 4, pairs), dim3(256), 0, st, rows, H, chunks);
+    SM_LAUNCH_CHECK("k_itp_rowscan");
+    hipLaunchKernelGGL(k_itp_sweep<T>, dim3((lines + 255) / 256, segs, 6 * pairs), dim3(256), 0, st, in, loc, car, W, H,
+                       segs);
+    SM_LAUNCH_CHECK("k_itp_sweep");
+    hipLaunchKernelGGL(k_itp_resolve, dim3((lines + 255) / 256, 6, pairs), dim3(256), 0, st, car, W, H, segs);
+    SM_LAUNCH_CHECK("k_itp_resolve");
+    hipLaunchKernelGGL(k_itp_combine<T>, dim3(std::min((items + 3) / 4, (unsigned)SM_LR_BLOCKS), pairs), dim3(256), 0, st,
+                       in, cls, out, (const T *)loc, (const i32 *)car, (const i32 *)rows, filled, W, H, segs, chunks);
+    SM_LAUNCH_CHECK("k_itp_combine");
+    return SM_OK;
+}
+
+extern "C" int sm_interpolate(sm_plan *plan, const void *d_in, int map_type, const uint8_t *d_class, int pairs,
+                              void *d_out, int32_t *d_filled, void *stream)
+{
+    const char *me = "sm_interpolate";
+    size_t elem;
+    if (!d_in || !d_out) return sm_fail(SM_ERR_ARG, "%s: a map pointer is NULL", me);
+    SM_TRY(filter_map_type(map_type, me, &elem));
+    SM_TRY(check_pairs(plan, pairs, me));
+    const size_t px = (size_t)pairs * plan->width * plan->height, map = px * elem;
+    if (overlap(d_in, d_out, map))
+        return sm_fail(SM_ERR_ARG, "%s: maps overlap (every candidate is read from the input)", me);
+    if (d_class && overlap(d_class, d_out, px, map)) return sm_fail(SM_ERR_ARG, "%s: d_class overlaps d_out", me);
+    const size_t counts = (size_t)pairs * sizeof(i32);
+    if (d_filled && (overlap(d_filled, d_in, counts, map) || overlap(d_filled, d_out, counts, map) ||
+                     (d_class && overlap(d_filled, d_class, counts, px))))
+        return sm_fail(SM_ERR_ARG, "%s: d_filled overlaps a map", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (!plan->d_interp) {
+        if (sm_stream_capturing(st))
+            return sm_fail(SM_ERR_ARG, "%s: the workspace of the interpolation is not allocated and the stream is capturing "
+                           "(an allocation cannot be captured): call sm_plan_reserve_interp(plan) first", me);
+        SM_TRY(reserve_interp(plan, me));
+    }
+    if (map_type == SM_MAP_I32)
+        return interp_launch<i32>(plan, (const i32 *)d_in, d_class, (i32 *)d_out, pairs, d_filled, st);
+    return interp_launch<int16_t>(plan, (const int16_t *)d_in, d_class, (int16_t *)d_out, pairs, d_filled, st);
 }

@@ -555,6 +555,40 @@ class StereoPlan:
         check(lib.sm_sub_mask(self._h, _ptr(web), _ptr(sub), web.shape[0], self._stream()))
         return sub
 
+    # ---- occlusion-aware interpolation (between the post-filters and step 3) -----
+    def reserve_interp(self):
+        """The interpolation's workspace (six directional maps and the carries of their sweeps for max_pairs maps),
+        allocated now: keeps the allocation out of timed paths and out of stream captures."""
+        check(lib.sm_plan_reserve_interp(self._h))
+
+    def occlusion_classify(self, web, web_right, out=None):
+        """Class of every pixel of a checked web map (sm_occlusion_classify) -> uint8 tensor: 0 valid, 1 occluded, 2
+        mismatched (the pixel's line of sight meets the right-reference map web_right of the check)."""
+        web = self._images(web, torch.int32, "web")
+        web_right = self._images(web_right, torch.int32, "web_right")
+        pairs = web.shape[0]
+        if web_right.shape[0] != pairs:
+            raise ValueError(f"web_right: {web_right.shape[0]} maps for {pairs} pairs")
+        out = self._out(out, pairs, "out", torch.uint8)
+        check(lib.sm_occlusion_classify(self._h, _ptr(web), _ptr(web_right), pairs, _ptr(out), self._stream()))
+        return out
+
+    def interpolate(self, maps, cls=None, want_filled=False, out=None):
+        """Discontinuity-preserving fill (sm_interpolate) of the 0s of an int32 web map or an int16 sub map -> the
+        filled map, or (map, filled pixels per pair) with want_filled: an invalid pixel takes the second lowest of the
+        first valid values met along the eight directions where cls is 1 (occluded), else their lower median."""
+        maps = self._filter_map(maps, "maps")
+        pairs = maps.shape[0]
+        if cls is not None:
+            cls = self._images(cls, torch.uint8, "cls")
+            if cls.shape[0] != pairs:
+                raise ValueError(f"cls: {cls.shape[0]} maps for {pairs} pairs")
+        out = self._out(out, pairs, "out", maps.dtype)
+        filled = torch.empty(pairs, dtype=torch.int32, device=self._dev) if want_filled else None
+        check(lib.sm_interpolate(self._h, _ptr(maps), MAP_TYPES[maps.dtype], _ptr(cls), pairs, _ptr(out), _ptr(filled),
+                                 self._stream()))
+        return (out, filled) if want_filled else out
+
     def debug_planes(self, pair: int, shift: int):
         """matches-i, score_all-i, scores-i of the reference's debug build."""
         m = torch.empty((self.height, self.width), dtype=torch.uint8, device=self._dev)
