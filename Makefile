@@ -52,7 +52,7 @@ $(DEVSTAMP): FORCE
 	@mkdir -p $(dir $@)
 	@if [ "$$(cat $@ 2>/dev/null)" != "$(HIPFLAGS_BARE)" ]; then rm -f $(dir $@)*.o; echo "$(HIPFLAGS_BARE)" > $@; fi
 FORCE:
-stereomatching_amd/obj/product/%.o: $(CSRC)/%.hip $(CSRC)/sm_internal.h $(CSRC)/sm_match_bs_kernel.h $(CSRC)/sm_cost.h $(CSRC)/sm_sgm.h $(CSRC)/sm_filter.h $(CSRC)/sm_interp.h include/stereo_hip.h $(DEVSTAMP)
+stereomatching_amd/obj/product/%.o: $(CSRC)/%.hip $(CSRC)/sm_internal.h $(CSRC)/sm_match_bs_kernel.h $(CSRC)/sm_cost.h $(CSRC)/sm_sgm.h $(CSRC)/sm_filter.h $(CSRC)/sm_interp.h $(CSRC)/sm_rectify.h include/stereo_hip.h $(DEVSTAMP)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(DEVLIB): $(DEVOBJ)
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC $^ -o $@

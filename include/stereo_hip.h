@@ -609,6 +609,67 @@ int sm_interpolate(sm_plan *plan, const void *d_in, int map_type, const uint8_t 
 /* adds: allocates sm_interpolate's workspace now; idempotent */
 int sm_plan_reserve_interp(sm_plan *plan);
 
+/* ---- rectification: PARITY UNPINNED -------------------------------------- *
+ * New work (no reference counterpart): the stage in FRONT of the matchers.  Every matcher searches along
+ * the image row, which is right on a rectified pair only; these calls make one from raw camera images and a
+ * calibration: map build (once) -> rectify (every frame) -> any matcher -> valid mask -> filters / interpolation.
+ * The rectified images are the plan's W x H; the raw images are src_w x src_h, given per call, tightly packed u8.
+ *   map: tells every destination pixel where to read in the source, in fixed point with SM_RMAP_FRAC_BITS fraction
+ *     bits (1/32 pixel).  SM_RMAP_ABS32: [H][W][2] int32 (mx, my), the source position times 32; any int32 value is
+ *     legal.  SM_RMAP_REL16: [H][W][2] int16 (dx, dy) with mx = 32 x + dx, my = 32 y + dy: half the bytes,
+ *     displacements of up to +-1023 pixels.  A map pointer is aligned to its element (4 or 2 bytes).
+ *   remap, per destination pixel, exact integer arithmetic: x0 = mx >> 5 (arithmetic: floor), fx = mx & 31, likewise
+ *     y0, fy.  tap(i, j) = src(x0 + i, y0 + j) if 0 <= x0 + i < src_w and 0 <= y0 + j < src_h, else `border`
+ *     (0 .. 255).  Nothing wraps, in either border mode of the plan.
+ *     SM_INTERP_BILINEAR: w00 = (32-fx)(32-fy), w10 = fx (32-fy), w01 = (32-fx) fy, w11 = fx fy (sum 1024);
+ *       out = (sum of w_ij tap(i, j) + 512) >> 10.
+ *     SM_INTERP_NEAREST: out = the one tap at (floor((mx + 16) / 32), floor((my + 16) / 32)), same border rule.
+ *     validity (optional, one u8 image per side): 1 iff every tap whose weight is not 0 lies inside the source
+ *     (nearest: the one tap), else 0.  The identity map is valid everywhere.
+ *   one sm_rectify call does both sides of `pairs` pairs: raw left / right [pairs][src_h][src_w], one map per SIDE
+ *     shared by all pairs (the two map pointers may be equal), rectified left / right [pairs][H][W], validity
+ *     [pairs][H][W] per side or NULL.  Outputs must not overlap inputs or one another.
+ *   map build, from one side's calibration (sm_rectify_calib: camera matrix fx, fy, cx, cy; Brown-Conrady distortion
+ *     k1, k2, p1, p2, k3 in OpenCV's order; rectifying rotation R; new projection new_fx, new_fy, new_cx, new_cy),
+ *     IEEE double, every operation rounded on its own, in this order, for destination pixel (x, y):
+ *       xn = (x - new_cx) / new_fx, yn = (y - new_cy) / new_fy;
+ *       X = R00 xn + R10 yn + R20, Y = R01 xn + R11 yn + R21, Z = R02 xn + R12 yn + R22 (R transposed; left to right);
+ *       a = X / Z, b = Y / Z; r2 = a a + b b; rad = 1 + r2 (k1 + r2 (k2 + r2 k3));
+ *       ad = a rad + (((2 p1) a) b + p2 (r2 + (2 a) a)), bd = b rad + (p1 (r2 + (2 b) b) + ((2 p2) a) b);
+ *       u = fx ad + cx, v = fy bd + cy; mx = floor(u 32 + 0.5), my = floor(v 32 + 0.5), saturated to int32;
+ *       a non-finite u or v (Z = 0) gives mx = my = INT32_MIN (far outside: border).
+ *     SM_RMAP_REL16 is refused with SM_ERR_ARG, and a message naming SM_RMAP_ABS32 as the remedy, if a displacement
+ *     does not fit int16; d_map then holds no map.  The builder reads that flag back: it SYNCHRONISES `stream`,
+ *     allocates and frees four bytes, and CANNOT BE CAPTURED (refused with SM_ERR_ARG, the capture left valid).
+ *   valid mask: d_map = 0 where d_valid = 0, else unchanged, in place, on an SM_MAP_I32 web map or an SM_MAP_I16 sub
+ *     map [pairs][H][W]: the wedges a rectification leaves empty become 0s, which the check, the filters,
+ *     sm_interpolate and step 3 treat as "invalid".
+ * Arguments are checked before any device call; a refusal names the function.  All calls run in `stream` order and
+ * use nothing the pipelined lanes use.  None needs workspace: a plan that rectifies reports the same
+ * sm_plan_workspace_bytes.  STREAM CAPTURE: sm_rectify and sm_valid_mask always; sm_rectify_map_build never.   */
+#define SM_RMAP_FRAC_BITS 5
+#define SM_RMAP_ABS32 0
+#define SM_RMAP_REL16 1
+#define SM_INTERP_BILINEAR 0
+#define SM_INTERP_NEAREST 1
+typedef struct sm_rectify_calib {
+    int struct_size;            /* sizeof(sm_rectify_calib) as the caller compiled it; a shorter struct is refused (every
+                                 * field is needed), of a longer (newer) one the fields this library knows are taken */
+    int reserved;               /* 0 */
+    double fx, fy, cx, cy;      /* camera matrix of the raw image */
+    double k1, k2, p1, p2, k3;  /* distortion */
+    double R[3][3];             /* rectifying rotation, row-major (OpenCV's R1 / R2) */
+    double new_fx, new_fy, new_cx, new_cy;   /* projection of the rectified image (OpenCV's P1 / P2, left 3 x 3) */
+} sm_rectify_calib;
+/* adds: rectified left / right images (and validity) of raw pairs through one map per side */
+int sm_rectify(sm_plan *plan, const uint8_t *d_raw_left, const uint8_t *d_raw_right, int src_w, int src_h,
+               const void *d_map_left, const void *d_map_right, int map_format, int interp, int border, int pairs,
+               uint8_t *d_left, uint8_t *d_right, uint8_t *d_valid_left, uint8_t *d_valid_right, void *stream);
+/* adds: the W x H map of one side's calibration, in either format, on the device; synchronises, not capturable */
+int sm_rectify_map_build(sm_plan *plan, const sm_rectify_calib *calib, int map_format, void *d_map, void *stream);
+/* adds: d_map = 0 where d_valid = 0, in place */
+int sm_valid_mask(sm_plan *plan, void *d_map, int map_type, const uint8_t *d_valid, int pairs, void *stream);
+
 /* ---- step 3 -------------------------------------------------------------- *
  * fill_web_holes (src/stereo.cu:235-256): every pixel that is 0 becomes the
  * truncated mean of its four flat-index neighbours.  The reference's pointer

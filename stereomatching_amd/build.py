@@ -22,7 +22,7 @@ LIB = PKG / "libstereo_hip.so"
 SOURCES = ["sm_match_bs_ds8.hip", "sm_match_bs.hip", "sm_match_bs_duo8.hip", "sm_match_bs_duo.hip", "sm_match_bs_ds4.hip",
            "sm_api.hip", "sm_match.hip", "sm_cost.hip", "sm_cost_qs.hip", "sm_cost_pc.hip", "sm_cost_mfma.hip", "sm_cost_strip.hip", "sm_gather.hip", "sm_lr.hip",
            "sm_subpix.hip", "sm_census.hip"]
-HEADERS = [CSRC / "sm_internal.h", CSRC / "sm_match_bs_kernel.h", CSRC / "sm_cost.h", CSRC / "sm_sgm.h", CSRC / "sm_filter.h", CSRC / "sm_interp.h", ROOT / "include" / "stereo_hip.h"]
+HEADERS = [CSRC / "sm_internal.h", CSRC / "sm_match_bs_kernel.h", CSRC / "sm_cost.h", CSRC / "sm_sgm.h", CSRC / "sm_filter.h", CSRC / "sm_interp.h", CSRC / "sm_rectify.h", ROOT / "include" / "stereo_hip.h"]
 OBJDIR = PKG / "obj"
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",

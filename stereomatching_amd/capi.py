@@ -21,6 +21,11 @@ SM_TOROIDAL, SM_GHOST = 0, 1
 SM_WEB_I32, SM_WEB_U16, SM_WEB_U8 = 0, 1, 2
 SM_MAP_I32, SM_MAP_I16 = 0, 1
 SM_CLASS_VALID, SM_CLASS_OCCLUDED, SM_CLASS_MISMATCHED = 0, 1, 2
+SM_RMAP_FRAC_BITS = 5
+SM_RMAP_ABS32, SM_RMAP_REL16 = 0, 1
+SM_INTERP_BILINEAR, SM_INTERP_NEAREST = 0, 1
+RMAP_FORMATS = {"abs32": SM_RMAP_ABS32, "rel16": SM_RMAP_REL16}
+INTERPS = {"bilinear": SM_INTERP_BILINEAR, "nearest": SM_INTERP_NEAREST}
 BORDERS = {"toroidal": SM_TOROIDAL, "ghost": SM_GHOST}
 
 
@@ -61,6 +66,28 @@ class PlanOptions(C.Structure):
     @classmethod
     def make(cls, **kw):
         o = cls(**kw)
+        o.struct_size = C.sizeof(cls)
+        return o
+
+
+class RectifyCalib(C.Structure):
+    """sm_rectify_calib of include/stereo_hip.h: one side's camera matrix, distortion (k1, k2, p1, p2, k3), rectifying
+    rotation R (row-major) and the projection of the rectified image"""
+    _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int)] + \
+               [(n, C.c_double) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")] + \
+               [("R", C.c_double * 3 * 3)] + [(n, C.c_double) for n in ("new_fx", "new_fy", "new_cx", "new_cy")]
+
+    @classmethod
+    def make(cls, fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0, R=None, new_fx=None, new_fy=None,
+             new_cx=None, new_cy=None):
+        """R: None (identity) or 3 x 3 numbers; the new projection defaults to the camera matrix"""
+        o = cls(fx=fx, fy=fy, cx=cx, cy=cy, k1=k1, k2=k2, p1=p1, p2=p2, k3=k3,
+                new_fx=fx if new_fx is None else new_fx, new_fy=fy if new_fy is None else new_fy,
+                new_cx=cx if new_cx is None else new_cx, new_cy=cy if new_cy is None else new_cy)
+        rows = ((1, 0, 0), (0, 1, 0), (0, 0, 1)) if R is None else R
+        for i in range(3):
+            for j in range(3):
+                o.R[i][j] = float(rows[i][j])
         o.struct_size = C.sizeof(cls)
         return o
 
@@ -144,6 +171,9 @@ _SIGNATURES = {
     "sm_occlusion_classify": (_int, [_vp, _vp, _vp, _int, _vp, _vp]),
     "sm_interpolate": (_int, [_vp, _vp, _int, _vp, _int, _vp, _vp, _vp]),
     "sm_plan_reserve_interp": (_int, [_vp]),
+    "sm_rectify": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    "sm_rectify_map_build": (_int, [_vp, C.POINTER(RectifyCalib), _int, _vp, _vp]),
+    "sm_valid_mask": (_int, [_vp, _vp, _int, _vp, _int, _vp]),
 }
 
 

@@ -589,6 +589,77 @@ class StereoPlan:
                                  self._stream()))
         return (out, filled) if want_filled else out
 
+    # ---- rectification (in front of the matchers) --------------------------------
+    def _rectify_map(self, t, name):
+        """-> (map, format): [H][W][2] int32 (abs32) or int16 (rel16), contiguous, on the plan's device"""
+        fmts = {torch.int32: capi.SM_RMAP_ABS32, torch.int16: capi.SM_RMAP_REL16}
+        if t.dtype not in fmts:
+            raise ValueError(f"{name}: need an int32 (abs32) or int16 (rel16) map, got {t.dtype}")
+        if t.device != self._dev or not t.is_contiguous():
+            raise ValueError(f"{name}: need a contiguous tensor on {self._dev}, got one on {t.device}")
+        if tuple(t.shape) != (self.height, self.width, 2):
+            raise ValueError(f"{name}: shape {tuple(t.shape)} is not ({self.height}, {self.width}, 2)")
+        return t, fmts[t.dtype]
+
+    def rectify_map(self, calibration, fmt="rel16", out=None):
+        """The W x H map of one side's calibration (sm_rectify_map_build) -> device tensor [H][W][2], int16 for
+        fmt="rel16" (refused where a displacement exceeds 1023 pixels: use "abs32"), int32 for "abs32".
+        calibration: a capi.RectifyCalib or a dict of RectifyCalib.make's arguments.  Synchronises; not capturable."""
+        if fmt not in capi.RMAP_FORMATS:
+            raise ValueError(f"fmt: {fmt!r} is not one of {sorted(capi.RMAP_FORMATS)}")
+        calib = calibration if isinstance(calibration, capi.RectifyCalib) else capi.RectifyCalib.make(**calibration)
+        dtype = torch.int16 if fmt == "rel16" else torch.int32
+        if out is None:
+            out = torch.empty((self.height, self.width, 2), dtype=dtype, device=self._dev)
+        out, _ = self._rectify_map(out, "out")
+        if out.dtype != dtype:
+            raise ValueError(f"out: {out.dtype} is not the {dtype} of a {fmt} map")
+        check(lib.sm_rectify_map_build(self._h, C.byref(calib), capi.RMAP_FORMATS[fmt], _ptr(out), self._stream()))
+        return out
+
+    def rectify(self, raw_left, raw_right, map_left, map_right, interp="bilinear", border=0, want_valid=False,
+                left=None, right=None):
+        """Rectified images of raw pairs (sm_rectify) -> (left, right), or (left, right, valid_left, valid_right) with
+        want_valid.  raw_*: uint8 [pairs][src_h][src_w] (or one [src_h][src_w] image) of any size; map_*: one map per
+        side (rectify_map, or any [H][W][2] int32 / int16 tensor), both of one format; a tap outside the raw image
+        reads `border`; valid_* is 1 where every tap that counts lay inside."""
+        if interp not in capi.INTERPS:
+            raise ValueError(f"interp: {interp!r} is not one of {sorted(capi.INTERPS)}")
+        raws = []
+        for t, name in ((raw_left, "raw_left"), (raw_right, "raw_right")):
+            if t.device != self._dev or t.dtype != torch.uint8 or not t.is_contiguous():
+                raise ValueError(f"{name}: need a contiguous {torch.uint8} tensor on {self._dev}, "
+                                 f"got {t.dtype} on {t.device}")
+            t = t.unsqueeze(0) if t.dim() == 2 else t
+            if t.dim() != 3 or t.shape[1] < 1 or t.shape[2] < 1:
+                raise ValueError(f"{name}: shape {tuple(t.shape)} is not (pairs, src_h, src_w)")
+            raws.append(t)
+        if raws[0].shape != raws[1].shape:
+            raise ValueError(f"raw_right: shape {tuple(raws[1].shape)} is not raw_left's {tuple(raws[0].shape)}")
+        pairs, src_h, src_w = raws[0].shape
+        map_left, fmt = self._rectify_map(map_left, "map_left")
+        map_right, fmt_r = self._rectify_map(map_right, "map_right")
+        if fmt != fmt_r:
+            raise ValueError(f"map_right: {map_right.dtype} is not map_left's {map_left.dtype}")
+        left = self._out(left, pairs, "left", torch.uint8)
+        right = self._out(right, pairs, "right", torch.uint8)
+        vl = self._new(pairs, torch.uint8) if want_valid else None
+        vr = self._new(pairs, torch.uint8) if want_valid else None
+        check(lib.sm_rectify(self._h, _ptr(raws[0]), _ptr(raws[1]), src_w, src_h, _ptr(map_left), _ptr(map_right), fmt,
+                             capi.INTERPS[interp], int(border), pairs, _ptr(left), _ptr(right), _ptr(vl), _ptr(vr),
+                             self._stream()))
+        return (left, right, vl, vr) if want_valid else (left, right)
+
+    def valid_mask(self, map, valid):
+        """map = 0 where valid = 0, in place (sm_valid_mask) -> map: an int32 web map or an int16 sub map follows the
+        validity image rectify returns."""
+        map = self._filter_map(map, "map")
+        valid = self._images(valid, torch.uint8, "valid")
+        if valid.shape[0] != map.shape[0]:
+            raise ValueError(f"valid: {valid.shape[0]} images for {map.shape[0]} maps")
+        check(lib.sm_valid_mask(self._h, _ptr(map), MAP_TYPES[map.dtype], _ptr(valid), map.shape[0], self._stream()))
+        return map
+
     def debug_planes(self, pair: int, shift: int):
         """matches-i, score_all-i, scores-i of the reference's debug build."""
         m = torch.empty((self.height, self.width), dtype=torch.uint8, device=self._dev)
