@@ -21,8 +21,8 @@ LIB = PKG / "libstereo_hip.so"
 # compile side by side (one unit: ~2 min; four beside the rest: ~50 s on 8 cores)
 SOURCES = ["sm_match_bs_ds8.hip", "sm_match_bs.hip", "sm_match_bs_duo8.hip", "sm_match_bs_duo.hip", "sm_match_bs_ds4.hip",
            "sm_api.hip", "sm_match.hip", "sm_cost.hip", "sm_cost_qs.hip", "sm_cost_pc.hip", "sm_cost_mfma.hip", "sm_cost_strip.hip", "sm_gather.hip", "sm_lr.hip",
-           "sm_subpix.hip", "sm_census.hip"]
-HEADERS = [CSRC / "sm_internal.h", CSRC / "sm_match_bs_kernel.h", CSRC / "sm_cost.h", CSRC / "sm_sgm.h", CSRC / "sm_filter.h", CSRC / "sm_interp.h", CSRC / "sm_rectify.h", ROOT / "include" / "stereo_hip.h"]
+           "sm_subpix.hip", "sm_census.hip", "sm_sgm.hip", "sm_filter.hip", "sm_interp.hip", "sm_rectify.hip"]
+HEADERS = [CSRC / "sm_internal.h", CSRC / "sm_match_bs_kernel.h", CSRC / "sm_cost.h", CSRC / "sm_device.h", ROOT / "include" / "stereo_hip.h"]
 OBJDIR = PKG / "obj"
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
@@ -52,7 +52,8 @@ def _stale(target: Path, deps) -> bool:
 
 def _jobs() -> int:
     env = os.environ.get("SM_BUILD_JOBS")
-    return max(1, int(env)) if env else max(1, min(len(SOURCES), os.cpu_count() or 1))
+    # at most 16 compilers side by side, however many sources and cores there are
+    return max(1, int(env)) if env else max(1, min(len(SOURCES), os.cpu_count() or 1, 16))
 
 
 def _compile_and_link(out: Path, objdir: Path, flags=(), verbose: bool = False, jobs: int | None = None) -> None:

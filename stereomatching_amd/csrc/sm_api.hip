@@ -7,6 +7,7 @@
 
 #include <limits.h>
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
@@ -913,7 +914,6 @@ extern "C" int sm_plan_create_ex(int device, int width, int height, int num_shif
             if (p->ev_fork[b]) (void)hipEventDestroy(p->ev_fork[b]);
         if (p->d_flags) (void)hipFree(p->d_flags);
         if (p->d_edge_tab) (void)hipFree(p->d_edge_tab);
-        if (p->d_web_tmp) (void)hipFree(p->d_web_tmp);
         if (p->h_flags) (void)hipHostFree(p->h_flags);
         free(p);
         return sm_fail(e == hipErrorOutOfMemory ? SM_ERR_NOMEM : SM_ERR_HIP,
@@ -942,25 +942,105 @@ extern "C" int sm_plan_create_ex(int device, int width, int height, int num_shif
     return SM_OK;
 }
 
-// the int32 staging map of narrow results for the kernels that have no narrow store path
-static int reserve_narrow(sm_plan *plan, const char *me)
+// ---------------------------------------------------------------------------
+// the lazily allocated workspaces (sm_internal.h): the table, and the four functions on it
+// ---------------------------------------------------------------------------
+
+size_t sm_lr_map_bytes(const sm_plan *plan) { return (size_t)plan->max_pairs * plan->width * plan->height * sizeof(i32); }
+size_t sm_lr_gray_batch_bytes(const sm_plan *plan)
 {
-    if (plan->d_web_tmp || plan->kernel == SM_KERNEL_BS) return SM_OK;
-    const size_t bytes = (size_t)plan->max_pairs * plan->width * plan->height * sizeof(i32);
-    const hipError_t e = hipMalloc((void **)&plan->d_web_tmp, bytes);
-    if (e != hipSuccess) {
-        plan->d_web_tmp = nullptr;
-        return sm_fail(e == hipErrorOutOfMemory ? SM_ERR_NOMEM : SM_ERR_HIP,
-                       "%s: %zu bytes for the int32 staging map of narrow results: %s", me, bytes, hipGetErrorString(e));
+    return ((size_t)plan->max_pairs * plan->width * plan->height + 255) & ~(size_t)255;
+}
+// (the bit-sliced kernel stores narrow maps itself: its plans never need the staging map)
+static size_t ws_narrow_bytes(const sm_plan *plan) { return plan->kernel == SM_KERNEL_BS ? 0 : sm_lr_map_bytes(plan); }
+static size_t ws_ext_bytes(const sm_plan *plan) { return plan->ext_bytes; }
+static size_t ws_gray_bytes(const sm_plan *plan) { return 2 * sm_lr_gray_batch_bytes(plan); }
+static size_t ws_census_bytes(const sm_plan *plan)      // both images of max_pairs pairs, 8 bytes a descriptor
+{
+    return (size_t)2 * plan->max_pairs * plan->width * plan->height * sizeof(uint64_t);
+}
+static size_t ws_filter_bytes(const sm_plan *plan) { return 2 * sm_lr_map_bytes(plan); }
+
+static const struct {
+    size_t member;                          // offsetof(sm_plan, the pointer)
+    size_t (*bytes)(const sm_plan *);
+    bool zero;                              // filled with zeros when allocated
+    const char *what;
+} ws_rows[SM_WS_ROWS] = {
+    /* SM_WS_NARROW  */ {offsetof(sm_plan, d_web_tmp), ws_narrow_bytes, false, "int32 staging map of narrow results"},
+    // (zero-filled: the words beyond each side's row extent stay zero, as in the plan's own images)
+    /* SM_WS_EXT_LR  */ {offsetof(sm_plan, d_ext_lr), ws_ext_bytes, true, "mirrored images of the consistency check"},
+    /* SM_WS_WEB_LR  */ {offsetof(sm_plan, d_web_lr), sm_lr_map_bytes, false, "map of the consistency check"},
+    /* SM_WS_GRAY_LR */ {offsetof(sm_plan, d_gray_lr), ws_gray_bytes, false, "mirrored gray images of the consistency check"},
+    /* SM_WS_CENSUS  */ {offsetof(sm_plan, d_census), ws_census_bytes, false, "census descriptors"},
+    /* SM_WS_SGM     */ {offsetof(sm_plan, d_sgm), sm_sgm_volume_bytes, false, "SGM volumes"},
+    /* SM_WS_FILTER  */ {offsetof(sm_plan, d_filter), ws_filter_bytes, false, "labels and sizes of the speckle filter"},
+    /* SM_WS_INTERP  */ {offsetof(sm_plan, d_interp), sm_itp_bytes, false, "directional maps and carries of the interpolation"},
+};
+
+static void *&ws_ptr(const sm_plan *plan, int r) { return *(void **)((char *)plan + ws_rows[r].member); }
+
+// the rows of `set` (and of the sets before it) that this plan needs and does not have
+static unsigned ws_missing(const sm_plan *plan, const sm_ws_set &set)
+{
+    unsigned m = set.first ? ws_missing(plan, *set.first) : 0;
+    for (int r = 0; r < SM_WS_ROWS; r++)
+        if ((set.rows >> r & 1) && !ws_ptr(plan, r) && ws_rows[r].bytes(plan)) m |= 1u << r;
+    return m;
+}
+
+int sm_ws_reserve(sm_plan *plan, const sm_ws_set &set, const char *me)
+{
+    if (set.first) SM_TRY(sm_ws_reserve(plan, *set.first, me));
+    const unsigned todo = ws_missing(plan, set);
+    for (int r = 0; r < SM_WS_ROWS; r++) {
+        if (!(todo >> r & 1)) continue;
+        const size_t bytes = ws_rows[r].bytes(plan);
+        hipError_t e = hipMalloc(&ws_ptr(plan, r), bytes);
+        if (e != hipSuccess) ws_ptr(plan, r) = nullptr;
+        else if (ws_rows[r].zero) e = hipMemset(ws_ptr(plan, r), 0, bytes);
+        if (e == hipSuccess) continue;
+        for (int q = 0; q <= r; q++)
+            if ((todo >> q & 1) && ws_ptr(plan, q)) {
+                (void)hipFree(ws_ptr(plan, q));
+                ws_ptr(plan, q) = nullptr;
+            }
+        return sm_fail(e == hipErrorOutOfMemory ? SM_ERR_NOMEM : SM_ERR_HIP, "%s: %zu bytes for the %s: %s", me, bytes,
+                       ws_rows[r].what, hipGetErrorString(e));
     }
     return SM_OK;
+}
+
+int sm_ws_need(sm_plan *plan, const sm_ws_set &set, hipStream_t st, const char *me)
+{
+    if (!ws_missing(plan, set)) return SM_OK;
+    if (sm_stream_capturing(st))
+        return sm_fail(SM_ERR_ARG, "%s: the workspace of %s is not allocated and the stream is capturing (an allocation "
+                       "cannot be captured): call %s(plan) first", me, set.what, set.reserve);
+    return sm_ws_reserve(plan, set, me);
+}
+
+size_t sm_ws_bytes(const sm_plan *plan)
+{
+    size_t sum = 0;
+    for (int r = 0; r < SM_WS_ROWS; r++)
+        if (ws_ptr(plan, r)) sum += ws_rows[r].bytes(plan);
+    return sum;
+}
+
+void sm_ws_free(sm_plan *plan)
+{
+    for (int r = 0; r < SM_WS_ROWS; r++) {
+        if (ws_ptr(plan, r)) (void)hipFree(ws_ptr(plan, r));
+        ws_ptr(plan, r) = nullptr;
+    }
 }
 
 extern "C" int sm_plan_reserve_narrow(sm_plan *plan)
 {
     if (!plan) return sm_fail(SM_ERR_ARG, "sm_plan_reserve_narrow: plan is NULL");
     SM_TRY(use_device(plan->device));
-    return reserve_narrow(plan, "sm_plan_reserve_narrow");
+    return sm_ws_reserve(plan, SM_WS_SET_NARROW, "sm_plan_reserve_narrow");
 }
 
 extern "C" void sm_plan_destroy(sm_plan *plan)
@@ -976,9 +1056,7 @@ extern "C" void sm_plan_destroy(sm_plan *plan)
     for (int q = 0; q < 4; q++) (void)hipEventDestroy(plan->ev_free[q]);
     (void)hipEventDestroy(plan->ev_inputs);
     for (int b = 0; b < 2; b++) (void)hipEventDestroy(plan->ev_fork[b]);
-    if (plan->d_web_tmp) (void)hipFree(plan->d_web_tmp);
-    sm_lr_free(plan);
-    sm_census_free(plan);
+    sm_ws_free(plan);
     (void)hipFree(plan->d_flags);
     (void)hipFree(plan->d_edge_tab);
     (void)hipHostFree(plan->h_flags);
@@ -1025,9 +1103,7 @@ extern "C" int sm_plan_geometry(const sm_plan *plan, sm_geometry *out)
 extern "C" size_t sm_plan_workspace_bytes(const sm_plan *plan)
 {
     if (!plan) return 0;
-    const size_t staging = plan->d_web_tmp ? (size_t)plan->max_pairs * plan->width * plan->height * sizeof(i32) : 0;
-    return 2 * plan->ext_bytes + 4 * sizeof(i32) + 768 * sizeof(u32) + staging + sm_lr_workspace_bytes(plan) +
-           sm_census_workspace_bytes(plan);
+    return 2 * plan->ext_bytes + 4 * sizeof(i32) + 768 * sizeof(u32) + sm_ws_bytes(plan);
 }
 
 // synchronise `st` and return the plan's flags as they were at that point; flags in
@@ -1053,12 +1129,56 @@ static bool stream_capturing(hipStream_t st, unsigned long long *id = nullptr)
 }
 bool sm_stream_capturing(hipStream_t st) { return stream_capturing(st); }
 
-static int check_plan_pairs(const sm_plan *plan, int pairs, const char *who)
+// ---------------------------------------------------------------------------
+// argument rules shared by the entry points of every unit (sm_internal.h)
+// ---------------------------------------------------------------------------
+
+int sm_check_pairs(const sm_plan *plan, int pairs, const char *me)
 {
-    if (!plan) return sm_fail(SM_ERR_ARG, "%s: plan is NULL", who);
+    if (!plan) return sm_fail(SM_ERR_ARG, "%s: plan is NULL", me);
     if (pairs < 1 || pairs > plan->max_pairs)
-        return sm_fail(SM_ERR_ARG, "%s: pairs %d outside 1..%d (max_pairs of the plan)", who, pairs,
-                       plan->max_pairs);
+        return sm_fail(SM_ERR_ARG, "%s: pairs %d outside 1..%d (max_pairs of the plan)", me, pairs, plan->max_pairs);
+    return SM_OK;
+}
+
+int sm_check_reach(const sm_plan *plan, int max_shifts, const char *me)
+{
+    const int n = 2 * (plan->square_width / 2) + 1;
+    if (n > 25 || plan->num_shifts > max_shifts)
+        return sm_fail(SM_ERR_ARG, "%s: built for windows up to 25x25 and at most %d shifts (got %dx%d, %d)", me, max_shifts,
+                       n, n, plan->num_shifts);
+    return SM_OK;
+}
+
+int sm_check_census_width(int census_width, const char *me)
+{
+    if (census_width != 3 && census_width != 5 && census_width != 7)
+        return sm_fail(SM_ERR_ARG, "%s: census_width %d is not 3, 5 or 7", me, census_width);
+    return SM_OK;
+}
+
+int sm_check_map_type(int map_type, const char *me, size_t *elem)
+{
+    if (map_type != SM_MAP_I32 && map_type != SM_MAP_I16)
+        return sm_fail(SM_ERR_ARG, "%s: map_type %d is neither SM_MAP_I32 nor SM_MAP_I16", me, map_type);
+    *elem = map_type == SM_MAP_I32 ? sizeof(i32) : sizeof(int16_t);
+    return SM_OK;
+}
+
+int sm_check_lr_maps(const sm_plan *plan, int pairs, const int32_t *d_web, const int32_t *d_best,
+                     const int32_t *d_web_right, const int16_t *d_sub, const int32_t *d_rejected, const char *me)
+{
+    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
+    if ((d_best && overlap(d_best, d_web, map)) || (d_web_right && overlap(d_web_right, d_web, map)) ||
+        (d_best && d_web_right && overlap(d_best, d_web_right, map)) ||
+        (d_sub && (overlap(d_sub, d_web, map / 2, map) || (d_best && overlap(d_sub, d_best, map / 2, map)) ||
+                   (d_web_right && overlap(d_sub, d_web_right, map / 2, map)))))
+        return sm_fail(SM_ERR_ARG, "%s: result maps overlap", me);
+    const size_t counts = (size_t)pairs * sizeof(i32);
+    if (d_rejected && (overlap(d_rejected, d_web, counts, map) || (d_best && overlap(d_rejected, d_best, counts, map)) ||
+                       (d_web_right && overlap(d_rejected, d_web_right, counts, map)) ||
+                       (d_sub && overlap(d_rejected, d_sub, counts, map / 2))))
+        return sm_fail(SM_ERR_ARG, "%s: d_rejected overlaps a map", me);
     return SM_OK;
 }
 
@@ -1131,7 +1251,7 @@ extern "C" int sm_find_edges(sm_plan *plan, const uint8_t *d_gray_left,
                              const uint8_t *d_gray_right, double threshold, int pairs,
                              uint8_t *d_edges_left, uint8_t *d_edges_right, void *stream)
 {
-    SM_TRY(check_plan_pairs(plan, pairs, "sm_find_edges"));
+    SM_TRY(sm_check_pairs(plan, pairs, "sm_find_edges"));
     if (!d_gray_left || !d_gray_right)
         return sm_fail(SM_ERR_ARG, "sm_find_edges: input image pointer is NULL");
     if (!(threshold >= 0.0 && threshold <= 1.0))
@@ -1185,7 +1305,7 @@ extern "C" int sm_find_edges(sm_plan *plan, const uint8_t *d_gray_left,
 extern "C" int sm_load_edges(sm_plan *plan, const uint8_t *d_edges_left,
                              const uint8_t *d_edges_right, int pairs, void *stream)
 {
-    SM_TRY(check_plan_pairs(plan, pairs, "sm_load_edges"));
+    SM_TRY(sm_check_pairs(plan, pairs, "sm_load_edges"));
     if (!d_edges_left || !d_edges_right)
         return sm_fail(SM_ERR_ARG, "sm_load_edges: edge image pointer is NULL");
     SM_TRY(use_device(plan->device));
@@ -1212,7 +1332,7 @@ extern "C" int sm_match_wta_typed(sm_plan *plan, int pairs, void *d_web_any, int
                                   int32_t *d_best, void *stream)
 {
     const char *me = web_type == SM_WEB_I32 ? "sm_match_wta" : "sm_match_wta_typed";
-    SM_TRY(check_plan_pairs(plan, pairs, me));
+    SM_TRY(sm_check_pairs(plan, pairs, me));
     if (!d_web_any) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
     if (web_type != SM_WEB_I32 && web_type != SM_WEB_U16 && web_type != SM_WEB_U8)
         return sm_fail(SM_ERR_ARG, "%s: web_type %d is not SM_WEB_I32/U16/U8", me, web_type);
@@ -1226,10 +1346,7 @@ extern "C" int sm_match_wta_typed(sm_plan *plan, int pairs, void *d_web_any, int
     if (via_tmp) {
         if (!plan->d_web_tmp) {         // the first narrow request on such a plan (sm_plan_reserve_narrow keeps
             SM_TRY(use_device(plan->device));      // this allocation, which synchronises the device, out of a timed path)
-            if (stream_capturing((hipStream_t)stream))
-                return sm_fail(SM_ERR_ARG, "%s: the int32 staging map of narrow results is not allocated and the stream is "
-                               "capturing (an allocation cannot be captured): call sm_plan_reserve_narrow(plan) first", me);
-            SM_TRY(reserve_narrow(plan, me));
+            SM_TRY(sm_ws_need(plan, SM_WS_SET_NARROW, (hipStream_t)stream, me));
         }
         d_web = plan->d_web_tmp;
     }
@@ -1392,7 +1509,7 @@ extern "C" int sm_run_after(sm_plan *plan, const uint8_t *d_gray_left, const uin
                             double threshold, int pairs, void *d_web, int web_type, int32_t *d_best,
                             void *stream, void *inputs_ready_event)
 {
-    SM_TRY(check_plan_pairs(plan, pairs, "sm_run_after"));
+    SM_TRY(sm_check_pairs(plan, pairs, "sm_run_after"));
     const MatchGeom &g = plan->g;
     const long long waves = (long long)g.tiles_x * g.tiles_y * pairs * ((g.threads + 63) / 64);
     // (... and no more than 128 shifts: the edge detection the overlap hides is then a ninth of a step or more.  At 256 shifts --
@@ -1424,7 +1541,7 @@ static int run_on_lanes(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t
     // (the younger wave of every SIMD pair ends alone).  Call q - 3 (the one before q - 1
     // on the other lane) has finished before q starts: at most two calls are in flight.  `stream`
     // waits for the call's release event: work the caller puts on it afterwards sees the results.
-    SM_TRY(check_plan_pairs(plan, pairs, "sm_run"));
+    SM_TRY(sm_check_pairs(plan, pairs, "sm_run"));
     SM_TRY(use_device(plan->device));
     hipStream_t user = (hipStream_t)stream;
     unsigned long long cap_id = 0;
@@ -1438,9 +1555,7 @@ static int run_on_lanes(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t
         if (plan->timing_n < plan->timing_cap)
             return sm_fail(SM_ERR_ARG, "sm_run: kernel timing is armed (sm_plan_time_kernels) and the stream is capturing: "
                            "disarm with sm_plan_time_kernels(plan, 0) before the capture begins");
-        if (web_type != SM_WEB_I32 && plan->kernel != SM_KERNEL_BS && !plan->d_web_tmp)
-            return sm_fail(SM_ERR_ARG, "sm_run: the int32 staging map of narrow results is not allocated and the stream is "
-                           "capturing: call sm_plan_reserve_narrow(plan) first");
+        if (web_type != SM_WEB_I32) SM_TRY(sm_ws_need(plan, SM_WS_SET_NARROW, user, "sm_run"));   // (capturing: a refusal)
     }
     SM_TRY(check_run_args(plan, d_gray_left, d_gray_right, threshold, d_web, web_type, "sm_run"));
     const int b = plan->cur ^ 1;
@@ -1545,7 +1660,7 @@ extern "C" int sm_debug_edge_table(int device, double threshold, uint8_t *d_tabl
 extern "C" int sm_fill_web_holes(sm_plan *plan, int32_t *d_web, int32_t *d_tmp, int times,
                                  int pairs, int *result_in_tmp, void *stream)
 {
-    SM_TRY(check_plan_pairs(plan, pairs, "sm_fill_web_holes"));
+    SM_TRY(sm_check_pairs(plan, pairs, "sm_fill_web_holes"));
     if (!d_web || !d_tmp || !result_in_tmp)
         return sm_fail(SM_ERR_ARG, "sm_fill_web_holes: NULL argument");
     SM_TRY(use_device(plan->device));
@@ -1582,7 +1697,7 @@ static dim3 minmax_grid(long long n, int pairs)
 extern "C" int sm_min_max(sm_plan *plan, const int32_t *d_image, int pairs, int32_t *d_minmax,
                           void *stream)
 {
-    SM_TRY(check_plan_pairs(plan, pairs, "sm_min_max"));
+    SM_TRY(sm_check_pairs(plan, pairs, "sm_min_max"));
     if (!d_image || !d_minmax) return sm_fail(SM_ERR_ARG, "sm_min_max: NULL argument");
     SM_TRY(use_device(plan->device));
     hipStream_t st = (hipStream_t)stream;
@@ -1597,7 +1712,7 @@ extern "C" int sm_min_max(sm_plan *plan, const int32_t *d_image, int pairs, int3
 extern "C" int sm_draw_contour_map(sm_plan *plan, const int32_t *d_web, const int32_t *d_minmax,
                                    int num_lines, int pairs, uint8_t *d_out, void *stream)
 {
-    SM_TRY(check_plan_pairs(plan, pairs, "sm_draw_contour_map"));
+    SM_TRY(sm_check_pairs(plan, pairs, "sm_draw_contour_map"));
     if (!d_web || !d_minmax || !d_out)
         return sm_fail(SM_ERR_ARG, "sm_draw_contour_map: NULL argument");
     SM_TRY(use_device(plan->device));
@@ -1630,7 +1745,7 @@ static int run_sweeps(sm_plan *plan, i32 *d_web, i32 *d_tmp, int times, int pair
 extern "C" int sm_step3(sm_plan *plan, int32_t *d_web, int32_t *d_tmp, int times, int num_lines,
                         int pairs, int32_t *d_minmax, uint8_t *d_out, int *result_in_tmp, void *stream)
 {
-    SM_TRY(check_plan_pairs(plan, pairs, "sm_step3"));
+    SM_TRY(sm_check_pairs(plan, pairs, "sm_step3"));
     if (!d_web || !d_tmp || !d_minmax || !d_out || !result_in_tmp)
         return sm_fail(SM_ERR_ARG, "sm_step3: NULL argument");
     SM_TRY(use_device(plan->device));

@@ -27,7 +27,7 @@
 //   k_census_refine     the three window costs C(s-2), C(s-1), C(s) of each pixel, 3 n^2 taps, and sm_cost_refine's
 //                       equiangular fit.
 
-#include "sm_internal.h"
+#include "sm_device.h"
 
 typedef unsigned long long u64;
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
@@ -38,12 +38,6 @@ typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 #define SMN_DCHUNK 128     // wta: shifts per launch at most
 #define SMN_PFMAX 9        // wta: descriptors one lane fetches per ring row at most (checked by the host)
 #define SMN_THREADS 512    // wta: threads per workgroup at most
-
-__device__ __forceinline__ int smn_mod(int v, int m)
-{
-    int r = v % m;
-    return r < 0 ? r + m : r;
-}
 
 // ---------------------------------------------------------------------------
 // transform
@@ -384,12 +378,6 @@ struct CensusRefineGeom {
     long long side;
 };
 
-__device__ __forceinline__ int smn_floordiv(int num, int den)      // den > 0
-{
-    const int q = num / den;
-    return (num % den != 0 && num < 0) ? q - 1 : q;
-}
-
 template <int NW>
 __device__ __forceinline__ u32 smn_load(const u32 *img, size_t i)
 {
@@ -474,99 +462,23 @@ __global__ __launch_bounds__(256) void k_census_refine(const u32 *__restrict__ d
     }
 }
 
-// semi-global matching: the kernels
-#include "sm_sgm.h"
-
 // ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
-
-static size_t census_desc_bytes(const sm_plan *plan)
-{
-    return (size_t)2 * plan->max_pairs * plan->width * plan->height * sizeof(u64);
-}
-
-// 64, 128 or 256: the path kernel's lanes hold 1, 2 or 4 shifts each
-static int sgm_padded_shifts(const sm_plan *plan)
-{
-    return plan->num_shifts <= 64 ? 64 : plan->num_shifts <= 128 ? 128 : 256;
-}
-
-// one pair's data-term volume (u16) and aggregate volume (i32), Dp entries per pixel each
-static size_t sgm_volume_bytes(const sm_plan *plan)
-{
-    return (size_t)6 * plan->width * plan->height * sgm_padded_shifts(plan);
-}
-
-size_t sm_census_workspace_bytes(const sm_plan *plan)
-{
-    return (plan->d_census ? census_desc_bytes(plan) : 0) + (plan->d_sgm ? sgm_volume_bytes(plan) : 0);
-}
-
-void sm_census_free(sm_plan *plan)
-{
-    if (plan->d_census) (void)hipFree(plan->d_census);
-    plan->d_census = nullptr;
-    if (plan->d_sgm) (void)hipFree(plan->d_sgm);
-    plan->d_sgm = nullptr;
-}
-
-// the descriptors of both images of max_pairs pairs, and the mirrored-order map the consistency checks share (if the
-// plan has none yet); on failure neither is kept
-static int reserve_census(sm_plan *plan, const char *me)
-{
-    if (plan->d_census && plan->d_web_lr) return SM_OK;
-    if (!plan->d_census) {
-        void *b = nullptr;
-        const hipError_t e = hipMalloc(&b, census_desc_bytes(plan));
-        if (e != hipSuccess)
-            return sm_fail(e == hipErrorOutOfMemory ? SM_ERR_NOMEM : SM_ERR_HIP, "%s: %zu bytes for the census "
-                           "descriptors: %s", me, census_desc_bytes(plan), hipGetErrorString(e));
-        const int rc = sm_lr_reserve_map(plan, me);
-        if (rc) {
-            (void)hipFree(b);
-            return rc;
-        }
-        plan->d_census = (u32 *)b;
-        return SM_OK;
-    }
-    return sm_lr_reserve_map(plan, me);
-}
 
 extern "C" int sm_plan_reserve_census(sm_plan *plan)
 {
     if (!plan) return sm_fail(SM_ERR_ARG, "sm_plan_reserve_census: plan is NULL");
     SM_TRY(sm_use_device(plan->device));
-    return reserve_census(plan, "sm_plan_reserve_census");
-}
-
-static int need_census(sm_plan *plan, hipStream_t st, const char *me)
-{
-    if (plan->d_census && plan->d_web_lr) return SM_OK;
-    if (sm_stream_capturing(st))
-        return sm_fail(SM_ERR_ARG, "%s: the census workspace is not allocated and the stream is capturing (an allocation "
-                       "cannot be captured): call sm_plan_reserve_census(plan) first", me);
-    return reserve_census(plan, me);
+    return sm_ws_reserve(plan, SM_WS_SET_CENSUS, "sm_plan_reserve_census");
 }
 
 // what every census entry checks besides its pointers (before any device call)
-static int census_args(const sm_plan *plan, int census_width, int pairs, bool window, const char *me)
+static int census_args(const sm_plan *plan, int census_width, int pairs, const char *me)
 {
-    if (census_width != 3 && census_width != 5 && census_width != 7)
-        return sm_fail(SM_ERR_ARG, "%s: census_width %d is not 3, 5 or 7", me, census_width);
-    if (!plan) return sm_fail(SM_ERR_ARG, "%s: plan is NULL", me);
-    if (pairs < 1 || pairs > plan->max_pairs)
-        return sm_fail(SM_ERR_ARG, "%s: pairs %d outside 1..%d (max_pairs of the plan)", me, pairs, plan->max_pairs);
-    const int n = 2 * (plan->square_width / 2) + 1;
-    if (window && (n > 25 || plan->num_shifts > 512))
-        return sm_fail(SM_ERR_ARG, "%s: built for windows up to 25x25 and at most 512 shifts (got %dx%d, %d)", me, n, n,
-                       plan->num_shifts);
-    return SM_OK;
-}
-
-static bool overlap(const void *a, const void *b, size_t a_bytes, size_t b_bytes = 0)
-{
-    return (uintptr_t)a < (uintptr_t)b + (b_bytes ? b_bytes : a_bytes) && (uintptr_t)b < (uintptr_t)a + a_bytes;
+    SM_TRY(sm_check_census_width(census_width, me));
+    SM_TRY(sm_check_pairs(plan, pairs, me));
+    return sm_check_reach(plan, 512, me);
 }
 
 template <int CW, int NW>
@@ -594,8 +506,7 @@ static int transform_launch(const sm_plan *plan, int cw, int nw, const uint8_t *
 }
 
 // both images of `pairs` pairs into the workspace: 4-byte descriptors for c <= 5, 8-byte for c = 7
-static int census_descriptors(sm_plan *plan, int cw, const uint8_t *left, const uint8_t *right, int pairs,
-                              hipStream_t st)
+int sm_census_descriptors(sm_plan *plan, int cw, const uint8_t *left, const uint8_t *right, int pairs, hipStream_t st)
 {
     const long long side = (long long)plan->max_pairs * plan->width * plan->height;
     return transform_launch(plan, cw, cw == 7 ? 2 : 1, left, pairs, right, pairs, plan->d_census, side, st);
@@ -661,8 +572,7 @@ extern "C" int sm_census_transform(sm_plan *plan, const uint8_t *d_gray, int cen
 {
     const char *me = "sm_census_transform";
     if (!d_gray || !d_desc) return sm_fail(SM_ERR_ARG, "%s: NULL argument", me);
-    if (census_width != 3 && census_width != 5 && census_width != 7)
-        return sm_fail(SM_ERR_ARG, "%s: census_width %d is not 3, 5 or 7", me, census_width);
+    SM_TRY(sm_check_census_width(census_width, me));
     if (!plan) return sm_fail(SM_ERR_ARG, "%s: plan is NULL", me);
     if (images < 1 || images > 2 * plan->max_pairs)
         return sm_fail(SM_ERR_ARG, "%s: images %d outside 1..%d (2 * max_pairs of the plan)", me, images,
@@ -677,13 +587,13 @@ extern "C" int sm_census_wta(sm_plan *plan, const uint8_t *d_gray_left, const ui
     const char *me = "sm_census_wta";
     if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
     if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
-    SM_TRY(census_args(plan, census_width, pairs, true, me));
+    SM_TRY(census_args(plan, census_width, pairs, me));
     const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
     if (d_best && overlap(d_web, d_best, map)) return sm_fail(SM_ERR_ARG, "%s: d_web and d_best overlap", me);
     SM_TRY(sm_use_device(plan->device));
     hipStream_t st = (hipStream_t)stream;
-    SM_TRY(need_census(plan, st, me));
-    SM_TRY(census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
+    SM_TRY(sm_ws_need(plan, SM_WS_SET_CENSUS, st, me));
+    SM_TRY(sm_census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
     return wta_launch(plan, census_width, false, pairs, d_web, d_best, st);
 }
 
@@ -693,14 +603,14 @@ extern "C" int sm_census_wta_right(sm_plan *plan, const uint8_t *d_gray_left, co
     const char *me = "sm_census_wta_right";
     if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
     if (!d_web_right) return sm_fail(SM_ERR_ARG, "%s: d_web_right is NULL", me);
-    SM_TRY(census_args(plan, census_width, pairs, true, me));
+    SM_TRY(census_args(plan, census_width, pairs, me));
     const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
     if (d_best_right && overlap(d_web_right, d_best_right, map))
         return sm_fail(SM_ERR_ARG, "%s: d_web_right and d_best_right overlap", me);
     SM_TRY(sm_use_device(plan->device));
     hipStream_t st = (hipStream_t)stream;
-    SM_TRY(need_census(plan, st, me));
-    SM_TRY(census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
+    SM_TRY(sm_ws_need(plan, SM_WS_SET_CENSUS, st, me));
+    SM_TRY(sm_census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
     return wta_launch(plan, census_width, true, pairs, d_web_right, d_best_right, st);
 }
 
@@ -712,22 +622,15 @@ extern "C" int sm_census_lr(sm_plan *plan, const uint8_t *d_gray_left, const uin
     if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
     if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
     if (max_diff < 0) return sm_fail(SM_ERR_ARG, "%s: max_diff %d is negative", me, max_diff);
-    SM_TRY(census_args(plan, census_width, pairs, true, me));
-    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
-    if ((d_best && overlap(d_best, d_web, map)) || (d_web_right && overlap(d_web_right, d_web, map)) ||
-        (d_best && d_web_right && overlap(d_best, d_web_right, map)))
-        return sm_fail(SM_ERR_ARG, "%s: result maps overlap", me);
-    const size_t counts = (size_t)pairs * sizeof(i32);
-    if (d_rejected && (overlap(d_rejected, d_web, counts, map) || (d_best && overlap(d_rejected, d_best, counts, map)) ||
-                       (d_web_right && overlap(d_rejected, d_web_right, counts, map))))
-        return sm_fail(SM_ERR_ARG, "%s: d_rejected overlaps a map", me);
+    SM_TRY(census_args(plan, census_width, pairs, me));
+    SM_TRY(sm_check_lr_maps(plan, pairs, d_web, d_best, d_web_right, nullptr, d_rejected, me));
     SM_TRY(sm_use_device(plan->device));
     hipStream_t st = (hipStream_t)stream;
-    SM_TRY(need_census(plan, st, me));
+    SM_TRY(sm_ws_need(plan, SM_WS_SET_CENSUS, st, me));
     // the descriptors once for both directions; the right-reference map in natural order (the caller's, or the
     // plan's mirrored-order map used as scratch), then the check, which gathers from it
     i32 *right = d_web_right ? d_web_right : plan->d_web_lr;
-    SM_TRY(census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
+    SM_TRY(sm_census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
     SM_TRY(wta_launch(plan, census_width, false, pairs, d_web, d_best, st));
     SM_TRY(wta_launch(plan, census_width, true, pairs, right, nullptr, st));
     return sm_lr_check_natural(plan, d_web, right, d_web, d_rejected, max_diff, pairs, st);
@@ -739,11 +642,11 @@ extern "C" int sm_census_refine(sm_plan *plan, const uint8_t *d_gray_left, const
 {
     const char *me = "sm_census_refine";
     if (!d_gray_left || !d_gray_right || !d_web || !d_sub) return sm_fail(SM_ERR_ARG, "%s: NULL argument", me);
-    SM_TRY(census_args(plan, census_width, pairs, true, me));
+    SM_TRY(census_args(plan, census_width, pairs, me));
     SM_TRY(sm_use_device(plan->device));
     hipStream_t st = (hipStream_t)stream;
-    SM_TRY(need_census(plan, st, me));
-    SM_TRY(census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
+    SM_TRY(sm_ws_need(plan, SM_WS_SET_CENSUS, st, me));
+    SM_TRY(sm_census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
     CensusRefineGeom g;
     g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts;
     g.half = plan->square_width / 2; g.n = 2 * g.half + 1;
@@ -755,231 +658,5 @@ extern "C" int sm_census_refine(sm_plan *plan, const uint8_t *d_gray_left, const
     void *args[] = {(void *)&plan->d_census, (void *)&d_web, (void *)&d_sub, (void *)&d_costs, (void *)&g};
     const hipError_t e = hipLaunchKernel(fn, dim3((g.w + 63) / 64, (g.h + 3) / 4, pairs), dim3(64, 4), args, 0, st);
     if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_census_refine failed: %s", hipGetErrorString(e));
-    return SM_OK;
-}
-
-// ---------------------------------------------------------------------------
-// semi-global matching (sm_sgm.h): host
-// ---------------------------------------------------------------------------
-
-// the census workspace (descriptors, and the mirrored-order map if the plan has none yet) and one pair's volumes; on
-// failure the volumes are not kept
-static int reserve_sgm(sm_plan *plan, const char *me)
-{
-    SM_TRY(reserve_census(plan, me));
-    if (plan->d_sgm) return SM_OK;
-    void *b = nullptr;
-    const hipError_t e = hipMalloc(&b, sgm_volume_bytes(plan));
-    if (e != hipSuccess)
-        return sm_fail(e == hipErrorOutOfMemory ? SM_ERR_NOMEM : SM_ERR_HIP, "%s: %zu bytes for the SGM volumes: %s", me,
-                       sgm_volume_bytes(plan), hipGetErrorString(e));
-    plan->d_sgm = b;
-    return SM_OK;
-}
-
-extern "C" int sm_plan_reserve_sgm(sm_plan *plan)
-{
-    if (!plan) return sm_fail(SM_ERR_ARG, "sm_plan_reserve_sgm: plan is NULL");
-    SM_TRY(sm_use_device(plan->device));
-    return reserve_sgm(plan, "sm_plan_reserve_sgm");
-}
-
-static int need_sgm(sm_plan *plan, hipStream_t st, const char *me)
-{
-    if (plan->d_census && plan->d_web_lr && plan->d_sgm) return SM_OK;
-    if (sm_stream_capturing(st))
-        return sm_fail(SM_ERR_ARG, "%s: the SGM workspace is not allocated and the stream is capturing (an allocation "
-                       "cannot be captured): call sm_plan_reserve_sgm(plan) first", me);
-    return reserve_sgm(plan, me);
-}
-
-// what every SGM entry checks besides its pointers (before any device call; the checks that need no plan first)
-static int sgm_args(const sm_plan *plan, int census_width, int p1, int p2, int paths, int pairs, const char *me)
-{
-    if (census_width != 3 && census_width != 5 && census_width != 7)
-        return sm_fail(SM_ERR_ARG, "%s: census_width %d is not 3, 5 or 7", me, census_width);
-    if (paths != 4 && paths != 8) return sm_fail(SM_ERR_ARG, "%s: paths %d is not 4 or 8", me, paths);
-    if (p1 < 0 || p2 < p1 || p2 > 32767)
-        return sm_fail(SM_ERR_ARG, "%s: penalties p1 %d, p2 %d break 0 <= p1 <= p2 <= 32767", me, p1, p2);
-    if (!plan) return sm_fail(SM_ERR_ARG, "%s: plan is NULL", me);
-    if (pairs < 1 || pairs > plan->max_pairs)
-        return sm_fail(SM_ERR_ARG, "%s: pairs %d outside 1..%d (max_pairs of the plan)", me, pairs, plan->max_pairs);
-    const int n = 2 * (plan->square_width / 2) + 1;
-    if (n > 25 || plan->num_shifts > SGM_MAX_SHIFTS)
-        return sm_fail(SM_ERR_ARG, "%s: built for windows up to 25x25 and at most %d shifts (got %dx%d, %d)", me,
-                       SGM_MAX_SHIFTS, n, n, plan->num_shifts);
-    return SM_OK;
-}
-
-// the data term of one pair into the A volume (S's memory holds the horizontal sums for n > 1)
-static int sgm_cost_launch(const sm_plan *plan, int cw, bool mirror, int pair, hipStream_t st)
-{
-    SgmCostGeom g;
-    g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts; g.Dp = sgm_padded_shifts(plan);
-    g.half = plan->square_width / 2;
-    g.side = (long long)plan->max_pairs * g.w * g.h;
-    g.pair = (long long)pair * g.w * g.h;
-    u16 *A = (u16 *)plan->d_sgm;
-    u16 *hs = g.half ? (u16 *)((char *)plan->d_sgm + (size_t)2 * g.w * g.h * g.Dp) : A;
-    const bool ghost = plan->border == SM_GHOST;
-    const void *fn;
-#define SGM_H(NW) (ghost ? (mirror ? (const void *)k_sgm_cost_h<NW, true, true> : (const void *)k_sgm_cost_h<NW, true, false>) \
-                         : (mirror ? (const void *)k_sgm_cost_h<NW, false, true> : (const void *)k_sgm_cost_h<NW, false, false>))
-    fn = cw == 7 ? SGM_H(2) : SGM_H(1);
-#undef SGM_H
-    {
-        void *args[] = {(void *)&plan->d_census, (void *)&hs, (void *)&g};
-        const hipError_t e = hipLaunchKernel(fn, dim3((g.w + SGC_XR - 1) / SGC_XR, (g.h + 3) / 4, g.Dp / 64),
-                                             dim3(64, 4), args, 0, st);
-        if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_sgm_cost_h failed: %s", hipGetErrorString(e));
-    }
-    if (!g.half) return SM_OK;
-    fn = ghost ? (const void *)k_sgm_cost_v<true> : (const void *)k_sgm_cost_v<false>;
-    void *args[] = {(void *)&hs, (void *)&A, (void *)&g};
-    const hipError_t e = hipLaunchKernel(fn, dim3((g.w + 3) / 4, (g.h + SGC_YR - 1) / SGC_YR, g.Dp / 64), dim3(64, 4),
-                                         args, 0, st);
-    if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_sgm_cost_v failed: %s", hipGetErrorString(e));
-    return SM_OK;
-}
-
-template <int K>
-static const void *sgm_path_ptr(int mode)
-{
-    return mode == SGM_FIRST ? (const void *)k_sgm_path<K, SGM_FIRST>
-         : mode == SGM_MID ? (const void *)k_sgm_path<K, SGM_MID> : (const void *)k_sgm_path<K, SGM_LAST>;
-}
-
-// the directions in stream order (integer sums: the order changes nothing); the last one emits the maps
-static int sgm_paths_launch(const sm_plan *plan, int p1, int p2, int paths, bool mirror, int pair, i32 *web, i32 *best,
-                            int16_t *sub, hipStream_t st)
-{
-    static const int dirs[8][2] = {{1, 0}, {0, 1}, {1, 1}, {-1, 1}, {1, -1}, {-1, -1}, {0, -1}, {-1, 0}};
-    static const int four[4] = {0, 1, 6, 7};
-    SgmPathGeom g;
-    g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts; g.Dp = sgm_padded_shifts(plan);
-    g.p1 = p1; g.p2 = p2;
-    g.mirror = mirror;
-    g.map = (long long)pair * g.w * g.h;
-    const int K = g.Dp / 64;
-    const u16 *A = (const u16 *)plan->d_sgm;
-    i32 *S = (i32 *)((char *)plan->d_sgm + (size_t)2 * g.w * g.h * g.Dp);
-    for (int r = 0; r < paths; r++) {
-        const int *dir = dirs[paths == 4 ? four[r] : r];
-        g.dx = dir[0]; g.dy = dir[1];
-        g.lines = g.dy == 0 ? g.h : g.dx == 0 ? g.w : g.w + g.h - 1;
-        const int mode = r == 0 ? SGM_FIRST : r == paths - 1 ? SGM_LAST : SGM_MID;
-        const void *fn = K == 1 ? sgm_path_ptr<1>(mode) : K == 2 ? sgm_path_ptr<2>(mode) : sgm_path_ptr<4>(mode);
-        // (paths >= 4: the last direction is never the first, so S always holds the other directions' sum)
-        void *args[] = {(void *)&A, (void *)&S, (void *)&web, (void *)&best, (void *)&sub, (void *)&g};
-        const hipError_t e = hipLaunchKernel(fn, dim3((g.lines + 3) / 4), dim3(256), args, 0, st);
-        if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_sgm_path failed: %s", hipGetErrorString(e));
-    }
-    return SM_OK;
-}
-
-// the left (or right-reference) SGM maps of `pairs` pairs, one pair at a time through the volumes
-static int sgm_pass(const sm_plan *plan, int cw, int p1, int p2, int paths, bool mirror, int pairs, i32 *web, i32 *best,
-                    int16_t *sub, hipStream_t st)
-{
-    for (int q = 0; q < pairs; q++) {
-        SM_TRY(sgm_cost_launch(plan, cw, mirror, q, st));
-        SM_TRY(sgm_paths_launch(plan, p1, p2, paths, mirror, q, web, best, sub, st));
-    }
-    return SM_OK;
-}
-
-extern "C" int sm_sgm_wta(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
-                          int p1, int p2, int paths, int pairs, int32_t *d_web, int32_t *d_best, int16_t *d_sub,
-                          void *stream)
-{
-    const char *me = "sm_sgm_wta";
-    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
-    if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
-    SM_TRY(sgm_args(plan, census_width, p1, p2, paths, pairs, me));
-    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
-    if ((d_best && overlap(d_web, d_best, map)) || (d_sub && overlap(d_sub, d_web, map / 2, map)) ||
-        (d_sub && d_best && overlap(d_sub, d_best, map / 2, map)))
-        return sm_fail(SM_ERR_ARG, "%s: result maps overlap", me);
-    SM_TRY(sm_use_device(plan->device));
-    hipStream_t st = (hipStream_t)stream;
-    SM_TRY(need_sgm(plan, st, me));
-    SM_TRY(census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
-    return sgm_pass(plan, census_width, p1, p2, paths, false, pairs, d_web, d_best, d_sub, st);
-}
-
-extern "C" int sm_sgm_wta_right(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right,
-                                int census_width, int p1, int p2, int paths, int pairs, int32_t *d_web_right,
-                                int32_t *d_best_right, void *stream)
-{
-    const char *me = "sm_sgm_wta_right";
-    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
-    if (!d_web_right) return sm_fail(SM_ERR_ARG, "%s: d_web_right is NULL", me);
-    SM_TRY(sgm_args(plan, census_width, p1, p2, paths, pairs, me));
-    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
-    if (d_best_right && overlap(d_web_right, d_best_right, map))
-        return sm_fail(SM_ERR_ARG, "%s: result maps overlap", me);
-    SM_TRY(sm_use_device(plan->device));
-    hipStream_t st = (hipStream_t)stream;
-    SM_TRY(need_sgm(plan, st, me));
-    SM_TRY(census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
-    return sgm_pass(plan, census_width, p1, p2, paths, true, pairs, d_web_right, d_best_right, nullptr, st);
-}
-
-extern "C" int sm_sgm_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
-                         int p1, int p2, int paths, int pairs, int max_diff, int32_t *d_web, int32_t *d_best,
-                         int32_t *d_web_right, int32_t *d_rejected, int16_t *d_sub, void *stream)
-{
-    const char *me = "sm_sgm_lr";
-    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
-    if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
-    if (max_diff < 0) return sm_fail(SM_ERR_ARG, "%s: max_diff %d is negative", me, max_diff);
-    SM_TRY(sgm_args(plan, census_width, p1, p2, paths, pairs, me));
-    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
-    if ((d_best && overlap(d_best, d_web, map)) || (d_web_right && overlap(d_web_right, d_web, map)) ||
-        (d_best && d_web_right && overlap(d_best, d_web_right, map)) ||
-        (d_sub && (overlap(d_sub, d_web, map / 2, map) || (d_best && overlap(d_sub, d_best, map / 2, map)) ||
-                   (d_web_right && overlap(d_sub, d_web_right, map / 2, map)))))
-        return sm_fail(SM_ERR_ARG, "%s: result maps overlap", me);
-    const size_t counts = (size_t)pairs * sizeof(i32);
-    if (d_rejected && (overlap(d_rejected, d_web, counts, map) || (d_best && overlap(d_rejected, d_best, counts, map)) ||
-                       (d_web_right && overlap(d_rejected, d_web_right, counts, map)) ||
-                       (d_sub && overlap(d_rejected, d_sub, counts, map / 2))))
-        return sm_fail(SM_ERR_ARG, "%s: d_rejected overlaps a map", me);
-    SM_TRY(sm_use_device(plan->device));
-    hipStream_t st = (hipStream_t)stream;
-    SM_TRY(need_sgm(plan, st, me));
-    // the descriptors once for both directions; the right-reference map in natural order (the caller's, or the
-    // plan's mirrored-order map used as scratch), then the check, which gathers from it
-    i32 *right = d_web_right ? d_web_right : plan->d_web_lr;
-    SM_TRY(census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
-    SM_TRY(sgm_pass(plan, census_width, p1, p2, paths, false, pairs, d_web, d_best, d_sub, st));
-    SM_TRY(sgm_pass(plan, census_width, p1, p2, paths, true, pairs, right, nullptr, nullptr, st));
-    SM_TRY(sm_lr_check_natural(plan, d_web, right, d_web, d_rejected, max_diff, pairs, st));
-    if (!d_sub) return SM_OK;
-    const long long n = (long long)pairs * plan->width * plan->height;
-    void *args[] = {(void *)&d_web, (void *)&d_sub, (void *)&n};
-    const hipError_t e = hipLaunchKernel((const void *)k_sgm_sub_mask, dim3((unsigned)((n + 255) / 256)), dim3(256), args,
-                                         0, st);
-    if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_sgm_sub_mask failed: %s", hipGetErrorString(e));
-    return SM_OK;
-}
-
-// sub = 0 where web = 0, for maps of the caller's: k_sgm_sub_mask as sm_sgm_lr launches it (a sub map follows a web map
-// that sm_speckle_filter has thinned)
-extern "C" int sm_sub_mask(sm_plan *plan, const int32_t *d_web, int16_t *d_sub, int pairs, void *stream)
-{
-    const char *me = "sm_sub_mask";
-    if (!d_web || !d_sub) return sm_fail(SM_ERR_ARG, "%s: a map pointer is NULL", me);
-    if (!plan) return sm_fail(SM_ERR_ARG, "%s: plan is NULL", me);
-    if (pairs < 1 || pairs > plan->max_pairs)
-        return sm_fail(SM_ERR_ARG, "%s: pairs %d outside 1..%d (max_pairs of the plan)", me, pairs, plan->max_pairs);
-    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
-    if (overlap(d_sub, d_web, map / 2, map)) return sm_fail(SM_ERR_ARG, "%s: maps overlap", me);
-    SM_TRY(sm_use_device(plan->device));
-    const long long n = (long long)pairs * plan->width * plan->height;
-    void *args[] = {(void *)&d_web, (void *)&d_sub, (void *)&n};
-    const hipError_t e = hipLaunchKernel((const void *)k_sgm_sub_mask, dim3((unsigned)((n + 255) / 256)), dim3(256), args,
-                                         0, (hipStream_t)stream);
-    if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_sgm_sub_mask failed: %s", hipGetErrorString(e));
     return SM_OK;
 }

@@ -261,9 +261,7 @@ static int launch_general(sm_plan *plan, const uint8_t *d_gray_left, const uint8
     CostGeom g;
     g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts;
     g.half = plan->square_width / 2; g.n = 2 * g.half + 1;
-    if (g.n > 25 || g.D > 512)
-        return sm_fail(SM_ERR_ARG, "sm_cost_wta: built for windows up to 25x25 and at most 512 shifts "
-                       "(got %dx%d, %d)", g.n, g.n, g.D);
+    SM_TRY(sm_check_reach(plan, 512, "sm_cost_wta"));
     g.nl = 1; g.log2nl = 0;
     while (g.nl * SMC_DS < g.D) { g.nl <<= 1; g.log2nl++; }
     // 256 threads = 256 / nl pixel groups per workgroup
@@ -305,14 +303,11 @@ static int launch_general(sm_plan *plan, const uint8_t *d_gray_left, const uint8
 extern "C" int sm_cost_wta(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right,
                            int cost, int pairs, int32_t *d_web, int32_t *d_best, void *stream)
 {
-    if (!plan) return sm_fail(SM_ERR_ARG, "sm_cost_wta: plan is NULL");
-    if (pairs < 1 || pairs > plan->max_pairs)
-        return sm_fail(SM_ERR_ARG, "sm_cost_wta: pairs %d outside 1..%d", pairs, plan->max_pairs);
+    SM_TRY(sm_check_pairs(plan, pairs, "sm_cost_wta"));
     if (!d_gray_left || !d_gray_right || !d_web) return sm_fail(SM_ERR_ARG, "sm_cost_wta: NULL argument");
     if (cost != SM_COST_SAD && cost != SM_COST_SSD)
         return sm_fail(SM_ERR_ARG, "sm_cost_wta: cost %d is neither SM_COST_SAD nor SM_COST_SSD", cost);
-    const hipError_t es = hipSetDevice(plan->device);
-    if (es != hipSuccess) return sm_fail(SM_ERR_HIP, "sm_cost_wta: %s", hipGetErrorString(es));
+    SM_TRY(sm_use_device(plan->device));
     {
         // SAD on the quad-SAD unit (sm_cost_pc.hip: window rows by prefix chains, windows up to 15 x 15; sm_cost_qs.hip:
         // 17 .. 21), SSD on the matrix cores (sm_cost_mfma.hip), where they are built for this window and shift count;

@@ -1,6 +1,7 @@
-// sm_filter.h -- disparity post-filters on the maps the library produces: a validity-aware median and speckle
-// removal (include/stereo_hip.h).  Included by sm_lr.hip only: map post-processing, beside the check
-// whose zeros these filters respect, and its per-pair counts (lr_count, k_lr_zero_counts) are reused.
+// sm_filter.hip -- disparity post-filters on the maps the library produces: a validity-aware median and speckle
+// removal (include/stereo_hip.h), and the two masks
+// that carry validity from one map to another (sm_sub_mask, sm_valid_mask).  The per-pair counts of the consistency
+// check are reused (lr_count of sm_device.h; k_lr_zero_counts through sm_lr_zero_counts).
 //
 // PARITY UNPINNED: the reference has no such stage.  Definition (tests/filter_reference.py is its executable form).
 // Maps are [pairs][H][W] of int32 (a web map) or int16 (a sub map); a pixel is valid iff its value != 0; a tap
@@ -31,51 +32,18 @@
 // root), a find follows strictly decreasing labels, and a union retries only when its compare-and-swap (an atomic
 // min whose old value is not the root it meant to link) lost to a smaller label.
 
-#pragma once
+
+#include "sm_device.h"
+
+#include <algorithm>
 
 #define FLT_TW 64
 #define FLT_TH 16
 #define FLT_PX (FLT_TW * FLT_TH)
 
 // ---------------------------------------------------------------------------
-// median
+// median (the exchange network, flt_sort, is in sm_device.h: the interpolation sorts its candidates with it)
 // ---------------------------------------------------------------------------
-
-// Batcher's merge exchange (Knuth 5.2.2 M) for N elements: the comparators in order
-template <int N>
-struct FltNet {
-    int n;
-    unsigned char a[N * 8], b[N * 8];
-};
-
-template <int N>
-constexpr FltNet<N> flt_make_net()
-{
-    FltNet<N> net{};
-    for (int p = 1; p < N; p *= 2)
-        for (int k = p; k >= 1; k /= 2)
-            for (int j = k % p; j <= N - 1 - k; j += 2 * k)
-                for (int i = 0; i <= (k - 1 < N - j - k - 1 ? k - 1 : N - j - k - 1); i++)
-                    if ((i + j) / (2 * p) == (i + j + k) / (2 * p)) {
-                        net.a[net.n] = (unsigned char)(i + j);
-                        net.b[net.n] = (unsigned char)(i + j + k);
-                        net.n++;
-                    }
-    return net;
-}
-
-// v sorted ascending (every use reads v[(N - 1) / 2] only)
-template <int N>
-__host__ __device__ __forceinline__ void flt_sort(i32 (&v)[N])
-{
-    constexpr FltNet<N> net = flt_make_net<N>();
-#pragma unroll
-    for (int c = 0; c < net.n; c++) {
-        const i32 x = v[net.a[c]], y = v[net.b[c]];
-        v[net.a[c]] = x < y ? x : y;
-        v[net.b[c]] = x < y ? y : x;
-    }
-}
 
 // the lower median of the non-zero entries of v (at least one); v is consumed
 template <int N>
@@ -306,4 +274,148 @@ __global__ __launch_bounds__(256) void k_spk_apply(const T *in, T *out, const i3
         out[base + t] = keep ? v : (T)0;
     }
     if (removed) lr_count(removed + blockIdx.y, cnt);
+}
+
+// ---------------------------------------------------------------------------
+// masks
+// ---------------------------------------------------------------------------
+
+// sub = 0 where the checked map is 0
+__global__ __launch_bounds__(256) void k_sgm_sub_mask(const i32 *__restrict__ web, int16_t *__restrict__ sub, long long n)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n && web[i] == 0) sub[i] = 0;
+}
+
+// map = 0 where valid = 0, in place, one element per lane over all pairs
+template <typename T>
+__global__ __launch_bounds__(256) void k_valid_mask(T *map, const u8 *__restrict__ valid, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i < n && valid[i] == 0) map[i] = 0;
+}
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+
+extern "C" int sm_median_filter(sm_plan *plan, const void *d_in, int map_type, int k, int pairs, void *d_out, void *stream)
+{
+    const char *me = "sm_median_filter";
+    size_t elem;
+    if (!d_in || !d_out) return sm_fail(SM_ERR_ARG, "%s: a map pointer is NULL", me);
+    SM_TRY(sm_check_map_type(map_type, me, &elem));
+    if (k != 3 && k != 5) return sm_fail(SM_ERR_ARG, "%s: k %d is not 3 or 5", me, k);
+    SM_TRY(sm_check_pairs(plan, pairs, me));
+    const int W = plan->width, H = plan->height;
+    if (overlap(d_in, d_out, (size_t)pairs * W * H * elem))
+        return sm_fail(SM_ERR_ARG, "%s: maps overlap (every output pixel reads its neighbours' inputs)", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((W + FLT_TW - 1) / FLT_TW, (H + FLT_TH - 1) / FLT_TH, pairs), block(256);
+#define SM_MED_GO(T, K) hipLaunchKernelGGL((k_median<T, K>), grid, block, 0, st, (const T *)d_in, (T *)d_out, W, H)
+    if (map_type == SM_MAP_I32) { if (k == 3) SM_MED_GO(i32, 3); else SM_MED_GO(i32, 5); }
+    else                        { if (k == 3) SM_MED_GO(int16_t, 3); else SM_MED_GO(int16_t, 5); }
+#undef SM_MED_GO
+    SM_LAUNCH_CHECK("k_median");
+    return SM_OK;
+}
+
+extern "C" int sm_plan_reserve_filter(sm_plan *plan)
+{
+    if (!plan) return sm_fail(SM_ERR_ARG, "sm_plan_reserve_filter: plan is NULL");
+    SM_TRY(sm_use_device(plan->device));
+    return sm_ws_reserve(plan, SM_WS_SET_FILTER, "sm_plan_reserve_filter");
+}
+
+template <typename T>
+static int speckle_launch(const sm_plan *plan, const T *in, T *out, int max_size, int max_diff, int pairs, i32 *removed,
+                          hipStream_t st)
+{
+    const int W = plan->width, H = plan->height;
+    const unsigned npx = (unsigned)W * H;
+    i32 *labels = plan->d_filter, *sizes = plan->d_filter + (size_t)plan->max_pairs * npx;
+    const unsigned tiles_x = (W + FLT_TW - 1) / FLT_TW, tiles_y = (H + FLT_TH - 1) / FLT_TH;
+    if (removed) SM_TRY(sm_lr_zero_counts(removed, pairs, st));
+    hipLaunchKernelGGL(k_spk_local<T>, dim3(tiles_x, tiles_y, pairs), dim3(256), 0, st, in, labels, sizes, W, H, max_diff);
+    SM_LAUNCH_CHECK("k_spk_local");
+    const unsigned n_h = (tiles_y - 1) * (unsigned)W, n_all = n_h + (tiles_x - 1) * (unsigned)H;
+    if (n_all) {
+        hipLaunchKernelGGL(k_spk_merge<T>, dim3((n_all + 255) / 256, pairs), dim3(256), 0, st, in, labels, W, H, max_diff,
+                           n_h, n_all);
+        SM_LAUNCH_CHECK("k_spk_merge");
+    }
+    hipLaunchKernelGGL(k_spk_count, dim3((npx + 255) / 256, pairs), dim3(256), 0, st, labels, sizes, npx);
+    SM_LAUNCH_CHECK("k_spk_count");
+    hipLaunchKernelGGL(k_spk_apply<T>, dim3(std::min((npx + 255) / 256, (unsigned)SM_LR_BLOCKS), pairs), dim3(256), 0, st,
+                       in, out, labels, sizes, removed, npx, max_size);
+    SM_LAUNCH_CHECK("k_spk_apply");
+    return SM_OK;
+}
+
+extern "C" int sm_speckle_filter(sm_plan *plan, const void *d_in, int map_type, int max_size, int max_diff, int pairs,
+                                 void *d_out, int32_t *d_removed, void *stream)
+{
+    const char *me = "sm_speckle_filter";
+    size_t elem;
+    if (!d_in || !d_out) return sm_fail(SM_ERR_ARG, "%s: a map pointer is NULL", me);
+    SM_TRY(sm_check_map_type(map_type, me, &elem));
+    if (max_size < 0) return sm_fail(SM_ERR_ARG, "%s: max_size %d is negative", me, max_size);
+    if (max_diff < 0) return sm_fail(SM_ERR_ARG, "%s: max_diff %d is negative", me, max_diff);
+    SM_TRY(sm_check_pairs(plan, pairs, me));
+    const size_t map = (size_t)pairs * plan->width * plan->height * elem;
+    if (d_in != d_out && overlap(d_in, d_out, map))
+        return sm_fail(SM_ERR_ARG, "%s: maps overlap without d_out being d_in", me);
+    const size_t counts = (size_t)pairs * sizeof(i32);
+    if (d_removed && (overlap(d_removed, d_in, counts, map) || overlap(d_removed, d_out, counts, map)))
+        return sm_fail(SM_ERR_ARG, "%s: d_removed overlaps a map", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    SM_TRY(sm_ws_need(plan, SM_WS_SET_FILTER, st, me));
+    if (map_type == SM_MAP_I32)
+        return speckle_launch<i32>(plan, (const i32 *)d_in, (i32 *)d_out, max_size, max_diff, pairs, d_removed, st);
+    return speckle_launch<int16_t>(plan, (const int16_t *)d_in, (int16_t *)d_out, max_size, max_diff, pairs, d_removed, st);
+}
+
+// k_sgm_sub_mask over n elements: sm_sub_mask below, and sm_sgm_lr (sm_sgm.hip) behind its check
+int sm_sub_mask_launch(const i32 *web, int16_t *sub, long long n, hipStream_t st)
+{
+    void *args[] = {(void *)&web, (void *)&sub, (void *)&n};
+    const hipError_t e = hipLaunchKernel((const void *)k_sgm_sub_mask, dim3((unsigned)((n + 255) / 256)), dim3(256), args,
+                                         0, st);
+    if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_sgm_sub_mask failed: %s", hipGetErrorString(e));
+    return SM_OK;
+}
+
+// sub = 0 where web = 0, for maps of the caller's: k_sgm_sub_mask as sm_sgm_lr launches it (a sub map follows a web map
+// that sm_speckle_filter has thinned)
+extern "C" int sm_sub_mask(sm_plan *plan, const int32_t *d_web, int16_t *d_sub, int pairs, void *stream)
+{
+    const char *me = "sm_sub_mask";
+    if (!d_web || !d_sub) return sm_fail(SM_ERR_ARG, "%s: a map pointer is NULL", me);
+    SM_TRY(sm_check_pairs(plan, pairs, me));
+    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
+    if (overlap(d_sub, d_web, map / 2, map)) return sm_fail(SM_ERR_ARG, "%s: maps overlap", me);
+    SM_TRY(sm_use_device(plan->device));
+    return sm_sub_mask_launch(d_web, d_sub, (long long)pairs * plan->width * plan->height, (hipStream_t)stream);
+}
+
+// map = 0 where valid = 0 (the validity sm_rectify writes, carried to a disparity map)
+extern "C" int sm_valid_mask(sm_plan *plan, void *d_map, int map_type, const uint8_t *d_valid, int pairs, void *stream)
+{
+    const char *me = "sm_valid_mask";
+    size_t elem;
+    if (!d_map) return sm_fail(SM_ERR_ARG, "%s: a map pointer is NULL", me);
+    if (!d_valid) return sm_fail(SM_ERR_ARG, "%s: d_valid is NULL", me);
+    SM_TRY(sm_check_map_type(map_type, me, &elem));
+    if ((const void *)d_valid == d_map) return sm_fail(SM_ERR_ARG, "%s: d_valid overlaps the map", me);
+    SM_TRY(sm_check_pairs(plan, pairs, me));
+    const size_t n = (size_t)pairs * plan->width * plan->height;
+    if (overlap(d_valid, d_map, n, n * elem)) return sm_fail(SM_ERR_ARG, "%s: d_valid overlaps the map", me);
+    SM_TRY(sm_use_device(plan->device));
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (map_type == SM_MAP_I32) hipLaunchKernelGGL(k_valid_mask<i32>, grid, block, 0, (hipStream_t)stream, (i32 *)d_map, d_valid, n);
+    else hipLaunchKernelGGL(k_valid_mask<int16_t>, grid, block, 0, (hipStream_t)stream, (int16_t *)d_map, d_valid, n);
+    SM_LAUNCH_CHECK("k_valid_mask");
+    return SM_OK;
 }

@@ -94,8 +94,6 @@ struct sm_plan {
     // optional timing of the match launches (sm_plan_time_kernels)
     int timing_cap, timing_n, timing_every, timing_seen;
     hipEvent_t *t_begin, *t_end;
-    i32 *d_web_tmp;      // int32 map for narrow results of kernels without a narrow store path
-                         // (allocated with the plan for the kernels that need it; part of the workspace)
     i32 *d_flags;        // [0] = zero-interval flag, [1] = has-zero scratch,
                          // [2] = edge table is not of threshold form
     i32 *h_flags;        // pinned host copy of d_flags (k_publish_flags)
@@ -104,28 +102,21 @@ struct sm_plan {
     int tab_valid;
     int tab_ok;          // tables verified to be of threshold form
     int pairs_loaded;    // batch size of the edges currently in d_ext
-    // left-right consistency check (sm_lr.hip): NOT allocated with the plan, but by sm_plan_reserve_lr
-    // or the first call that needs them; part of the workspace from then on
-    u32 *d_ext_lr;       // mirrored packed images, d_ext's layout: side 0 = mirror(right), side 1 = mirror(left)
+    // the lazily allocated workspaces (the table `sm_ws` below): NOT allocated with the plan, but by a
+    // sm_plan_reserve_* or by the first call that needs them; part of the workspace from then on
+    i32 *d_web_tmp;      // int32 map for narrow results of kernels without a narrow store path (sm_plan_reserve_narrow)
+    u32 *d_ext_lr;       // sm_lr.hip: mirrored packed images, d_ext's layout: side 0 = mirror(right), side 1 = mirror(left)
     i32 *d_web_lr;       // right-reference map of sm_run_lr / sm_cost_lr in mirrored order: max_pairs * W * H
-                         // (shared by the two checks: allocated by whichever reserves first)
+                         // (shared by the checks of every cost mode: allocated by whichever reserves first)
     u8 *d_gray_lr;       // sm_cost_lr: mirrored gray images, batch 0 = mirror(right), batch 1 = mirror(left),
                          // each of max_pairs * W * H bytes starting 256-byte aligned (sm_plan_reserve_cost_lr)
+    u32 *d_census;       // sm_census.hip: descriptors [side: 0 = left, 1 = right][max_pairs][H][W], 8 bytes each (4 for c <= 5)
+    void *d_sgm;         // sm_sgm.hip: one pair's volumes: A [H][W][Dp] u16, then S [H][W][Dp] i32 (Dp = 64, 128 or 256 >= num_shifts)
+    i32 *d_filter;       // sm_filter.hip, speckle filter: labels [max_pairs][H][W] int32, then component sizes [max_pairs][H][W] int32
+    i32 *d_interp;       // sm_interp.hip: per pair six directional maps [6][H][W], line carries [6][segments][W + H - 1], row
+                         // carries [2][H][chunks], 4 bytes an element (layout at the top of sm_interp.hip)
     int cost_lds_raised; // sm_cost_wta: the LDS limit of this plan's four-wave SAD kernel is raised (on `device`)
     char describe[512];
-    // census cost mode (sm_census.hip): NOT allocated with the plan, but by sm_plan_reserve_census or the first call
-    // that needs it; part of the workspace from then on (with d_web_lr, which it allocates if the plan has none yet)
-    u32 *d_census;       // descriptors [side: 0 = left, 1 = right][max_pairs][H][W], 8 bytes each (4 for c <= 5)
-    // SGM over the census data term (sm_census.hip, sm_sgm.h): NOT allocated with the plan, but by sm_plan_reserve_sgm or
-    // the first call that needs it (with the census workspace); part of the workspace from then on
-    void *d_sgm;         // one pair's volumes: A [H][W][Dp] u16, then S [H][W][Dp] i32 (Dp = 64, 128 or 256 >= num_shifts)
-    // speckle filter (sm_filter.h, launched by sm_lr.hip): NOT allocated with the plan, but by sm_plan_reserve_filter or
-    // the first sm_speckle_filter; part of the workspace from then on
-    i32 *d_filter;       // labels [max_pairs][H][W] int32, then component sizes [max_pairs][H][W] int32
-    // interpolation (sm_interp.h, launched by sm_lr.hip): NOT allocated with the plan, but by sm_plan_reserve_interp or
-    // the first sm_interpolate; part of the workspace from then on
-    i32 *d_interp;       // per pair: six directional maps [6][H][W], line carries [6][segments][W + H - 1], row carries
-                         // [2][H][chunks], 4 bytes an element (layout in sm_interp.h)
 };
 
 // XCD-aware tile order (device side).  Workgroups are dealt round-robin to the 8
@@ -172,15 +163,64 @@ int sm_fail(int code, const char *fmt, ...);
 // sm_api.hip
 int sm_use_device(int device);                    // hipSetDevice, failure as SM_ERR_HIP
 bool sm_stream_capturing(hipStream_t st);         // is `st` recording into a graph?
-size_t sm_lr_workspace_bytes(const sm_plan *plan);    // sm_lr.hip: 0 until sm_plan_reserve_lr / _cost_lr
-void sm_lr_free(sm_plan *plan);                       // sm_lr.hip: sm_plan_destroy
-// sm_lr.hip, for the census mode: the mirrored-order map alone (if the plan has none yet), and k_lr_check on a
-// right-reference map in natural order (the rejection counts zeroed by a kernel first)
-int sm_lr_reserve_map(sm_plan *plan, const char *me);
+
+// ---------------------------------------------------------------------------
+// The lazily allocated workspaces: one table in sm_api.hip, one row per buffer (the sm_plan member, its bytes for
+// this plan, whether it is zero-filled, its name in a message).  A stage names the SET of rows it needs; a new stage
+// adds a member, a row and a set, and nothing else.  A row of 0 bytes is never allocated and never missing.
+// ---------------------------------------------------------------------------
+enum { SM_WS_NARROW, SM_WS_EXT_LR, SM_WS_WEB_LR, SM_WS_GRAY_LR, SM_WS_CENSUS, SM_WS_SGM, SM_WS_FILTER, SM_WS_INTERP,
+       SM_WS_ROWS };
+struct sm_ws_set {
+    unsigned rows;             // bit r = row r
+    const char *what;          // "the workspace of <what> is not allocated"
+    const char *reserve;       // the public function a refusal inside a stream capture points to
+    const sm_ws_set *first;    // a set reserved before this one, and kept where this one then fails
+};
+static const sm_ws_set SM_WS_SET_NARROW = {1u << SM_WS_NARROW, "narrow results (the int32 staging map)", "sm_plan_reserve_narrow", nullptr};
+static const sm_ws_set SM_WS_SET_LR = {1u << SM_WS_EXT_LR | 1u << SM_WS_WEB_LR, "the consistency check", "sm_plan_reserve_lr", nullptr};
+static const sm_ws_set SM_WS_SET_COST_LR = {1u << SM_WS_GRAY_LR | 1u << SM_WS_WEB_LR, "the cost mode's consistency check", "sm_plan_reserve_cost_lr", nullptr};
+static const sm_ws_set SM_WS_SET_CENSUS = {1u << SM_WS_CENSUS | 1u << SM_WS_WEB_LR, "the census mode", "sm_plan_reserve_census", nullptr};
+static const sm_ws_set SM_WS_SET_SGM = {1u << SM_WS_SGM, "SGM", "sm_plan_reserve_sgm", &SM_WS_SET_CENSUS};
+static const sm_ws_set SM_WS_SET_FILTER = {1u << SM_WS_FILTER, "the speckle filter", "sm_plan_reserve_filter", nullptr};
+static const sm_ws_set SM_WS_SET_INTERP = {1u << SM_WS_INTERP, "the interpolation", "sm_plan_reserve_interp", nullptr};
+// all or nothing: on a failure every buffer this call allocated is freed and the plan is as before (but `first` stays)
+int sm_ws_reserve(sm_plan *plan, const sm_ws_set &set, const char *me);
+// from an entry point: nothing if present; SM_ERR_ARG naming set.reserve if `st` is capturing; otherwise reserve
+int sm_ws_need(sm_plan *plan, const sm_ws_set &set, hipStream_t st, const char *me);
+size_t sm_ws_bytes(const sm_plan *plan);          // of the rows that are allocated (sm_plan_workspace_bytes)
+void sm_ws_free(sm_plan *plan);                   // all rows (sm_plan_destroy)
+size_t sm_lr_map_bytes(const sm_plan *plan);      // one int32 map of max_pairs pairs
+size_t sm_lr_gray_batch_bytes(const sm_plan *plan);   // one batch of mirrored gray images, rounded up to 256 bytes
+size_t sm_itp_bytes(const sm_plan *plan);         // sm_interp.hip (its tile constants decide)
+size_t sm_sgm_volume_bytes(const sm_plan *plan);  // sm_sgm.hip (its padded shift count decides)
+
+// ---------------------------------------------------------------------------
+// Argument rules that more than one entry point applies (sm_api.hip).  Each reports as `me`, the entry point's name.
+// ---------------------------------------------------------------------------
+// do [a, a + a_bytes) and [b, b + b_bytes) share a byte?  (b_bytes = 0: as many as a)
+static inline bool overlap(const void *a, const void *b, size_t a_bytes, size_t b_bytes = 0)
+{
+    return (uintptr_t)a < (uintptr_t)b + (b_bytes ? b_bytes : a_bytes) && (uintptr_t)b < (uintptr_t)a + a_bytes;
+}
+int sm_check_pairs(const sm_plan *plan, int pairs, const char *me);       // plan is NULL; pairs outside 1..max_pairs
+int sm_check_reach(const sm_plan *plan, int max_shifts, const char *me);  // windows up to 25x25, at most max_shifts shifts
+int sm_check_census_width(int census_width, const char *me);              // 3, 5 or 7
+int sm_check_map_type(int map_type, const char *me, size_t *elem);        // SM_MAP_I32 / SM_MAP_I16 and its element size
+// the result maps of a *_lr entry (d_best, d_web_right, d_sub, d_rejected may be NULL): "result maps overlap", then
+// "d_rejected overlaps a map"
+int sm_check_lr_maps(const sm_plan *plan, int pairs, const int32_t *d_web, const int32_t *d_best,
+                     const int32_t *d_web_right, const int16_t *d_sub, const int32_t *d_rejected, const char *me);
+
+// sm_lr.hip, for the other stages: the per-pair counts zeroed by k_lr_zero_counts (a kernel: a captured memset of them
+// replayed wrongly), and k_lr_check on a right-reference map in natural order (the rejection counts zeroed first)
+int sm_lr_zero_counts(i32 *counts, int pairs, hipStream_t st);
 int sm_lr_check_natural(const sm_plan *plan, const i32 *web, const i32 *right, i32 *out, i32 *rejected, int max_diff,
                         int pairs, hipStream_t st);
-size_t sm_census_workspace_bytes(const sm_plan *plan);   // sm_census.hip: 0 until sm_plan_reserve_census
-void sm_census_free(sm_plan *plan);                      // sm_census.hip: sm_plan_destroy
+// sm_census.hip, for SGM: both images of `pairs` pairs into the census workspace (4-byte descriptors for c <= 5, 8 for 7)
+int sm_census_descriptors(sm_plan *plan, int cw, const uint8_t *left, const uint8_t *right, int pairs, hipStream_t st);
+// sm_filter.hip, for sm_sgm_lr: k_sgm_sub_mask, sub = 0 where web = 0, over n elements
+int sm_sub_mask_launch(const i32 *web, int16_t *sub, long long n, hipStream_t st);
 
 // sm_match_bs.hip (bit-sliced kernel; nullptr if not built for this window)
 const void *sm_bs_kernel_ptr(int n, int ds, bool fulld, bool ghost, bool cap2, bool duo = false);

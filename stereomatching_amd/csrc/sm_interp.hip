@@ -1,6 +1,6 @@
-// sm_interp.h -- occlusion-aware interpolation of checked disparity maps: classification of the invalid pixels and
-// the discontinuity-preserving fill (include/stereo_hip.h).  Included by sm_lr.hip only, after
-// sm_filter.h: it reuses flt_sort (the exchange network), lr_count and k_lr_zero_counts.
+// sm_interp.hip -- occlusion-aware interpolation of checked disparity maps: classification of the invalid pixels and
+// the discontinuity-preserving fill (include/stereo_hip.h).  It reuses flt_sort (the exchange network) and
+// lr_count of sm_device.h, and k_lr_zero_counts through sm_lr_zero_counts.
 //
 // PARITY UNPINNED: the reference has no such stage.  Definition (tests/interp_reference.py is its executable form).
 // Maps are [pairs][H][W] of int32 (a web map) or int16 (a sub map); a pixel is valid iff its value != 0; pairs are
@@ -30,7 +30,10 @@
 // Workspace per pair, 4 bytes an element: directional maps [6][H][W] (int16 maps use the first half), line carries
 // [6][segments][W + H - 1], row carries [2][H][chunks].
 
-#pragma once
+
+#include "sm_device.h"
+
+#include <algorithm>
 
 #define ITP_SEG 64      // rows of a line segment (k_itp_sweep)
 #define ITP_CW 64       // pixels of a row chunk: one wave
@@ -234,4 +237,95 @@ __global__ __launch_bounds__(256) void k_itp_combine(const T *__restrict__ in, c
         if (inb) out[base + p] = (T)res;
     }
     if (filled) lr_count(filled + pair, cnt);
+}
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+
+// sm_interpolate's workspace (layout above), in 4-byte elements per pair: six directional maps, the carries of
+// W + H - 1 lines for six directions and every segment, the carries of every row chunk from either side
+static int itp_segs(const sm_plan *plan) { return (plan->height + ITP_SEG - 1) / ITP_SEG; }
+static int itp_chunks(const sm_plan *plan) { return (plan->width + ITP_CW - 1) / ITP_CW; }
+static size_t itp_loc_elems(const sm_plan *plan) { return (size_t)6 * plan->width * plan->height; }
+static size_t itp_car_elems(const sm_plan *plan)
+{
+    return (size_t)6 * itp_segs(plan) * (plan->width + plan->height - 1);
+}
+static size_t itp_row_elems(const sm_plan *plan) { return (size_t)2 * plan->height * itp_chunks(plan); }
+size_t sm_itp_bytes(const sm_plan *plan)
+{
+    return (size_t)plan->max_pairs * sizeof(i32) * (itp_loc_elems(plan) + itp_car_elems(plan) + itp_row_elems(plan));
+}
+
+extern "C" int sm_occlusion_classify(sm_plan *plan, const int32_t *d_web, const int32_t *d_web_right, int pairs,
+                                     uint8_t *d_class, void *stream)
+{
+    const char *me = "sm_occlusion_classify";
+    if (!d_web || !d_web_right || !d_class) return sm_fail(SM_ERR_ARG, "%s: a map pointer is NULL", me);
+    SM_TRY(sm_check_pairs(plan, pairs, me));
+    const unsigned npx = (unsigned)plan->width * plan->height;
+    const size_t map = (size_t)pairs * npx * sizeof(i32);
+    if (overlap(d_class, d_web, map / 4, map) || overlap(d_class, d_web_right, map / 4, map))
+        return sm_fail(SM_ERR_ARG, "%s: d_class overlaps a map", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipLaunchKernelGGL(k_itp_classify, dim3((npx + 255) / 256, pairs), dim3(256), 0, (hipStream_t)stream, d_web,
+                       d_web_right, d_class, plan->width, npx, plan->num_shifts, plan->border == SM_GHOST ? 1 : 0);
+    SM_LAUNCH_CHECK("k_itp_classify");
+    return SM_OK;
+}
+
+extern "C" int sm_plan_reserve_interp(sm_plan *plan)
+{
+    if (!plan) return sm_fail(SM_ERR_ARG, "sm_plan_reserve_interp: plan is NULL");
+    SM_TRY(sm_use_device(plan->device));
+    return sm_ws_reserve(plan, SM_WS_SET_INTERP, "sm_plan_reserve_interp");
+}
+
+template <typename T>
+static int interp_launch(const sm_plan *plan, const T *in, const u8 *cls, T *out, int pairs, i32 *filled, hipStream_t st)
+{
+    const int W = plan->width, H = plan->height, segs = itp_segs(plan), chunks = itp_chunks(plan);
+    T *loc = (T *)plan->d_interp;
+    i32 *car = plan->d_interp + plan->max_pairs * itp_loc_elems(plan);
+    i32 *rows = car + plan->max_pairs * itp_car_elems(plan);
+    const unsigned items = (unsigned)H * chunks, lines = W + H - 1;
+    if (filled) SM_TRY(sm_lr_zero_counts(filled, pairs, st));
+    hipLaunchKernelGGL(k_itp_rowsum<T>, dim3((items + 3) / 4, pairs), dim3(256), 0, st, in, rows, W, H, chunks);
+    SM_LAUNCH_CHECK("k_itp_rowsum");
+    hipLaunchKernelGGL(k_itp_rowscan, dim3((H + 3) / 4, pairs), dim3(256), 0, st, rows, H, chunks);
+    SM_LAUNCH_CHECK("k_itp_rowscan");
+    hipLaunchKernelGGL(k_itp_sweep<T>, dim3((lines + 255) / 256, segs, 6 * pairs), dim3(256), 0, st, in, loc, car, W, H,
+                       segs);
+    SM_LAUNCH_CHECK("k_itp_sweep");
+    hipLaunchKernelGGL(k_itp_resolve, dim3((lines + 255) / 256, 6, pairs), dim3(256), 0, st, car, W, H, segs);
+    SM_LAUNCH_CHECK("k_itp_resolve");
+    hipLaunchKernelGGL(k_itp_combine<T>, dim3(std::min((items + 3) / 4, (unsigned)SM_LR_BLOCKS), pairs), dim3(256), 0, st,
+                       in, cls, out, (const T *)loc, (const i32 *)car, (const i32 *)rows, filled, W, H, segs, chunks);
+    SM_LAUNCH_CHECK("k_itp_combine");
+    return SM_OK;
+}
+
+extern "C" int sm_interpolate(sm_plan *plan, const void *d_in, int map_type, const uint8_t *d_class, int pairs,
+                              void *d_out, int32_t *d_filled, void *stream)
+{
+    const char *me = "sm_interpolate";
+    size_t elem;
+    if (!d_in || !d_out) return sm_fail(SM_ERR_ARG, "%s: a map pointer is NULL", me);
+    SM_TRY(sm_check_map_type(map_type, me, &elem));
+    SM_TRY(sm_check_pairs(plan, pairs, me));
+    const size_t px = (size_t)pairs * plan->width * plan->height, map = px * elem;
+    if (overlap(d_in, d_out, map))
+        return sm_fail(SM_ERR_ARG, "%s: maps overlap (every candidate is read from the input)", me);
+    if (d_class && overlap(d_class, d_out, px, map)) return sm_fail(SM_ERR_ARG, "%s: d_class overlaps d_out", me);
+    const size_t counts = (size_t)pairs * sizeof(i32);
+    if (d_filled && (overlap(d_filled, d_in, counts, map) || overlap(d_filled, d_out, counts, map) ||
+                     (d_class && overlap(d_filled, d_class, counts, px))))
+        return sm_fail(SM_ERR_ARG, "%s: d_filled overlaps a map", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    SM_TRY(sm_ws_need(plan, SM_WS_SET_INTERP, st, me));
+    if (map_type == SM_MAP_I32)
+        return interp_launch<i32>(plan, (const i32 *)d_in, d_class, (i32 *)d_out, pairs, d_filled, st);
+    return interp_launch<int16_t>(plan, (const int16_t *)d_in, d_class, (int16_t *)d_out, pairs, d_filled, st);
 }

@@ -1,12 +1,11 @@
-// sm_rectify.h -- stereo rectification (include/stereo_hip.h "rectification"): kernels; their
-// entry points are at the end of sm_lr.hip.
+// sm_rectify.hip -- stereo rectification (include/stereo_hip.h "rectification").
 //
 //   k_rectify        the remap: every destination pixel reads the raw image where a fixed-point map says, bilinear or
 //                    nearest, with a validity bit.  Integer arithmetic throughout.
 //   k_rmap_build     the map of a calibration (Brown-Conrady distortion, rectifying rotation, new projection), IEEE
-//                    double, one operation at a time in the order tests/rectify_reference.py fixes (this file is
+//                    double, one operation at a time in the order tests/rectify_reference.py fixes (this unit is
 //                    compiled with -ffp-contract=off, as every file of the library is)
-//   k_valid_mask     map = 0 where valid = 0, in place
+// (k_valid_mask, which carries the validity to a disparity map, is a post-filter: sm_filter.hip)
 //
 // The remap is a stream (map in, pixels out) around a gather (the raw image).  Per destination pixel it moves 8 (ABS32)
 // or 4 (REL16) map bytes, one output byte, one validity byte if asked, and about one source byte that a smooth map keeps
@@ -18,7 +17,8 @@
 //
 // Every tap is loaded from a clamped, always legal position and replaced by `border` afterwards where the position
 // was outside: sixteen independent byte loads per lane and pair, no divergent branch.
-#pragma once
+
+#include "sm_internal.h"
 
 #define SM_RECT_FRAC 5      // SM_RMAP_FRAC_BITS
 #define SM_RECT_ONE 32
@@ -188,10 +188,131 @@ __global__ __launch_bounds__(256) void k_rmap_build(RectCalib c, void *map, int 
     }
 }
 
-// map = 0 where valid = 0, in place, one element per lane over all pairs
-template <typename T>
-__global__ __launch_bounds__(256) void k_valid_mask(T *map, const u8 *__restrict__ valid, size_t n)
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+
+static int rect_format(int map_format, const char *me, size_t *entry)
 {
-    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (i < n && valid[i] == 0) map[i] = 0;
+    if (map_format != SM_RMAP_ABS32 && map_format != SM_RMAP_REL16)
+        return sm_fail(SM_ERR_ARG, "%s: map_format %d is neither SM_RMAP_ABS32 nor SM_RMAP_REL16", me, map_format);
+    *entry = map_format == SM_RMAP_ABS32 ? 2 * sizeof(i32) : 2 * sizeof(int16_t);
+    return SM_OK;
+}
+
+// 32 * x + dx of a REL16 map is formed in 32 bits
+static int rect_plan_size(const sm_plan *plan, const char *me)
+{
+    if (plan->width > (1 << 25) || plan->height > (1 << 25))
+        return sm_fail(SM_ERR_ARG, "%s: built for images of up to %d pixels a side (got %dx%d)", me, 1 << 25, plan->width,
+                       plan->height);
+    return SM_OK;
+}
+
+extern "C" int sm_rectify(sm_plan *plan, const uint8_t *d_raw_left, const uint8_t *d_raw_right, int src_w, int src_h,
+                          const void *d_map_left, const void *d_map_right, int map_format, int interp, int border,
+                          int pairs, uint8_t *d_left, uint8_t *d_right, uint8_t *d_valid_left, uint8_t *d_valid_right,
+                          void *stream)
+{
+    const char *me = "sm_rectify";
+    size_t entry;
+    if (!d_raw_left || !d_raw_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
+    if (!d_map_left || !d_map_right) return sm_fail(SM_ERR_ARG, "%s: a map pointer is NULL", me);
+    if (!d_left || !d_right) return sm_fail(SM_ERR_ARG, "%s: output image pointer is NULL", me);
+    SM_TRY(rect_format(map_format, me, &entry));
+    if (interp != SM_INTERP_BILINEAR && interp != SM_INTERP_NEAREST)
+        return sm_fail(SM_ERR_ARG, "%s: interp %d is neither SM_INTERP_BILINEAR nor SM_INTERP_NEAREST", me, interp);
+    if (border < 0 || border > 255) return sm_fail(SM_ERR_ARG, "%s: border %d outside 0..255", me, border);
+    if (src_w < 1 || src_h < 1 || (long long)src_w * src_h > INT32_MAX)
+        return sm_fail(SM_ERR_ARG, "%s: source size %dx%d is not positive or has more than 2^31 - 1 pixels", me, src_w, src_h);
+    // an output that IS an input or another output overlaps it whatever the sizes are (the ranges follow, with the plan)
+    const void *outs[4] = {d_left, d_right, d_valid_left, d_valid_right};
+    for (int i = 0; i < 4; i++) {
+        if (!outs[i]) continue;
+        if (outs[i] == d_raw_left || outs[i] == d_raw_right || outs[i] == d_map_left || outs[i] == d_map_right)
+            return sm_fail(SM_ERR_ARG, "%s: an output overlaps an input (every tap is read from the raw images)", me);
+        for (int j = 0; j < i; j++)
+            if (outs[i] == outs[j]) return sm_fail(SM_ERR_ARG, "%s: outputs overlap", me);
+    }
+    SM_TRY(sm_check_pairs(plan, pairs, me));
+    SM_TRY(rect_plan_size(plan, me));
+    if ((((uintptr_t)d_map_left | (uintptr_t)d_map_right) & (entry / 2 - 1)) != 0)
+        return sm_fail(SM_ERR_ARG, "%s: a map pointer is not aligned to its %zu-byte elements", me, entry / 2);
+    const int W = plan->width;
+    const unsigned npx = (unsigned)W * plan->height;
+    const size_t raw = (size_t)pairs * src_w * src_h, img = (size_t)pairs * npx, map = (size_t)npx * entry;
+    for (int i = 0; i < 4; i++) {
+        if (!outs[i]) continue;
+        if (overlap(outs[i], d_raw_left, img, raw) || overlap(outs[i], d_raw_right, img, raw) ||
+            overlap(outs[i], d_map_left, img, map) || overlap(outs[i], d_map_right, img, map))
+            return sm_fail(SM_ERR_ARG, "%s: an output overlaps an input (every tap is read from the raw images)", me);
+        for (int j = 0; j < i; j++)
+            if (outs[j] && overlap(outs[i], outs[j], img)) return sm_fail(SM_ERR_ARG, "%s: outputs overlap", me);
+    }
+    SM_TRY(sm_use_device(plan->device));
+    const RectSide l = {d_raw_left, d_map_left, d_left, d_valid_left}, r = {d_raw_right, d_map_right, d_right, d_valid_right};
+    const bool vec = W % 4 == 0 && (((uintptr_t)d_map_left | (uintptr_t)d_map_right) & 15) == 0 &&
+                     (((uintptr_t)d_left | (uintptr_t)d_right | (uintptr_t)d_valid_left | (uintptr_t)d_valid_right) & 3) == 0;
+    const unsigned lanes = vec ? npx / 4 : npx;
+    const dim3 grid((lanes + 255) / 256, 2), block(256);
+#define SM_RECT_GO(REL, V) hipLaunchKernelGGL((k_rectify<REL, V>), grid, block, 0, (hipStream_t)stream, l, r, W, npx, src_w, \
+                                              src_h, pairs, interp == SM_INTERP_NEAREST ? 1 : 0, (u32)border)
+    if (map_format == SM_RMAP_REL16) { if (vec) SM_RECT_GO(true, 4); else SM_RECT_GO(true, 1); }
+    else                             { if (vec) SM_RECT_GO(false, 4); else SM_RECT_GO(false, 1); }
+#undef SM_RECT_GO
+    SM_LAUNCH_CHECK("k_rectify");
+    return SM_OK;
+}
+
+extern "C" int sm_rectify_map_build(sm_plan *plan, const sm_rectify_calib *calib, int map_format, void *d_map, void *stream)
+{
+    const char *me = "sm_rectify_map_build";
+    size_t entry;
+    if (!plan) return sm_fail(SM_ERR_ARG, "%s: plan is NULL", me);
+    if (!calib) return sm_fail(SM_ERR_ARG, "%s: calib is NULL", me);
+    if (!d_map) return sm_fail(SM_ERR_ARG, "%s: a map pointer is NULL", me);
+    // every field is needed: a shorter struct is refused; of a longer (newer) one the fields this library knows are taken
+    if (calib->struct_size < (int)sizeof(sm_rectify_calib))
+        return sm_fail(SM_ERR_ARG, "%s: calib->struct_size %d is not that of a sm_rectify_calib (this library: %d bytes)", me,
+                       calib->struct_size, (int)sizeof(sm_rectify_calib));
+    SM_TRY(rect_format(map_format, me, &entry));
+    SM_TRY(rect_plan_size(plan, me));
+    if (((uintptr_t)d_map & (entry / 2 - 1)) != 0)
+        return sm_fail(SM_ERR_ARG, "%s: the map pointer is not aligned to its %zu-byte elements", me, entry / 2);
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (sm_stream_capturing(st))
+        return sm_fail(SM_ERR_ARG, "%s: the stream is capturing and the builder reads a flag back (it synchronises): build "
+                       "the maps before the capture begins", me);
+    RectCalib c;
+    c.fx = calib->fx; c.fy = calib->fy; c.cx = calib->cx; c.cy = calib->cy;
+    c.k1 = calib->k1; c.k2 = calib->k2; c.p1 = calib->p1; c.p2 = calib->p2; c.k3 = calib->k3;
+    for (int i = 0; i < 9; i++) c.R[i] = calib->R[i / 3][i % 3];
+    c.nfx = calib->new_fx; c.nfy = calib->new_fy; c.ncx = calib->new_cx; c.ncy = calib->new_cy;
+    const int W = plan->width;
+    const unsigned npx = (unsigned)W * plan->height;
+    const dim3 grid((npx + 255) / 256), block(256);
+    if (map_format == SM_RMAP_ABS32) {
+        hipLaunchKernelGGL(k_rmap_build<false>, grid, block, 0, st, c, d_map, W, npx, (i32 *)nullptr);
+        SM_LAUNCH_CHECK("k_rmap_build");
+        return SM_OK;
+    }
+    // REL16: one flag, raised by every displacement that does not fit, read back
+    i32 *flag = nullptr, over = 0;
+    SM_HIP(hipMalloc((void **)&flag, sizeof(i32)));
+    hipError_t e = hipMemsetAsync(flag, 0, sizeof(i32), st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_rmap_build<true>, grid, block, 0, st, c, d_map, W, npx, flag);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&over, flag, sizeof(i32), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(flag);
+    if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "%s: building the map failed: %s", me, hipGetErrorString(e));
+    if (over)
+        return sm_fail(SM_ERR_ARG, "%s: a displacement of this calibration does not fit the int16 of SM_RMAP_REL16 (more than "
+                       "1023 pixels, or a point at infinity): build the map with SM_RMAP_ABS32 (the contents of d_map are "
+                       "not a map)", me);
+    return SM_OK;
 }

@@ -1,5 +1,5 @@
-// sm_sgm.h -- semi-global matching over the census data term (include/stereo_hip.h).  Included by
-// sm_census.hip only: the kernels read its descriptors, and its entry points launch them.
+// sm_sgm.hip -- semi-global matching over the census data term (include/stereo_hip.h).  The
+// kernels read the census workspace's descriptors, which sm_census_descriptors (sm_census.hip) writes.
 //
 // PARITY UNPINNED, like census: the reference has no SGM.  Definition (tests/sgm_reference.py is its executable form):
 //   A(p, d)   = the census window cost of sm_census_wta (d = 0 .. D - 1), A <= 48 * 625
@@ -23,10 +23,12 @@
 //                  step i + SGP_PF is loaded while step i is computed: the chain of a line is thousands of steps long,
 //                  and without that it waits on memory at every one.  d -+ 1 are ds_bpermute shifts of one lane's end
 //                  values; m_q is an in-lane min, four DPP min steps within each row of 16 lanes and four readlanes.
-//   k_sgm_sub_mask sub = 0 where the checked map is 0 (sm_sgm_lr).
+// (k_sgm_sub_mask, sub = 0 where the checked map is 0, is a post-filter: sm_filter.hip, sm_sub_mask_launch)
 
-#pragma once
 
+#include "sm_device.h"
+
+typedef unsigned long long u64;
 typedef unsigned short u16;
 
 #define SGM_MAX_SHIFTS 256
@@ -308,9 +310,176 @@ __global__ __launch_bounds__(256) void k_sgm_path(const u16 *__restrict__ A, i32
     }
 }
 
-// sub = 0 where the checked map is 0
-__global__ __launch_bounds__(256) void k_sgm_sub_mask(const i32 *__restrict__ web, int16_t *__restrict__ sub, long long n)
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+
+// 64, 128 or 256: the path kernel's lanes hold 1, 2 or 4 shifts each
+static int sgm_padded_shifts(const sm_plan *plan)
 {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n && web[i] == 0) sub[i] = 0;
+    return plan->num_shifts <= 64 ? 64 : plan->num_shifts <= 128 ? 128 : 256;
+}
+
+// one pair's data-term volume (u16) and aggregate volume (i32), Dp entries per pixel each
+size_t sm_sgm_volume_bytes(const sm_plan *plan)
+{
+    return (size_t)6 * plan->width * plan->height * sgm_padded_shifts(plan);
+}
+
+// the census workspace (descriptors, and the mirrored-order map if the plan has none yet) and one pair's volumes; on
+// failure the volumes are not kept (a census workspace reserved on the way stays)
+extern "C" int sm_plan_reserve_sgm(sm_plan *plan)
+{
+    if (!plan) return sm_fail(SM_ERR_ARG, "sm_plan_reserve_sgm: plan is NULL");
+    SM_TRY(sm_use_device(plan->device));
+    return sm_ws_reserve(plan, SM_WS_SET_SGM, "sm_plan_reserve_sgm");
+}
+
+// what every SGM entry checks besides its pointers (before any device call; the checks that need no plan first)
+static int sgm_args(const sm_plan *plan, int census_width, int p1, int p2, int paths, int pairs, const char *me)
+{
+    SM_TRY(sm_check_census_width(census_width, me));
+    if (paths != 4 && paths != 8) return sm_fail(SM_ERR_ARG, "%s: paths %d is not 4 or 8", me, paths);
+    if (p1 < 0 || p2 < p1 || p2 > 32767)
+        return sm_fail(SM_ERR_ARG, "%s: penalties p1 %d, p2 %d break 0 <= p1 <= p2 <= 32767", me, p1, p2);
+    SM_TRY(sm_check_pairs(plan, pairs, me));
+    return sm_check_reach(plan, SGM_MAX_SHIFTS, me);
+}
+
+// the data term of one pair into the A volume (S's memory holds the horizontal sums for n > 1)
+static int sgm_cost_launch(const sm_plan *plan, int cw, bool mirror, int pair, hipStream_t st)
+{
+    SgmCostGeom g;
+    g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts; g.Dp = sgm_padded_shifts(plan);
+    g.half = plan->square_width / 2;
+    g.side = (long long)plan->max_pairs * g.w * g.h;
+    g.pair = (long long)pair * g.w * g.h;
+    u16 *A = (u16 *)plan->d_sgm;
+    u16 *hs = g.half ? (u16 *)((char *)plan->d_sgm + (size_t)2 * g.w * g.h * g.Dp) : A;
+    const bool ghost = plan->border == SM_GHOST;
+    const void *fn;
+#define SGM_H(NW) (ghost ? (mirror ? (const void *)k_sgm_cost_h<NW, true, true> : (const void *)k_sgm_cost_h<NW, true, false>) \
+                         : (mirror ? (const void *)k_sgm_cost_h<NW, false, true> : (const void *)k_sgm_cost_h<NW, false, false>))
+    fn = cw == 7 ? SGM_H(2) : SGM_H(1);
+#undef SGM_H
+    {
+        void *args[] = {(void *)&plan->d_census, (void *)&hs, (void *)&g};
+        const hipError_t e = hipLaunchKernel(fn, dim3((g.w + SGC_XR - 1) / SGC_XR, (g.h + 3) / 4, g.Dp / 64),
+                                             dim3(64, 4), args, 0, st);
+        if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_sgm_cost_h failed: %s", hipGetErrorString(e));
+    }
+    if (!g.half) return SM_OK;
+    fn = ghost ? (const void *)k_sgm_cost_v<true> : (const void *)k_sgm_cost_v<false>;
+    void *args[] = {(void *)&hs, (void *)&A, (void *)&g};
+    const hipError_t e = hipLaunchKernel(fn, dim3((g.w + 3) / 4, (g.h + SGC_YR - 1) / SGC_YR, g.Dp / 64), dim3(64, 4),
+                                         args, 0, st);
+    if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_sgm_cost_v failed: %s", hipGetErrorString(e));
+    return SM_OK;
+}
+
+template <int K>
+static const void *sgm_path_ptr(int mode)
+{
+    return mode == SGM_FIRST ? (const void *)k_sgm_path<K, SGM_FIRST>
+         : mode == SGM_MID ? (const void *)k_sgm_path<K, SGM_MID> : (const void *)k_sgm_path<K, SGM_LAST>;
+}
+
+// the directions in stream order (integer sums: the order changes nothing); the last one emits the maps
+static int sgm_paths_launch(const sm_plan *plan, int p1, int p2, int paths, bool mirror, int pair, i32 *web, i32 *best,
+                            int16_t *sub, hipStream_t st)
+{
+    static const int dirs[8][2] = {{1, 0}, {0, 1}, {1, 1}, {-1, 1}, {1, -1}, {-1, -1}, {0, -1}, {-1, 0}};
+    static const int four[4] = {0, 1, 6, 7};
+    SgmPathGeom g;
+    g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts; g.Dp = sgm_padded_shifts(plan);
+    g.p1 = p1; g.p2 = p2;
+    g.mirror = mirror;
+    g.map = (long long)pair * g.w * g.h;
+    const int K = g.Dp / 64;
+    const u16 *A = (const u16 *)plan->d_sgm;
+    i32 *S = (i32 *)((char *)plan->d_sgm + (size_t)2 * g.w * g.h * g.Dp);
+    for (int r = 0; r < paths; r++) {
+        const int *dir = dirs[paths == 4 ? four[r] : r];
+        g.dx = dir[0]; g.dy = dir[1];
+        g.lines = g.dy == 0 ? g.h : g.dx == 0 ? g.w : g.w + g.h - 1;
+        const int mode = r == 0 ? SGM_FIRST : r == paths - 1 ? SGM_LAST : SGM_MID;
+        const void *fn = K == 1 ? sgm_path_ptr<1>(mode) : K == 2 ? sgm_path_ptr<2>(mode) : sgm_path_ptr<4>(mode);
+        // (paths >= 4: the last direction is never the first, so S always holds the other directions' sum)
+        void *args[] = {(void *)&A, (void *)&S, (void *)&web, (void *)&best, (void *)&sub, (void *)&g};
+        const hipError_t e = hipLaunchKernel(fn, dim3((g.lines + 3) / 4), dim3(256), args, 0, st);
+        if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_sgm_path failed: %s", hipGetErrorString(e));
+    }
+    return SM_OK;
+}
+
+// the left (or right-reference) SGM maps of `pairs` pairs, one pair at a time through the volumes
+static int sgm_pass(const sm_plan *plan, int cw, int p1, int p2, int paths, bool mirror, int pairs, i32 *web, i32 *best,
+                    int16_t *sub, hipStream_t st)
+{
+    for (int q = 0; q < pairs; q++) {
+        SM_TRY(sgm_cost_launch(plan, cw, mirror, q, st));
+        SM_TRY(sgm_paths_launch(plan, p1, p2, paths, mirror, q, web, best, sub, st));
+    }
+    return SM_OK;
+}
+
+extern "C" int sm_sgm_wta(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+                          int p1, int p2, int paths, int pairs, int32_t *d_web, int32_t *d_best, int16_t *d_sub,
+                          void *stream)
+{
+    const char *me = "sm_sgm_wta";
+    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
+    if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
+    SM_TRY(sgm_args(plan, census_width, p1, p2, paths, pairs, me));
+    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
+    if ((d_best && overlap(d_web, d_best, map)) || (d_sub && overlap(d_sub, d_web, map / 2, map)) ||
+        (d_sub && d_best && overlap(d_sub, d_best, map / 2, map)))
+        return sm_fail(SM_ERR_ARG, "%s: result maps overlap", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    SM_TRY(sm_ws_need(plan, SM_WS_SET_SGM, st, me));
+    SM_TRY(sm_census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
+    return sgm_pass(plan, census_width, p1, p2, paths, false, pairs, d_web, d_best, d_sub, st);
+}
+
+extern "C" int sm_sgm_wta_right(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right,
+                                int census_width, int p1, int p2, int paths, int pairs, int32_t *d_web_right,
+                                int32_t *d_best_right, void *stream)
+{
+    const char *me = "sm_sgm_wta_right";
+    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
+    if (!d_web_right) return sm_fail(SM_ERR_ARG, "%s: d_web_right is NULL", me);
+    SM_TRY(sgm_args(plan, census_width, p1, p2, paths, pairs, me));
+    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
+    if (d_best_right && overlap(d_web_right, d_best_right, map))
+        return sm_fail(SM_ERR_ARG, "%s: result maps overlap", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    SM_TRY(sm_ws_need(plan, SM_WS_SET_SGM, st, me));
+    SM_TRY(sm_census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
+    return sgm_pass(plan, census_width, p1, p2, paths, true, pairs, d_web_right, d_best_right, nullptr, st);
+}
+
+extern "C" int sm_sgm_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+                         int p1, int p2, int paths, int pairs, int max_diff, int32_t *d_web, int32_t *d_best,
+                         int32_t *d_web_right, int32_t *d_rejected, int16_t *d_sub, void *stream)
+{
+    const char *me = "sm_sgm_lr";
+    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
+    if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
+    if (max_diff < 0) return sm_fail(SM_ERR_ARG, "%s: max_diff %d is negative", me, max_diff);
+    SM_TRY(sgm_args(plan, census_width, p1, p2, paths, pairs, me));
+    SM_TRY(sm_check_lr_maps(plan, pairs, d_web, d_best, d_web_right, d_sub, d_rejected, me));
+    SM_TRY(sm_use_device(plan->device));
+    hipStream_t st = (hipStream_t)stream;
+    SM_TRY(sm_ws_need(plan, SM_WS_SET_SGM, st, me));
+    // the descriptors once for both directions; the right-reference map in natural order (the caller's, or the
+    // plan's mirrored-order map used as scratch), then the check, which gathers from it
+    i32 *right = d_web_right ? d_web_right : plan->d_web_lr;
+    SM_TRY(sm_census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
+    SM_TRY(sgm_pass(plan, census_width, p1, p2, paths, false, pairs, d_web, d_best, d_sub, st));
+    SM_TRY(sgm_pass(plan, census_width, p1, p2, paths, true, pairs, right, nullptr, nullptr, st));
+    SM_TRY(sm_lr_check_natural(plan, d_web, right, d_web, d_rejected, max_diff, pairs, st));
+    if (!d_sub) return SM_OK;
+    return sm_sub_mask_launch(d_web, d_sub, (long long)pairs * plan->width * plan->height, st);
 }

@@ -310,19 +310,14 @@ static const void *refine_ptr(bool ssd, bool ghost)
 extern "C" int sm_cost_refine(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int cost,
                               int pairs, const int32_t *d_web, int16_t *d_sub, int32_t *d_costs, void *stream)
 {
-    if (!plan) return sm_fail(SM_ERR_ARG, "sm_cost_refine: plan is NULL");
-    if (pairs < 1 || pairs > plan->max_pairs)
-        return sm_fail(SM_ERR_ARG, "sm_cost_refine: pairs %d outside 1..%d", pairs, plan->max_pairs);
+    SM_TRY(sm_check_pairs(plan, pairs, "sm_cost_refine"));
     if (!d_gray_left || !d_gray_right || !d_web || !d_sub)
         return sm_fail(SM_ERR_ARG, "sm_cost_refine: NULL argument");
     if (cost != SM_COST_SAD && cost != SM_COST_SSD)
         return sm_fail(SM_ERR_ARG, "sm_cost_refine: cost %d is neither SM_COST_SAD nor SM_COST_SSD", cost);
     const int half = plan->square_width / 2, n = 2 * half + 1;
-    if (n > 25 || plan->num_shifts > 512)
-        return sm_fail(SM_ERR_ARG, "sm_cost_refine: built for windows up to 25x25 and at most 512 shifts "
-                       "(got %dx%d, %d)", n, n, plan->num_shifts);
-    const hipError_t es = hipSetDevice(plan->device);
-    if (es != hipSuccess) return sm_fail(SM_ERR_HIP, "sm_cost_refine: %s", hipGetErrorString(es));
+    SM_TRY(sm_check_reach(plan, 512, "sm_cost_refine"));
+    SM_TRY(sm_use_device(plan->device));
 
     RefineGeom g;
     g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts;

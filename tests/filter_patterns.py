@@ -7,7 +7,7 @@ import numpy as np
 
 from tests import filter_reference as fr
 
-TILE_W, TILE_H = 64, 16            # the kernels' tile (sm_filter.h: FLT_TW, FLT_TH)
+TILE_W, TILE_H = 64, 16            # the kernels' tile (sm_filter.hip: FLT_TW, FLT_TH)
 
 
 def random_map(w, h, dtype, seed, invalid=0.3, lo=1, hi=6, negative=False):

@@ -7,7 +7,7 @@ import numpy as np
 
 from tests import interp_reference as ir
 
-SEG_H, CHUNK_W = 64, 64            # the kernels' pieces (sm_interp.h: ITP_SEG rows of a line, ITP_CW pixels of a row)
+SEG_H, CHUNK_W = 64, 64            # the kernels' pieces (sm_interp.hip: ITP_SEG rows of a line, ITP_CW pixels of a row)
 # on and around one and two pieces, both ways (test_interp_gpu.py adds the post-filters' sizes)
 SIZES = [(63, 63), (64, 64), (65, 65), (127, 129), (129, 127), (128, 128), (1, 130), (130, 1), (2, 65), (65, 2),
          (200, 70), (70, 200)]
