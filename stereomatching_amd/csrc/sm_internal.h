@@ -141,7 +141,7 @@ __device__ __forceinline__ void sm_xcd_tile(int tiles_x, int tiles_y, int &tx, i
 }
 #endif
 
-// error plumbing (sm_api.hip)
+// error plumbing (sm_fail: sm_api.hip)
 int sm_fail(int code, const char *fmt, ...);
 #define SM_HIP(call)                                                          \
     do {                                                                      \
@@ -162,7 +162,13 @@ int sm_fail(int code, const char *fmt, ...);
 
 // sm_api.hip
 int sm_use_device(int device);                    // hipSetDevice, failure as SM_ERR_HIP
-bool sm_stream_capturing(hipStream_t st);         // is `st` recording into a graph?
+bool sm_stream_capturing(hipStream_t st, unsigned long long *id = nullptr);   // is `st` recording into a graph (and which)?
+// synchronise `st` and return the plan's flags (d_flags) as they were at that point; those in clear_mask are reset
+int sm_read_flags(sm_plan *plan, hipStream_t st, int clear_mask, i32 out[4]);
+// sm_plan_create: the code objects of a unit's kernels resolved at set-up, not by the first timed launch
+void sm_edges_resolve_kernels(bool ghost);        // sm_edges.hip
+void sm_run_resolve_kernels(void);                // sm_run.hip
+void sm_step3_resolve_kernels(void);              // sm_step3.hip
 
 // ---------------------------------------------------------------------------
 // The lazily allocated workspaces: one table in sm_api.hip, one row per buffer (the sm_plan member, its bytes for
@@ -196,7 +202,8 @@ size_t sm_itp_bytes(const sm_plan *plan);         // sm_interp.hip (its tile con
 size_t sm_sgm_volume_bytes(const sm_plan *plan);  // sm_sgm.hip (its padded shift count decides)
 
 // ---------------------------------------------------------------------------
-// Argument rules that more than one entry point applies (sm_api.hip).  Each reports as `me`, the entry point's name.
+// Argument rules that more than one entry point applies (sm_api.hip; the two on the decision tables: sm_edges.hip).
+// Each reports as `me`, the entry point's name.
 // ---------------------------------------------------------------------------
 // do [a, a + a_bytes) and [b, b + b_bytes) share a byte?  (b_bytes = 0: as many as a)
 static inline bool overlap(const void *a, const void *b, size_t a_bytes, size_t b_bytes = 0)
@@ -204,6 +211,12 @@ static inline bool overlap(const void *a, const void *b, size_t a_bytes, size_t 
     return (uintptr_t)a < (uintptr_t)b + (b_bytes ? b_bytes : a_bytes) && (uintptr_t)b < (uintptr_t)a + a_bytes;
 }
 int sm_check_pairs(const sm_plan *plan, int pairs, const char *me);       // plan is NULL; pairs outside 1..max_pairs
+int sm_check_pairs_loaded(const sm_plan *plan, int pairs, const char *me);   // more pairs than the loaded edges are of
+int sm_check_threshold(double threshold, const char *me);                 // outside 0..1 (the reference's message: no name in it)
+int sm_check_web_type(const sm_plan *plan, int web_type, const char *me); // SM_WEB_I32 / U16 / U8, and the shifts fit it
+bool sm_edge_tables_prepared(const sm_plan *plan, double threshold);      // the decision tables are those of `threshold`
+int sm_check_tables_prepared(const sm_plan *plan, double threshold, const char *me);   // ... refused where they are not
+                                                                          // and `me` is being captured (no set-up there)
 int sm_check_reach(const sm_plan *plan, int max_shifts, const char *me);  // windows up to 25x25, at most max_shifts shifts
 int sm_check_census_width(int census_width, const char *me);              // 3, 5 or 7
 int sm_check_map_type(int map_type, const char *me, size_t *elem);        // SM_MAP_I32 / SM_MAP_I16 and its element size
@@ -211,6 +224,16 @@ int sm_check_map_type(int map_type, const char *me, size_t *elem);        // SM_
 // "d_rejected overlaps a map"
 int sm_check_lr_maps(const sm_plan *plan, int pairs, const int32_t *d_web, const int32_t *d_best,
                      const int32_t *d_web_right, const int16_t *d_sub, const int32_t *d_rejected, const char *me);
+
+// sm_edges.hip, for sm_plan_geometry: ext rows a wave of this plan's edge kernel walks down
+int sm_edges_rows_per_wave(const sm_plan *plan);
+
+// sm_run.hip.  The lanes of pipelined calls, for a call of another unit that reads or rewrites the packed images on
+// `st`: `st` waits for every pipelined call before it (nothing inside a capture, where they have joined `st`), and
+// the next pipelined call waits for `st` as after any sequential launch
+int sm_lanes_fence(sm_plan *plan, hipStream_t st);
+void sm_lanes_release(sm_plan *plan);
+void sm_timing_free(sm_plan *plan);               // the timing events (sm_plan_time_kernels(plan, 0), sm_plan_destroy)
 
 // sm_lr.hip, for the other stages: the per-pair counts zeroed by k_lr_zero_counts (a kernel: a captured memset of them
 // replayed wrongly), and k_lr_check on a right-reference map in natural order (the rejection counts zeroed first)
@@ -230,6 +253,8 @@ struct MatchLaunch {
     MatchGeom g;                        // plan->g with vec_ok / web_bytes of this launch
     hipEvent_t ev_begin, ev_end;        // non-null: attach these events to the dispatch itself
 };
+// sm_run.hip: plan->g for maps of web_bytes an element (vec_ok cleared unless both are aligned for int4 stores), no events
+MatchLaunch sm_match_launch_args(const sm_plan *plan, const void *d_web, const void *d_best, int web_bytes);
 int sm_bs_launch(const sm_plan *plan, const MatchLaunch &l, int pairs, i32 *d_web, i32 *d_best, hipStream_t st);
 int sm_bs_prepare(sm_plan *plan);        // set-up launch: code object loaded before the first real one
 

@@ -17,8 +17,6 @@
 
 #include "sm_device.h"
 
-#include <string.h>
-
 #include <algorithm>
 
 // ---------------------------------------------------------------------------
@@ -208,37 +206,12 @@ extern "C" int sm_plan_reserve_lr(sm_plan *plan)
     return sm_ws_reserve(plan, SM_WS_SET_LR, "sm_plan_reserve_lr");
 }
 
-// A call that reads or rewrites the packed images runs on `stream`; the pipelined calls before it may
-// still be running on the plan's lanes (sm_plan_set_pipelined, sm_run_after): `stream` waits for all of
-// them.  Inside a capture the captured calls have joined `stream` already (and events of eager calls
-// must not be waited for there).
-static int lr_fence_lanes(sm_plan *plan, hipStream_t st)
-{
-    if (sm_stream_capturing(st)) return SM_OK;
-    for (int i = 0; i < 4; i++)
-        if (plan->ev_free_set[i]) SM_HIP(hipStreamWaitEvent(st, plan->ev_free[i], 0));
-    return SM_OK;
-}
-
-// ... and the next pipelined call must not overtake it: as after any sequential launch, its lanes wait for
-// `stream` first (a captured one leaves `stream` after this call, not where the previous captured call ended)
-static void lr_release_lanes(sm_plan *plan)
-{
-    plan->unfenced = 1;
-    plan->cap_live = 0;
-}
-
 // one launch of the plan's match kernel over other packed images (the plan is not modified)
 static int lr_match(const sm_plan *plan, u32 *ext, int pairs, i32 *d_web, i32 *d_best, hipStream_t st)
 {
     sm_plan view = *plan;
     view.d_ext = ext;
-    MatchLaunch l;
-    l.g = plan->g;
-    if (((uintptr_t)d_web & 15) != 0 || ((uintptr_t)d_best & 15) != 0) l.g.vec_ok = 0;
-    l.g.web_bytes = 4;
-    l.ev_begin = l.ev_end = nullptr;
-    return sm_match_launch(&view, l, pairs, d_web, d_best, st);
+    return sm_match_launch(&view, sm_match_launch_args(plan, d_web, d_best, 4), pairs, d_web, d_best, st);
 }
 
 static int lr_mirror(sm_plan *plan, int pairs, hipStream_t st)
@@ -294,17 +267,15 @@ extern "C" int sm_match_wta_right(sm_plan *plan, int pairs, int32_t *d_web_right
     const char *me = "sm_match_wta_right";
     if (!d_web_right) return sm_fail(SM_ERR_ARG, "%s: d_web_right is NULL", me);
     SM_TRY(sm_check_pairs(plan, pairs, me));
-    if (pairs > plan->pairs_loaded)
-        return sm_fail(SM_ERR_ARG, "%s: %d pairs requested but edges of only %d are loaded "
-                       "(call sm_find_edges or sm_load_edges first)", me, pairs, plan->pairs_loaded);
+    SM_TRY(sm_check_pairs_loaded(plan, pairs, me));
     const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
     if (d_best_right && overlap(d_web_right, d_best_right, map))
         return sm_fail(SM_ERR_ARG, "%s: d_web_right and d_best_right overlap", me);
     SM_TRY(sm_use_device(plan->device));
     hipStream_t st = (hipStream_t)stream;
     SM_TRY(sm_ws_need(plan, SM_WS_SET_LR, st, me));
-    SM_TRY(lr_fence_lanes(plan, st));
-    lr_release_lanes(plan);
+    SM_TRY(sm_lanes_fence(plan, st));
+    sm_lanes_release(plan);
     SM_TRY(lr_mirror(plan, pairs, st));
     // the maps come out in mirrored order, and are turned round in place
     SM_TRY(lr_match(plan, plan->d_ext_lr, pairs, d_web_right, d_best_right, st));
@@ -338,19 +309,17 @@ extern "C" int sm_run_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_
 {
     const char *me = "sm_run_lr";
     if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
-    if (!(threshold >= 0.0 && threshold <= 1.0)) return sm_fail(SM_ERR_ARG, "error: threshold must be between 0 and 1");
+    SM_TRY(sm_check_threshold(threshold, me));
     if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
     if (max_diff < 0) return sm_fail(SM_ERR_ARG, "%s: max_diff %d is negative", me, max_diff);
     SM_TRY(sm_check_pairs(plan, pairs, me));
     SM_TRY(sm_check_lr_maps(plan, pairs, d_web, d_best, d_web_right, nullptr, d_rejected, me));
     SM_TRY(sm_use_device(plan->device));
     hipStream_t st = (hipStream_t)stream;
-    if (sm_stream_capturing(st) && !(plan->tab_valid && memcmp(&plan->tab_threshold, &threshold, sizeof threshold) == 0))
-        return sm_fail(SM_ERR_ARG, "%s: the decision tables of threshold %g are not prepared and the stream is capturing: "
-                       "call sm_plan_prepare_threshold(plan, threshold, stream) before the capture begins", me, threshold);
+    if (sm_stream_capturing(st)) SM_TRY(sm_check_tables_prepared(plan, threshold, me));
     SM_TRY(sm_ws_need(plan, SM_WS_SET_LR, st, me));
-    SM_TRY(lr_fence_lanes(plan, st));
-    lr_release_lanes(plan);
+    SM_TRY(sm_lanes_fence(plan, st));
+    sm_lanes_release(plan);
     // edges into the plan's packed images (as sm_run; they stay loaded), the left match, the mirrored images,
     // the right match into the mirrored-order map, and the check, which gathers from that map
     SM_TRY(sm_find_edges(plan, d_gray_left, d_gray_right, threshold, pairs, nullptr, nullptr, stream));

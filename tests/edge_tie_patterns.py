@@ -6,7 +6,7 @@ An edge decision of src/stereo.c:16-70 compares the means of two three-pixel sid
     |ma - mb| > clamp(T * (ma + mb) / 2, 0, 1),     m = (p0/256 + p1/256 + p2/256) / 3.0   (doubles),
 
 so for in-image pixels it depends only on the two integer side sums (Sa, Sb) in [0, 765].  The edge kernels of
-csrc/sm_api.hip decide it with an f32 prefilter,
+csrc/sm_edges.hip decide it with an f32 prefilter,
 
     F = fma(Sa + Sb, -(float)(T / 2), |Sa - Sb|)     (one rounding to f32),
 

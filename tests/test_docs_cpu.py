@@ -75,7 +75,7 @@ def test_integration_lists_the_translation_units_that_are_built():
     named = set(re.findall(r"`(sm_[a-z_0-9]+\.hip)`", para))
     assert named == set(build.SOURCES), (sorted(named ^ set(build.SOURCES)))
     words = {10: "ten", 11: "eleven", 12: "twelve", 13: "thirteen", 14: "fourteen", 15: "fifteen", 16: "sixteen",
-             17: "seventeen", 18: "eighteen", 19: "nineteen", 20: "twenty", 21: "twenty-one", 22: "twenty-two"}
+             17: "seventeen", 18: "eighteen", 19: "nineteen", 20: "twenty", 21: "twenty-one", 22: "twenty-two", 23: "twenty-three"}
     assert f"is {words[len(build.SOURCES)]} translation units" in para
     mk = (ROOT / "Makefile").read_text()
     kernels = re.search(r"^KERNELS := (.*)$", mk, re.M).group(1).split()

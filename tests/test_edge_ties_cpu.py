@@ -1,4 +1,4 @@
-"""CPU proofs behind test_edge_ties_gpu.py (tests/edge_tie_patterns.py): the margin argument of csrc/sm_api.hip's
+"""CPU proofs behind test_edge_ties_gpu.py (tests/edge_tie_patterns.py): the margin argument of csrc/sm_edges.hip's
 f32 prefilter, the numpy restatement of the double decision against the oracle and against digests of the compiled
 reference, and that the near-tie images reach every band pair in every orientation and every kernel position they
 are meant to."""

@@ -1337,7 +1337,7 @@ def test_soak_random_pipelines(hip):
 def edges4_read_columns(w, g):
     """Host restatement of k_edges_ext4's toroidal address arithmetic: for every lane of
     the launch grid, the first source column of its dword load (xq) and of its single
-    neighbour byte (xn).  Mirrors csrc/sm_api.hip; the kernel must never read a column
+    neighbour byte (xn).  Mirrors csrc/sm_edges.hip; the kernel must never read a column
     outside [0, w)."""
     ext_px = g["ext_words"] * 32
     row = g["ext_words"] * 8

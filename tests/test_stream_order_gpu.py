@@ -1,4 +1,4 @@
-"""Stream ordering of the calls that run on a plan's two internal lanes (run_on_lanes in csrc/sm_api.hip: sm_run_after on
+"""Stream ordering of the calls that run on a plan's two internal lanes (run_on_lanes in csrc/sm_run.hip: sm_run_after on
 small launches, sm_run on a pipelined plan).  Such a call is ordered by events alone -- `inputs_ready`, the release
 events, the `ev_inputs` fence, the fork events of a capture -- so a missing or misplaced wait only shows when the work
 on the other side of the event is still running when the lane starts.  Every producer and consumer here is therefore
