@@ -298,6 +298,7 @@ __global__ __launch_bounds__(SMN_THREADS) void k_census_wta(const u32 *__restric
         // ---- horizontal window sums (packed u16: shifts 2k | 2k + 1), first-wins keys A << 16 | d, merge over the nl
         // lanes.  A shift outside the launch's range gets 0x8000 added to its sum (A <= 30000: the field cannot wrap,
         // and the key loses to every real one).
+        // (A = 30000 in a launch's first and last lane and just past its range: tests/test_census_extremes_gpu.py)
         u32 key[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
         if (out_grp) {
             for (int k = 0; k < 4; k++) {

@@ -6,6 +6,7 @@
 //   L_r(p, d) = A(p, d) where q = p - r lies outside the image (paths never wrap, in either border mode), else
 //               A(p, d) + min(L_r(q, d), L_r(q, d -+ 1) + P1, m_q + P2) - m_q,  m_q = min_k L_r(q, k);
 //               terms with d -+ 1 outside 0 .. D - 1 dropped.  A <= L_r <= A + P2 <= 62767 (u16 bound).
+//               (62767 is reached by tests/test_census_extremes_gpu.py test_sgm_at_its_u16_and_key_bounds)
 //   S(p, d)   = sum of L_r over the 4 or 8 directions r; best = min_d S, web = 1 + the first d reaching it;
 //   sub       = sm_cost_refine's SSD (parabola) rule on S(s-2), S(s-1), S(s), s = web.
 //
@@ -280,6 +281,7 @@ __global__ __launch_bounds__(256) void k_sgm_path(const u16 *__restrict__ A, i32
                 SgmVec<K>::store_s(s0 + i * vstep, t);
             } else {
                 // S <= 8 * 62767 < 2^19: keys S << 8 | d, the first d wins a tie; entries d >= D lose to every real one
+                // (S = 8 * 62767 and a padded range: tests/test_census_extremes_gpu.py test_sgm_at_its_u16_and_key_bounds)
                 i32 tot[K], key = 0x7fffffff;
 #pragma unroll
                 for (int k = 0; k < K; k++) {
