@@ -54,6 +54,8 @@ $(DEVSTAMP): FORCE
 FORCE:
 stereomatching_amd/obj/product/%.o: $(CSRC)/%.hip $(CSRC)/sm_internal.h $(CSRC)/sm_match_bs_kernel.h $(CSRC)/sm_cost.h $(CSRC)/sm_device.h include/stereo_hip.h $(DEVSTAMP)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+# (the reprojection stage is built in the rectification's unit, which includes it)
+stereomatching_amd/obj/product/sm_rectify.o: $(CSRC)/sm_reproject.hip
 $(DEVLIB): $(DEVOBJ)
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC $^ -o $@
 

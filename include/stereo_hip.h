@@ -670,6 +670,64 @@ int sm_rectify_map_build(sm_plan *plan, const sm_rectify_calib *calib, int map_f
 /* adds: d_map = 0 where d_valid = 0, in place */
 int sm_valid_mask(sm_plan *plan, void *d_map, int map_type, const uint8_t *d_valid, int pairs, void *stream);
 
+/* ---- reprojection: PARITY UNPINNED ---------------------------------------- *
+ * New work (no reference counterpart): the stage BEHIND the matchers, from a disparity map in shifts to
+ * depth in metres and 3-D points: map build -> rectify -> any matcher -> check -> filters -> interpolate -> reproject.
+ *   map: [pairs][H][W] of type SM_MAP_I32 (a web map) or SM_MAP_I16 (a sub map, 1/16 shift), the plan's W and H; a
+ *     pixel is VALID iff its value v != 0; any int32 / int16 value is legal.  Its disparity is the exact double
+ *     d = v - 1 (SM_MAP_I32) or d = v / 16 - 1 (SM_MAP_I16).
+ *   Q: 16 doubles, row-major 4 x 4, read from a HOST array at call time and passed to the kernels by value (no
+ *     upload, no synchronisation; the array may be reused at once).  Every entry must be finite.
+ *     [X Y Z Wh]' = Q [x y d 1]' with x, y the pixel's integer coordinates.
+ *   arithmetic, IEEE double, every operation rounded on its own (nothing fused, nothing reassociated), for each row i:
+ *       r_i = ((Qi0 x + Qi1 y) + Qi2 d) + Qi3          (left to right; r_3 = Wh)
+ *       Xf = (float)(r_0 / Wh), Yf = (float)(r_1 / Wh), Zf = (float)(r_2 / Wh)
+ *     division and double -> float round to nearest even.  (A result that is subnormal in float may be flushed to
+ *     zero on the device.)
+ *   a pixel is KEPT iff it is valid, Xf, Yf and Zf are all finite (Wh = 0 and float overflow drop it), and
+ *     z_min <= Zf <= z_max (float; -inf / +inf: no gate; a NaN bound or z_min > z_max is refused).
+ *   sm_reproject (dense): d_depth [pairs][H][W] receives Zf, d_xyz [pairs][H][W][3] the interleaved Xf, Yf, Zf; a pixel
+ *     that is not kept receives the float `missing` (0, +inf, a NaN, ...) in every channel.  Either may be NULL, not
+ *     both.  d_count: NULL or one int32 per pair, the number of kept pixels.  Outputs must not overlap the map or one
+ *     another.
+ *   sm_point_cloud (compacted): the kept pixels of each pair in RASTER ORDER (y outer, x inner); the k-th of pair p
+ *     writes the record d_points[p][k] = (Xf, Yf, Zf, I) of a [pairs][capacity][4] float array, I = (float)d_gray[p][y][x]
+ *     (d_gray: u8 [pairs][H][W], typically the rectified left image) or 0.0f where d_gray is NULL, and, where d_index
+ *     is not NULL, d_index[p][k] = y W + x ([pairs][capacity] int32).  d_count[p] (required) ALWAYS receives the total
+ *     number of kept pixels of pair p, also beyond `capacity`; records and indices with k >= capacity are not written,
+ *     slots count <= k < capacity are left untouched.  capacity >= 0; d_points may be NULL only with capacity = 0 (a
+ *     count-only call).  The order makes the result deterministic: two runs give identical bytes.
+ *   sm_reproject_q (host only; no plan, no device): the Q of a rectified rig.  This library's maps say that pixel x of
+ *     the first image matches pixel x + d of the second; with X_second = X_first + t, t = baseline,
+ *     f = first->new_fx, c1 = first->new_cx / new_cy, c2x = second->new_cx, each entry one or two rounded operations:
+ *       r = f / first->new_fy;
+ *       Q = [ 1  0  0    -c1x               ]      so that  Z = f t / (d - (c2x - c1x)),  X = (x - c1x) Z / f,
+ *           [ 0  r  0    -(c1y r)           ]               Y = (y - c1y) Z / new_fy,
+ *           [ 0  0  0     f                 ]      in the baseline's unit.
+ *           [ 0  0  1/t  -((c2x - c1x) / t) ]
+ *     Refused: a NULL pointer, a struct_size too short, a baseline that is 0 or not finite, new_fx / new_fy of the
+ *     first calibration not positive and finite.
+ * Pointers are aligned to their elements.  Arguments are checked before any device call; a refusal names the
+ * function.  All calls run in `stream` order and use nothing the pipelined lanes use.  sm_reproject needs no workspace
+ * and can always be captured.  sm_point_cloud's workspace is one int32 per tile of 1024 pixels and pair slot,
+ *     4 * max_pairs * ceil(W * H / 1024) bytes
+ * (tile counts, turned into offsets in place); allocated by sm_plan_reserve_cloud or, without it, by the first
+ * sm_point_cloud (a hipMalloc, which synchronises the device; SM_ERR_NOMEM on failure), counted in
+ * sm_plan_workspace_bytes from then on, freed by sm_plan_destroy; a plan that never builds a cloud allocates nothing.
+ * STREAM CAPTURE: sm_point_cloud once sm_plan_reserve_cloud has been called; before, it is refused with SM_ERR_ARG, a
+ * message naming it, and the capture valid.  Images of up to 2^30 pixels.                                            */
+/* adds: depth and / or XYZ of every pixel of a disparity map; d_depth or d_xyz and d_count may be NULL */
+int sm_reproject(sm_plan *plan, const void *d_map, int map_type, const double q[16], float z_min, float z_max,
+                 float missing, int pairs, float *d_depth, float *d_xyz, int32_t *d_count, void *stream);
+/* adds: the kept pixels of a disparity map as (X, Y, Z, I) records in raster order; d_gray and d_index may be NULL */
+int sm_point_cloud(sm_plan *plan, const void *d_map, int map_type, const double q[16], float z_min, float z_max,
+                   const uint8_t *d_gray, int pairs, int capacity, float *d_points, int32_t *d_index, int32_t *d_count,
+                   void *stream);
+/* adds: allocates sm_point_cloud's workspace now; idempotent */
+int sm_plan_reserve_cloud(sm_plan *plan);
+/* adds: the reprojection matrix of a rectified pair of calibrations and a baseline; host only */
+int sm_reproject_q(const sm_rectify_calib *first, const sm_rectify_calib *second, double baseline, double q[16]);
+
 /* ---- step 3 -------------------------------------------------------------- *
  * fill_web_holes (src/stereo.cu:235-256): every pixel that is 0 becomes the
  * truncated mean of its four flat-index neighbours.  The reference's pointer

@@ -22,6 +22,8 @@ LIB = PKG / "libstereo_hip.so"
 SOURCES = ["sm_match_bs_ds8.hip", "sm_match_bs.hip", "sm_match_bs_duo8.hip", "sm_match_bs_duo.hip", "sm_match_bs_ds4.hip",
            "sm_api.hip", "sm_edges.hip", "sm_run.hip", "sm_step3.hip", "sm_match.hip", "sm_cost.hip", "sm_cost_qs.hip", "sm_cost_pc.hip", "sm_cost_mfma.hip", "sm_cost_strip.hip", "sm_gather.hip", "sm_lr.hip",
            "sm_subpix.hip", "sm_census.hip", "sm_sgm.hip", "sm_filter.hip", "sm_interp.hip", "sm_rectify.hip"]
+# files a source includes beside HEADERS: the reprojection stage is built in the rectification's unit
+INCLUDED = {"sm_rectify.hip": [CSRC / "sm_reproject.hip"]}
 HEADERS = [CSRC / "sm_internal.h", CSRC / "sm_match_bs_kernel.h", CSRC / "sm_cost.h", CSRC / "sm_device.h", ROOT / "include" / "stereo_hip.h"]
 OBJDIR = PKG / "obj"
 HIPCC_FLAGS = [
@@ -74,7 +76,7 @@ def _compile_and_link(out: Path, objdir: Path, flags=(), verbose: bool = False, 
 
     def one(src: str) -> Path:
         obj = objdir / (Path(src).stem + ".o")
-        if not _stale(obj, [CSRC / src, *HEADERS]):
+        if not _stale(obj, [CSRC / src, *INCLUDED.get(src, []), *HEADERS]):
             return obj
         cmd = [_hipcc(), *common, "-c", str(CSRC / src), "-o", str(obj)]
         if verbose:
@@ -90,7 +92,7 @@ def _compile_and_link(out: Path, objdir: Path, flags=(), verbose: bool = False, 
 
 
 def build_hip(force: bool = False, verbose: bool = False) -> Path:
-    deps = [CSRC / s for s in SOURCES] + HEADERS
+    deps = [CSRC / s for s in SOURCES] + [f for fs in INCLUDED.values() for f in fs] + HEADERS
     if force or _stale(LIB, deps):
         _compile_and_link(LIB, OBJDIR / "product", verbose=verbose)
     return LIB
@@ -101,7 +103,7 @@ def build_diag(verbose: bool = False, name: str = "stamps", flags=()) -> Path:
     time stamps); a diagnostic build, loaded only by tools/wave_timeline.py."""
     out = ROOT / "tools" / "diag" / f"libstereo_hip_{name}.so"
     out.parent.mkdir(parents=True, exist_ok=True)
-    deps = [CSRC / s for s in SOURCES] + HEADERS
+    deps = [CSRC / s for s in SOURCES] + [f for fs in INCLUDED.values() for f in fs] + HEADERS
     if _stale(out, deps):
         _compile_and_link(out, OBJDIR / f"diag_{name}", ["-DSM_STAMPS", *flags], verbose)
     return out

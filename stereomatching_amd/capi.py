@@ -42,8 +42,10 @@ def declared_symbols() -> list[str]:
     return sorted(set(re.findall(r"\b(sm_[a-z0-9_]+)\s*\(", text)))
 
 
-_vp, _int, _sz, _dbl = C.c_void_p, C.c_int, C.c_size_t, C.c_double
+_vp, _int, _sz, _dbl, _flt = C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_float
 _intp = C.POINTER(C.c_int)
+_dblp = C.POINTER(C.c_double)      # a reprojection matrix: an instance of Q16 (or None)
+Q16 = C.c_double * 16
 
 class Geometry(C.Structure):
     """sm_geometry of include/stereo_hip.h"""
@@ -174,7 +176,22 @@ _SIGNATURES = {
     "sm_rectify": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "sm_rectify_map_build": (_int, [_vp, C.POINTER(RectifyCalib), _int, _vp, _vp]),
     "sm_valid_mask": (_int, [_vp, _vp, _int, _vp, _int, _vp]),
+    "sm_reproject": (_int, [_vp, _vp, _int, _dblp, _flt, _flt, _flt, _int, _vp, _vp, _vp, _vp]),
+    "sm_point_cloud": (_int, [_vp, _vp, _int, _dblp, _flt, _flt, _vp, _int, _int, _vp, _vp, _vp, _vp]),
+    "sm_plan_reserve_cloud": (_int, [_vp]),
+    "sm_reproject_q": (_int, [C.POINTER(RectifyCalib), C.POINTER(RectifyCalib), _dbl, _dblp]),
 }
+
+
+def q16(q) -> "Q16":
+    """A reprojection matrix as the c_double * 16 the C ABI takes: 16 numbers, or 4 rows of 4 (lists, numpy, torch)"""
+    if isinstance(q, Q16):
+        return q
+    q = q.tolist() if hasattr(q, "tolist") else list(q)
+    flat = [v for row in q for v in (row.tolist() if hasattr(row, "tolist") else row)] if len(q) == 4 else q
+    if len(flat) != 16:
+        raise ValueError(f"q: need 16 numbers (or 4 rows of 4), got {len(flat)}")
+    return Q16(*(float(v) for v in flat))
 
 
 def _load() -> C.CDLL:

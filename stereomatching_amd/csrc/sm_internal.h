@@ -115,6 +115,7 @@ struct sm_plan {
     i32 *d_filter;       // sm_filter.hip, speckle filter: labels [max_pairs][H][W] int32, then component sizes [max_pairs][H][W] int32
     i32 *d_interp;       // sm_interp.hip: per pair six directional maps [6][H][W], line carries [6][segments][W + H - 1], row
                          // carries [2][H][chunks], 4 bytes an element (layout at the top of sm_interp.hip)
+    i32 *d_cloud;        // sm_reproject.hip, sm_point_cloud: kept pixels per tile of 1024 pixels, then their offsets: [max_pairs][tiles]
     int cost_lds_raised; // sm_cost_wta: the LDS limit of this plan's four-wave SAD kernel is raised (on `device`)
     char describe[512];
 };
@@ -176,7 +177,7 @@ void sm_step3_resolve_kernels(void);              // sm_step3.hip
 // adds a member, a row and a set, and nothing else.  A row of 0 bytes is never allocated and never missing.
 // ---------------------------------------------------------------------------
 enum { SM_WS_NARROW, SM_WS_EXT_LR, SM_WS_WEB_LR, SM_WS_GRAY_LR, SM_WS_CENSUS, SM_WS_SGM, SM_WS_FILTER, SM_WS_INTERP,
-       SM_WS_ROWS };
+       SM_WS_CLOUD, SM_WS_ROWS };
 struct sm_ws_set {
     unsigned rows;             // bit r = row r
     const char *what;          // "the workspace of <what> is not allocated"
@@ -190,6 +191,7 @@ static const sm_ws_set SM_WS_SET_CENSUS = {1u << SM_WS_CENSUS | 1u << SM_WS_WEB_
 static const sm_ws_set SM_WS_SET_SGM = {1u << SM_WS_SGM, "SGM", "sm_plan_reserve_sgm", &SM_WS_SET_CENSUS};
 static const sm_ws_set SM_WS_SET_FILTER = {1u << SM_WS_FILTER, "the speckle filter", "sm_plan_reserve_filter", nullptr};
 static const sm_ws_set SM_WS_SET_INTERP = {1u << SM_WS_INTERP, "the interpolation", "sm_plan_reserve_interp", nullptr};
+static const sm_ws_set SM_WS_SET_CLOUD = {1u << SM_WS_CLOUD, "the point cloud", "sm_plan_reserve_cloud", nullptr};
 // all or nothing: on a failure every buffer this call allocated is freed and the plan is as before (but `first` stays)
 int sm_ws_reserve(sm_plan *plan, const sm_ws_set &set, const char *me);
 // from an entry point: nothing if present; SM_ERR_ARG naming set.reserve if `st` is capturing; otherwise reserve
@@ -200,6 +202,7 @@ size_t sm_lr_map_bytes(const sm_plan *plan);      // one int32 map of max_pairs 
 size_t sm_lr_gray_batch_bytes(const sm_plan *plan);   // one batch of mirrored gray images, rounded up to 256 bytes
 size_t sm_itp_bytes(const sm_plan *plan);         // sm_interp.hip (its tile constants decide)
 size_t sm_sgm_volume_bytes(const sm_plan *plan);  // sm_sgm.hip (its padded shift count decides)
+size_t sm_cloud_bytes(const sm_plan *plan);       // sm_reproject.hip (its tile size decides)
 
 // ---------------------------------------------------------------------------
 // Argument rules that more than one entry point applies (sm_api.hip; the two on the decision tables: sm_edges.hip).

@@ -59,6 +59,16 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def reprojection_matrix(first_calib, second_calib, baseline):
+    """The 4 x 4 matrix Q of a rectified rig (sm_reproject_q; host only) -> 16 floats, row-major: [X Y Z Wh]' =
+    Q [x y d 1]' with Z = f t / (d - (c2x - c1x)) in the baseline's unit.  *_calib: a capi.RectifyCalib or a dict of
+    RectifyCalib.make's arguments (the rectified projection new_fx, new_fy, new_cx, new_cy is what counts)."""
+    calibs = [c if isinstance(c, capi.RectifyCalib) else capi.RectifyCalib.make(**c) for c in (first_calib, second_calib)]
+    q = capi.Q16()
+    check(lib.sm_reproject_q(C.byref(calibs[0]), C.byref(calibs[1]), float(baseline), q))
+    return list(q)
+
+
 class StereoPlan:
     """Geometry + device workspace for one image size / shift count / window."""
 
@@ -659,6 +669,73 @@ class StereoPlan:
             raise ValueError(f"valid: {valid.shape[0]} images for {map.shape[0]} maps")
         check(lib.sm_valid_mask(self._h, _ptr(map), MAP_TYPES[map.dtype], _ptr(valid), map.shape[0], self._stream()))
         return map
+
+    # ---- reprojection (behind the filters and the interpolation) -----------------
+    def reserve_cloud(self):
+        """point_cloud's workspace (one count per tile of 1024 pixels of max_pairs maps), allocated now: keeps the
+        allocation out of timed paths and out of stream captures."""
+        check(lib.sm_plan_reserve_cloud(self._h))
+
+    @staticmethod
+    def _z_range(z_range):
+        lo, hi = (float("-inf"), float("inf")) if z_range is None else z_range
+        return float(lo), float(hi)
+
+    def _float_out(self, t, shape, name):
+        """a caller's float32 result buffer (checked like an input), or a new one"""
+        if t is None:
+            return torch.empty(shape, dtype=torch.float32, device=self._dev)
+        if t.device != self._dev or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{name}: need a contiguous {torch.float32} tensor on {self._dev}, got {t.dtype} on {t.device}")
+        if t.dim() != len(shape) or t.shape[0] < shape[0] or tuple(t.shape[1:]) != tuple(shape[1:]):
+            raise ValueError(f"{name}: shape {tuple(t.shape)} is not {tuple(shape)} (or more pairs)")
+        return t
+
+    def reproject(self, map, q, want_depth=True, want_xyz=False, missing=0.0, z_range=None, want_count=False,
+                  depth=None, xyz=None):
+        """Metric depth and / or 3-D points of an int32 web map or an int16 sub map (sm_reproject) through the 4 x 4
+        matrix q (reprojection_matrix, or any 16 finite numbers) -> those asked for of (depth [pairs][H][W], xyz
+        [pairs][H][W][3], kept pixels per pair), one tensor or a tuple in that order.  A pixel that is 0, whose point
+        is not finite or whose Z lies outside z_range = (z_min, z_max), both inclusive, receives `missing`.  depth= /
+        xyz= are result buffers of the caller's (and ask for that output)."""
+        map = self._filter_map(map, "map")
+        pairs = map.shape[0]
+        want_depth, want_xyz = want_depth or depth is not None, want_xyz or xyz is not None
+        depth = self._float_out(depth, (pairs, self.height, self.width), "depth") if want_depth else None
+        xyz = self._float_out(xyz, (pairs, self.height, self.width, 3), "xyz") if want_xyz else None
+        count = torch.empty(pairs, dtype=torch.int32, device=self._dev) if want_count else None
+        lo, hi = self._z_range(z_range)
+        check(lib.sm_reproject(self._h, _ptr(map), MAP_TYPES[map.dtype], capi.q16(q), lo, hi, float(missing), pairs,
+                               _ptr(depth), _ptr(xyz), _ptr(count), self._stream()))
+        res = tuple(t for t in (depth, xyz, count) if t is not None)
+        return res[0] if len(res) == 1 else res
+
+    def point_cloud(self, map, q, gray=None, capacity=None, z_range=None, want_index=False, points=None):
+        """The kept pixels of a disparity map as a compacted cloud (sm_point_cloud) -> (points, counts) or (points,
+        counts, index): points [pairs][capacity][4] float32 records (X, Y, Z, I) in raster order, I the value of the
+        uint8 image `gray` at the pixel (0 without one); counts [pairs] int32, the kept pixels of each pair, ALSO where
+        that exceeds capacity (records beyond it are dropped; slots from count on are not written); index
+        [pairs][capacity] int32, y W + x of each record.  capacity defaults to W H; points= is a buffer of the caller's
+        (its second dimension is then the capacity)."""
+        map = self._filter_map(map, "map")
+        pairs = map.shape[0]
+        if gray is not None:
+            gray = self._images(gray, torch.uint8, "gray")
+            if gray.shape[0] != pairs:
+                raise ValueError(f"gray: {gray.shape[0]} images for {pairs} maps")
+        if points is not None:
+            if points.dim() != 3 or points.shape[2] != 4 or (capacity is not None and points.shape[1] != int(capacity)):
+                raise ValueError(f"points: shape {tuple(points.shape)} is not (pairs, capacity, 4)")
+            capacity = points.shape[1]
+        capacity = self.width * self.height if capacity is None else int(capacity)
+        points = self._float_out(points, (pairs, capacity, 4), "points")
+        index = torch.empty((pairs, capacity), dtype=torch.int32, device=self._dev) if want_index else None
+        counts = torch.empty(pairs, dtype=torch.int32, device=self._dev)
+        lo, hi = self._z_range(z_range)
+        check(lib.sm_point_cloud(self._h, _ptr(map), MAP_TYPES[map.dtype], capi.q16(q), lo, hi, _ptr(gray), pairs, capacity,
+                                 _ptr(points) if capacity else C.c_void_p(0), _ptr(index) if capacity else C.c_void_p(0),
+                                 _ptr(counts), self._stream()))
+        return (points, counts, index) if want_index else (points, counts)
 
     def debug_planes(self, pair: int, shift: int):
         """matches-i, score_all-i, scores-i of the reference's debug build."""

@@ -1,0 +1,317 @@
+"""The reprojection stage on the CPU: tests/reproject_reference.py (the definition the GPU is held to) against per-pixel
+Python loops that share nothing with it, the host-only sm_reproject_q against it bit for bit, its physical meaning,
+and the argument refusals of the C ABI that need no device.  (The refusals that need a plan -- pairs outside
+1..max_pairs, ranges that overlap without being the same pointer -- are in tests/test_reproject_gpu.py: a plan cannot
+be made without a device.)"""
+import ctypes as C
+import math
+import struct
+
+import numpy as np
+import pytest
+
+from tests import reproject_patterns as pp
+from tests import reproject_reference as ref
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def f32(v):
+    """a Python float (double) rounded to float32, to nearest even, as a Python float; overflow -> inf"""
+    try:
+        return struct.unpack("f", struct.pack("f", v))[0]
+    except OverflowError:
+        return math.copysign(math.inf, v)
+
+
+def div(a, b):
+    """IEEE double division: Python raises where IEEE returns an infinity or a NaN"""
+    if b == 0.0:
+        if a == 0.0 or math.isnan(a):
+            return math.nan
+        return math.copysign(math.inf, a) * math.copysign(1.0, b)
+    return a / b
+
+
+def loop_pixel(v, is16, q, x, y, lo, hi):
+    """one pixel in Python floats -> (Xf, Yf, Zf, kept)"""
+    d = float(v) / 16.0 - 1.0 if is16 else float(v) - 1.0
+    r = [((q[4 * i] * float(x) + q[4 * i + 1] * float(y)) + q[4 * i + 2] * d) + q[4 * i + 3] for i in range(4)]
+    xf, yf, zf = (f32(div(r[i], r[3])) for i in range(3))
+    kept = v != 0 and all(math.isfinite(t) for t in (xf, yf, zf)) and lo <= zf <= hi
+    return xf, yf, zf, kept
+
+
+def test_definition_against_per_pixel_loops():
+    for (w, h) in ((1, 1), (3, 3), (9, 7), (16, 5)):
+        for name, q in pp.matrices(w, h).items():
+            q = [float(t) for t in q]
+            for mt, dtype in pp.DTYPES.items():
+                for pattern in ("all_valid", "random_50", "extremes"):
+                    for gate in pp.Z_GATES:
+                        m = pp.make_map(pattern, 1, w, h, dtype, seed=w + h)[0]
+                        lo, hi = (-math.inf, math.inf) if gate is None else gate
+                        xf, yf, zf, kept = ref.project(m, q, gate)
+                        depth, xyz, count = ref.reproject(m, q, -7.5, gate)
+                        pts, idx = ref.point_cloud(m, q, None, gate)
+                        k = 0
+                        for y in range(h):
+                            for x in range(w):
+                                want = loop_pixel(int(m[y, x]), dtype == np.int16, q, x, y, lo, hi)
+                                got = (float(xf[y, x]), float(yf[y, x]), float(zf[y, x]))
+                                tag = (name, w, h, pattern, gate, x, y)
+                                for g_, w_ in zip(got, want[:3]):
+                                    assert struct.pack("f", g_) == struct.pack("f", w_) or (math.isnan(g_) and math.isnan(w_)), tag
+                                assert bool(kept[y, x]) == want[3], tag
+                                if want[3]:
+                                    assert depth[y, x] == np.float32(want[2]) and idx[k] == y * w + x, tag
+                                    assert pts[k].tolist() == [np.float32(t) for t in want[:3]] + [0.0], tag
+                                    k += 1
+                                else:
+                                    assert depth[y, x] == np.float32(-7.5) and (xyz[y, x] == np.float32(-7.5)).all(), tag
+                        assert k == len(pts) == int(count)
+
+
+def test_no_pattern_depends_on_a_float32_subnormal():
+    tiny = np.finfo(np.float32).tiny
+    for (w, h) in pp.SIZES:
+        for name, q in pp.matrices(w, h).items():
+            for dtype in pp.DTYPES.values():
+                for pattern in pp.PATTERNS:
+                    m = pp.make_map(pattern, 1, w, h, dtype, seed=3)
+                    with np.errstate(all="ignore"):
+                        for a in ref.project(m, q)[:3]:
+                            a = np.abs(a[np.isfinite(a) & (a != 0)])
+                            assert not len(a) or a.min() >= tiny, (w, h, name, pattern)
+
+
+def test_matrix_patterns_are_what_they_claim():
+    w, h = 66, 7
+    qs = pp.matrices(w, h)
+    assert (qs["dense"] != 0).all()
+    m = pp.make_map("all_valid", 1, w, h, np.int32, 1)[0]
+    _, _, _, kept = ref.project(m, qs["wh_crossing"])
+    assert not kept[:, w // 2].any() and kept[:, :w // 2].all() and kept[:, w // 2 + 1:].all()
+    _, _, zf, kept = ref.project(m, qs["negative_z"])
+    assert 0 < (zf[kept] < 0).sum() < kept.sum()
+    m16 = np.full((h, w), 72, np.int16)                         # d = 72 / 16 - 1 = 3.5 = c2x - c1x: Wh = 0
+    assert not ref.project(m16, qs["rig"])[3].any()
+
+
+# ---------------------------------------------------------------------------
+# sm_reproject_q
+# ---------------------------------------------------------------------------
+
+def calib(capi, d):
+    return capi.RectifyCalib.make(100.0, 100.0, 10.0, 10.0, **d)
+
+
+def test_reproject_q_against_the_definition_bit_for_bit():
+    from stereomatching_amd import capi, pipeline
+    lib = capi.lib
+    cases = [pp.rig(w, h, off, t) for (w, h) in ((66, 7), (3840, 2160), (1, 1)) for off in (3.5, -0.1, 0.0)
+             for t in (0.12, -0.54, 1.0 / 3.0, 65.0)]
+    cases.append((dict(new_fx=1e-3, new_fy=7e5, new_cx=0.0, new_cy=-1234.567), dict(new_fx=1.0, new_fy=1.0, new_cx=1e6 / 3, new_cy=0.0), 1e-3 / 3))
+    for first, second, t in cases:
+        want = ref.reprojection_matrix(first, second, t)
+        q = capi.Q16()
+        assert lib.sm_reproject_q(C.byref(calib(capi, first)), C.byref(calib(capi, second)), t, q) == capi.SM_OK
+        assert np.array_equal(np.array(list(q)).view(np.uint64), want.view(np.uint64)), (first, second, t, list(q), want)
+        got = pipeline.reprojection_matrix(first_calib := dict(first, fx=1, fy=1, cx=0, cy=0), dict(second, fx=1, fy=1, cx=0, cy=0), t)
+        assert np.array_equal(np.array(got).view(np.uint64), want.view(np.uint64)), first_calib
+
+
+def test_reproject_q_refusals():
+    from stereomatching_amd import capi
+    lib = capi.lib
+    first, second, t = pp.rig(64, 48)
+    a, b = calib(capi, first), calib(capi, second)
+    q = capi.Q16(*([7.0] * 16))
+
+    def refused(rc, text):
+        assert rc == capi.SM_ERR_ARG and text in lib.sm_last_error(), lib.sm_last_error()
+    refused(lib.sm_reproject_q(None, C.byref(b), t, q), b"sm_reproject_q: calib is NULL")
+    refused(lib.sm_reproject_q(C.byref(a), None, t, q), b"sm_reproject_q: calib is NULL")
+    refused(lib.sm_reproject_q(C.byref(a), C.byref(b), t, None), b"sm_reproject_q: q is NULL")
+    for bad in (0.0, -0.0, math.inf, -math.inf, math.nan):
+        refused(lib.sm_reproject_q(C.byref(a), C.byref(b), bad, q), b"sm_reproject_q: baseline")
+    for side in (0, 1):
+        short = calib(capi, (first, second)[side])
+        short.struct_size = C.sizeof(capi.RectifyCalib) - 8
+        refused(lib.sm_reproject_q(C.byref(short) if side == 0 else C.byref(a), C.byref(short) if side == 1 else C.byref(b), t, q),
+                b"sm_reproject_q: calib->struct_size")
+    for field in ("new_fx", "new_fy"):
+        for bad in (0.0, -700.0, math.inf, math.nan):
+            refused(lib.sm_reproject_q(C.byref(calib(capi, dict(first, **{field: bad}))), C.byref(b), t, q),
+                    b"sm_reproject_q: new_fx")
+    assert list(q) == [7.0] * 16                               # a refusal writes nothing
+    longer = calib(capi, first)
+    longer.struct_size += 64                                    # a newer caller: the known fields are taken
+    assert lib.sm_reproject_q(C.byref(longer), C.byref(b), t, q) == capi.SM_OK
+    for f in (first, second):
+        with pytest.raises(ValueError):
+            ref.reprojection_matrix(dict(f, new_fx=0.0), second, t)
+    with pytest.raises(ValueError):
+        ref.reprojection_matrix(first, second, 0.0)
+
+
+# ---------------------------------------------------------------------------
+# what the numbers mean
+# ---------------------------------------------------------------------------
+
+@pytest.mark.parametrize("dtype", [np.int32, np.int16])
+def test_fronto_parallel_plane_comes_back_exactly(dtype):
+    """a plane at Z0 in front of a rig with power-of-two f, t and Z0: d = f t / Z0 + (c2x - c1x) is exact, and so is
+    everything after it"""
+    w, h = 40, 12
+    f, t, z0 = 512.0, 0.125, 4.0
+    first = dict(new_fx=f, new_fy=f, new_cx=16.0, new_cy=5.0)
+    second = dict(first, new_cx=19.0)
+    d = f * t / z0 + 3.0                                       # 19 shifts
+    v = d + 1.0 if dtype == np.int32 else 16.0 * (d + 1.0)
+    m = np.full((h, w), v, dtype)
+    q = ref.reprojection_matrix(first, second, t)
+    depth, xyz, count = ref.reproject(m, q)
+    assert (depth == np.float32(z0)).all() and count == w * h
+    xs, ys = np.arange(w, dtype=np.float64)[None, :], np.arange(h, dtype=np.float64)[:, None]
+    assert np.array_equal(xyz[..., 0], np.broadcast_to(((xs - 16.0) * z0 / f).astype(np.float32), (h, w)))
+    assert np.array_equal(xyz[..., 1], np.broadcast_to(((ys - 5.0) * z0 / f).astype(np.float32), (h, w)))
+    assert np.array_equal(xyz[..., 2], depth)
+    # a closer plane has the larger disparity
+    assert (ref.reproject(m + dtype(16), q)[0] < depth).all()
+
+
+def test_disparity_equal_to_the_principal_point_offset_is_dropped():
+    first = dict(new_fx=512.0, new_fy=512.0, new_cx=16.0, new_cy=5.0)
+    q = ref.reprojection_matrix(first, dict(first, new_cx=19.0), 0.125)
+    m = np.array([[4, 5, 3, 0]], np.int32)                      # d = 3 (Wh = 0: the point at infinity), 4, 2, invalid
+    depth, xyz, count = ref.reproject(m, q, np.nan)
+    assert np.isnan(depth[0, 0]) and np.isnan(xyz[0, 0]).all() and np.isnan(depth[0, 3])
+    assert depth[0, 1] == 64.0 and depth[0, 2] == -64.0 and count == 2
+    pts, idx = ref.point_cloud(m, q)
+    assert idx.tolist() == [1, 2] and pts[:, 2].tolist() == [64.0, -64.0]
+
+
+def test_z_gate_keeps_both_bounds():
+    first = dict(new_fx=512.0, new_fy=512.0, new_cx=0.0, new_cy=0.0)
+    q = ref.reprojection_matrix(first, first, 0.125)           # Z = 64 / d
+    m = np.array([[2, 3, 5, 9, 17, 33, 65]], np.int32)          # Z = 64, 32, 16, 8, 4, 2, 1
+    depth, _, count = ref.reproject(m, q, 0.0, (2.0, 32.0))
+    assert depth.tolist() == [[0.0, 32.0, 16.0, 8.0, 4.0, 2.0, 0.0]] and count == 5
+    assert ref.reproject(m, q, 0.0, (8.0, 8.0))[2] == 1
+    assert ref.reproject(m, q, 0.0, (-np.inf, np.inf))[2] == 7
+    assert ref.reproject(m, q, 0.0, (3.0, 3.5))[2] == 0
+    for bad in ((np.nan, 1.0), (0.0, np.nan), (2.0, 1.0)):
+        with pytest.raises(ValueError):
+            ref.reproject(m, q, 0.0, bad)
+    with pytest.raises(ValueError):
+        ref.reproject(m, np.where(np.arange(16) == 5, np.inf, q))
+
+
+def test_point_cloud_is_the_kept_pixels_of_the_dense_map_in_raster_order():
+    for (w, h) in ((37, 5), (64, 9), (41, 25)):
+        for name, q in pp.matrices(w, h).items():
+            for dtype in pp.DTYPES.values():
+                for pattern in pp.PATTERNS:
+                    for gate in pp.Z_GATES:
+                        m = pp.make_map(pattern, 1, w, h, dtype, seed=5)[0]
+                        g = pp.gray(1, w, h, 5)[0]
+                        depth, xyz, count = ref.reproject(m, q, np.nan, gate)
+                        kept = ref.project(m, q, gate)[3]
+                        pts, idx = ref.point_cloud(m, q, g, gate)
+                        assert len(pts) == len(idx) == int(count) == int(kept.sum())
+                        assert np.array_equal(idx, np.flatnonzero(kept.reshape(-1))) and (np.diff(idx) > 0).all()
+                        assert np.array_equal(bits(pts[:, :3]), bits(xyz.reshape(-1, 3)[idx]))
+                        assert np.array_equal(pts[:, 3], g.reshape(-1)[idx].astype(np.float32))
+                        assert np.array_equal(bits(ref.point_cloud(m, q, None, gate)[0][:, 3]), np.zeros(len(idx), np.uint32))
+
+
+def test_workspace_formula():
+    assert ref.workspace_bytes(1, 1, 1) == 4 and ref.workspace_bytes(32, 32, 3) == 12 and ref.workspace_bytes(41, 25, 2) == 16
+    assert ref.workspace_bytes(3840, 2160, 1) == 4 * 8100
+
+
+# ---------------------------------------------------------------------------
+# the C ABI: refusals that precede any device use
+# ---------------------------------------------------------------------------
+
+def test_argument_refusals_precede_device_use():
+    from stereomatching_amd import capi
+    lib = capi.lib
+    buf = [(C.c_ubyte * 64)() for _ in range(6)]
+    p = [C.c_void_p(C.addressof(b)) for b in buf]
+    I32, I16 = capi.SM_MAP_I32, capi.SM_MAP_I16
+    inf, nan = math.inf, math.nan
+    q = capi.Q16(*[float(v) for v in pp.matrices(8, 8)["dense"]])
+
+    def bad_q(i, v):
+        t = list(q)
+        t[i] = v
+        return capi.Q16(*t)
+
+    def refused(rc, text):
+        assert rc == capi.SM_ERR_ARG and text in lib.sm_last_error(), lib.sm_last_error()
+    me = b"sm_reproject: "
+    refused(lib.sm_reproject(None, p[0], I32, q, -inf, inf, 0.0, 1, p[1], p[2], p[3], None), me + b"plan is NULL")
+    refused(lib.sm_reproject(None, None, I32, q, -inf, inf, 0.0, 1, p[1], p[2], p[3], None), me + b"a map pointer is NULL")
+    refused(lib.sm_reproject(None, p[0], 2, q, -inf, inf, 0.0, 1, p[1], p[2], p[3], None), me + b"map_type 2")
+    refused(lib.sm_reproject(None, p[0], -1, q, -inf, inf, 0.0, 1, p[1], p[2], p[3], None), me + b"map_type -1")
+    refused(lib.sm_reproject(None, p[0], I16, None, -inf, inf, 0.0, 1, p[1], p[2], p[3], None), me + b"q is NULL")
+    for i in (0, 7, 15):
+        for v in (inf, -inf, nan):
+            refused(lib.sm_reproject(None, p[0], I16, bad_q(i, v), -inf, inf, 0.0, 1, p[1], p[2], p[3], None),
+                    me + b"q[%d]" % i)
+    refused(lib.sm_reproject(None, p[0], I32, q, nan, inf, 0.0, 1, p[1], p[2], p[3], None), me + b"a bound of the z range is NaN")
+    refused(lib.sm_reproject(None, p[0], I32, q, 0.0, nan, 0.0, 1, p[1], p[2], p[3], None), me + b"a bound of the z range is NaN")
+    refused(lib.sm_reproject(None, p[0], I32, q, 2.0, 1.0, 0.0, 1, p[1], p[2], p[3], None), me + b"z_min 2 is above z_max 1")
+    refused(lib.sm_reproject(None, p[0], I32, q, inf, -inf, 0.0, 1, p[1], p[2], p[3], None), me + b"z_min inf is above z_max -inf")
+    refused(lib.sm_reproject(None, p[0], I32, q, -inf, inf, 0.0, 1, None, None, p[3], None), me + b"d_depth and d_xyz are both NULL")
+    # overlapping pointers: an output that is the input, two outputs that are one
+    refused(lib.sm_reproject(None, p[0], I32, q, -inf, inf, 0.0, 1, p[0], None, None, None), me + b"an output overlaps an input")
+    refused(lib.sm_reproject(None, p[0], I32, q, -inf, inf, 0.0, 1, None, p[1], p[0], None), me + b"an output overlaps an input")
+    refused(lib.sm_reproject(None, p[0], I32, q, -inf, inf, 0.0, 1, p[1], p[1], None, None), me + b"outputs overlap")
+    refused(lib.sm_reproject(None, p[0], I32, q, -inf, inf, 0.0, 1, p[1], None, p[1], None), me + b"outputs overlap")
+    refused(lib.sm_reproject(None, C.c_void_p(p[0].value + 2), I32, q, -inf, inf, 0.0, 1, p[1], None, None, None),
+            me + b"the map pointer is not aligned")
+    refused(lib.sm_reproject(None, p[0], I16, q, -inf, inf, 0.0, 1, C.c_void_p(p[1].value + 2), None, None, None),
+            me + b"an output pointer is not aligned")
+    # an equal bound is a range, and the plan is looked at last
+    refused(lib.sm_reproject(None, p[0], I32, q, 1.0, 1.0, nan, 1, p[1], None, None, None), me + b"plan is NULL")
+
+    me = b"sm_point_cloud: "
+    refused(lib.sm_point_cloud(None, p[0], I32, q, -inf, inf, p[1], 1, 4, p[2], p[3], p[4], None), me + b"plan is NULL")
+    refused(lib.sm_point_cloud(None, None, I32, q, -inf, inf, p[1], 1, 4, p[2], p[3], p[4], None), me + b"a map pointer is NULL")
+    refused(lib.sm_point_cloud(None, p[0], 3, q, -inf, inf, p[1], 1, 4, p[2], p[3], p[4], None), me + b"map_type 3")
+    refused(lib.sm_point_cloud(None, p[0], I32, None, -inf, inf, p[1], 1, 4, p[2], p[3], p[4], None), me + b"q is NULL")
+    refused(lib.sm_point_cloud(None, p[0], I32, bad_q(12, nan), -inf, inf, p[1], 1, 4, p[2], p[3], p[4], None), me + b"q[12]")
+    refused(lib.sm_point_cloud(None, p[0], I32, q, nan, inf, p[1], 1, 4, p[2], p[3], p[4], None), me + b"a bound of the z range is NaN")
+    refused(lib.sm_point_cloud(None, p[0], I32, q, 1.5, 1.0, p[1], 1, 4, p[2], p[3], p[4], None), me + b"z_min 1.5 is above z_max 1")
+    refused(lib.sm_point_cloud(None, p[0], I32, q, -inf, inf, p[1], 1, -1, p[2], p[3], p[4], None), me + b"capacity -1 is negative")
+    refused(lib.sm_point_cloud(None, p[0], I32, q, -inf, inf, p[1], 1, 4, None, p[3], p[4], None), me + b"d_points is NULL and capacity is 4")
+    refused(lib.sm_point_cloud(None, p[0], I32, q, -inf, inf, p[1], 1, 4, p[2], p[3], None, None), me + b"d_count is NULL")
+    refused(lib.sm_point_cloud(None, p[0], I32, q, -inf, inf, p[1], 1, 0, None, None, None, None), me + b"d_count is NULL")
+    refused(lib.sm_point_cloud(None, p[0], I32, q, -inf, inf, p[1], 1, 4, p[0], p[3], p[4], None), me + b"an output overlaps an input")
+    refused(lib.sm_point_cloud(None, p[0], I32, q, -inf, inf, p[1], 1, 4, p[2], p[1], p[4], None), me + b"an output overlaps an input")
+    refused(lib.sm_point_cloud(None, p[0], I32, q, -inf, inf, None, 1, 4, p[2], p[3], p[0], None), me + b"an output overlaps an input")
+    refused(lib.sm_point_cloud(None, p[0], I32, q, -inf, inf, p[1], 1, 4, p[2], p[2], p[4], None), me + b"outputs overlap")
+    refused(lib.sm_point_cloud(None, p[0], I32, q, -inf, inf, p[1], 1, 4, p[2], p[3], p[3], None), me + b"outputs overlap")
+    # a count-only call passes every check up to the plan
+    refused(lib.sm_point_cloud(None, p[0], I16, q, -inf, inf, None, 1, 0, None, None, p[4], None), me + b"plan is NULL")
+    refused(lib.sm_plan_reserve_cloud(None), b"sm_plan_reserve_cloud: plan is NULL")
+    assert all(bytes(b) == bytes(64) for b in buf)
+
+
+def test_header_and_binding_agree():
+    import re
+    from stereomatching_amd import capi
+    text = capi.HEADER.read_text()
+    assert "4 * max_pairs * ceil(W * H / 1024) bytes" in text and ref.TILE == 1024
+    for name in ("sm_reproject", "sm_point_cloud", "sm_plan_reserve_cloud", "sm_reproject_q"):
+        assert name in capi.declared_symbols() and name in capi._SIGNATURES
+    assert C.sizeof(capi.Q16) == 128
+    assert re.search(r"#define SM_MAP_I32 0\b", text) and re.search(r"#define SM_MAP_I16 1\b", text) and (ref.I32, ref.I16) == (0, 1)
+    assert list(capi.q16(np.arange(16.0).reshape(4, 4))) == list(capi.q16(list(range(16)))) == [float(i) for i in range(16)]
+    with pytest.raises(ValueError):
+        capi.q16([1.0] * 15)
