@@ -379,6 +379,19 @@ int sm_debug_edge_table(int device, double threshold, uint8_t *d_table, void *st
 int sm_debug_edge_table_fast(sm_plan *plan, double threshold, uint8_t *d_table,
                              int *not_threshold_form, void *stream);
 
+/* debug tap, for tests only: fill the plan's lazily allocated workspaces with `word`, so that a stage which
+ * reads a workspace word before it has written it in the same call gives a wrong result instead of one that is
+ * right by luck (fresh device memory is very often zero).  Makes the plan's device current, synchronises the
+ * device (both lanes of the plan with it), fills every workspace that is allocated and is NOT zero-filled on
+ * allocation over its whole extent with the 32-bit word, and synchronises again.  The zero-filled workspace
+ * (the mirrored packed images of the consistency check) is left alone: the words beyond each side's row
+ * extent are zero by invariant, written by no call, and every match launch reads them, so poisoning them would
+ * break the plan instead of testing a stage.  Workspaces that are not allocated are skipped and nothing is
+ * allocated (reserve them first: sm_plan_reserve_*); the plan's permanent buffers -- packed images, tables,
+ * lane state -- are not touched.  SM_ERR_ARG for a NULL plan.  Must NOT be called while a stream is capturing
+ * (it synchronises the device), nor while another thread uses the plan.                                    */
+int sm_debug_poison_workspace(sm_plan *plan, uint32_t word);
+
 /* ---- left-right consistency check ---------------------------------------- *
  * New work (the reference matches one way only: each LEFT pixel's winning shift, src/stereo.cu:211-225).
  * The check marks the left pixels whose match does not point back to them with 0 -- the value

@@ -374,6 +374,24 @@ void sm_ws_free(sm_plan *plan)
     }
 }
 
+// test only (stereo_hip.h): every allocated row that is NOT zero-filled on allocation, filled with `word` over its whole
+// extent.  A zero == true row is left alone: its zero words are an invariant no call restores (SM_WS_EXT_LR: the
+// words beyond each side's row extent), so poisoning it would break the plan rather than test a stage.
+extern "C" int sm_debug_poison_workspace(sm_plan *plan, uint32_t word)
+{
+    const char *me = "sm_debug_poison_workspace";
+    if (!plan) return sm_fail(SM_ERR_ARG, "%s: plan is NULL", me);
+    SM_TRY(sm_use_device(plan->device));
+    hipError_t e = hipDeviceSynchronize();              // both lanes, and every stream a stage was given
+    for (int r = 0; r < SM_WS_ROWS && e == hipSuccess; r++) {
+        if (ws_rows[r].zero || !ws_ptr(plan, r)) continue;
+        e = hipMemsetD32((hipDeviceptr_t)ws_ptr(plan, r), (int)word, ws_rows[r].bytes(plan) / sizeof(u32));
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "%s: %s", me, hipGetErrorString(e));
+    return SM_OK;
+}
+
 extern "C" int sm_plan_reserve_narrow(sm_plan *plan)
 {
     if (!plan) return sm_fail(SM_ERR_ARG, "sm_plan_reserve_narrow: plan is NULL");

@@ -745,6 +745,11 @@ class StereoPlan:
         check(lib.sm_debug_planes(self._h, pair, shift, _ptr(m), _ptr(sa), _ptr(sc), self._stream()))
         return m, sa, sc
 
+    def _poison_workspace(self, word: int):
+        """Tests only (sm_debug_poison_workspace): every allocated workspace that is not zero-filled on allocation,
+        filled with the 32-bit `word`; synchronises the device.  Not inside a stream capture."""
+        check(lib.sm_debug_poison_workspace(self._h, int(word) & 0xFFFFFFFF))
+
     # ---- step 3 ------------------------------------------------------------
     def fill_web_holes(self, web, times=DEFAULT_TIMES):
         """src/stereo.cu:235-256; returns the buffer the reference would return."""

@@ -17,6 +17,41 @@ def test_library_exports_every_declared_symbol():
         assert s in capi._SIGNATURES, f"{s} has no ctypes signature"
     # and nothing is bound that the header does not declare
     assert set(capi._SIGNATURES) == set(syms)
+    # every binding has the header's parameters: as many, and of the same kind each
+    assert "sm_debug_poison_workspace" in syms
+    protos = header_prototypes(capi.HEADER)
+    assert set(protos) == set(syms)
+    for s in syms:
+        bound = [ctype_kind(a) for a in capi._SIGNATURES[s][1]]
+        assert bound == protos[s], f"{s}: bound as {bound}, declared as {protos[s]}"
+    assert protos["sm_debug_poison_workspace"] == ["pointer", "u32"]
+
+
+def header_prototypes(header):
+    """function name -> the kinds of its parameters as the header declares them"""
+    import re
+    text = re.sub(r"/\*.*?\*/", "", header.read_text(), flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    protos = {}
+    for name, params in re.findall(r"\b(sm_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        params = [p.strip() for p in params.split(",")]
+        protos[name] = [] if params in ([""], ["void"]) else [c_kind(p) for p in params]
+    return protos
+
+
+def c_kind(param):
+    if "*" in param or "[" in param:
+        return "pointer"
+    words = param.replace("const", " ").split()
+    base = " ".join(words[:-1]) if len(words) > 1 else words[0]      # (without the parameter's name)
+    return {"int": "int", "double": "double", "float": "float", "size_t": "size", "uint32_t": "u32",
+            "unsigned": "u32", "unsigned int": "u32"}[base]
+
+
+def ctype_kind(t):
+    if t in (C.c_void_p, C.c_char_p) or hasattr(t, "contents") or issubclass(t, C._Pointer):
+        return "pointer"
+    return {C.c_int: "int", C.c_double: "double", C.c_float: "float", C.c_size_t: "size", C.c_uint32: "u32"}[t]
 
 
 def test_exported_symbols_are_plain_c():
