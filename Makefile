@@ -56,6 +56,8 @@ stereomatching_amd/obj/product/%.o: $(CSRC)/%.hip $(CSRC)/sm_internal.h $(CSRC)/
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 # (the reprojection stage is built in the rectification's unit, which includes it)
 stereomatching_amd/obj/product/sm_rectify.o: $(CSRC)/sm_reproject.hip
+# (... and the guided weighted median in the post-filters')
+stereomatching_amd/obj/product/sm_filter.o: $(CSRC)/sm_wmedian.hip
 $(DEVLIB): $(DEVOBJ)
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC $^ -o $@
 

@@ -584,6 +584,36 @@ int sm_sub_mask(sm_plan *plan, const int32_t *d_web, int16_t *d_sub, int pairs, 
 /* adds: allocates the speckle filter's workspace now; idempotent */
 int sm_plan_reserve_filter(sm_plan *plan);
 
+/* ---- guided weighted median: PARITY UNPINNED ------------------------------ *
+ * New work (no reference counterpart; Ma et al., ICCV 2013): the one post-filter that looks at the
+ * image.  Every matcher aggregates over a square box, so its disparity edges lie up to half a window beside the
+ * image's; a median whose taps are weighted by how alike the GUIDE image is at the tap and at the centre moves them
+ * back.  cost -> check -> speckle -> weighted median (optionally filling) -> interpolate -> step 3 -> reproject.
+ * Maps, validity and borders follow the post-filters: [pairs][H][W] of SM_MAP_I32 or SM_MAP_I16; a pixel is valid iff
+ * its value != 0; a tap outside the image does not exist, in either border mode; pairs are independent.
+ *   guide g: u8 [pairs][H][W], typically the rectified left image.  radius r: 1 .. 7.  weights: 256 uint16_t ON THE
+ *     HOST (as q[16] of sm_reproject is), weights[0] >= 1.
+ *   For pixel p the taps are the pixels q of the (2r+1) x (2r+1) window around p that lie in the image and have
+ *     in(q) != 0; tap q has the weight w_q = weights[|g(p) - g(q)|]; T = the sum of the w_q (at most 225 * 65535: it
+ *     fits 32 bits).
+ *   wmed(p) = the smallest tap value v, in signed order, with 2 * sum{w_q : in(q) <= v} >= T: the lower weighted
+ *     median.  With all weights equal it is sm_median_filter's v_((m-1)/2).
+ *   flags = 0: out(p) = 0 where in(p) = 0; otherwise out(p) = wmed(p) (T >= 1: the centre is a tap).
+ *   flags = SM_WMED_FILL: where in(p) = 0, out(p) = wmed(p) if T >= fill_min_weight, otherwise 0.  fill_min_weight >=
+ *     1; it is ignored without the flag.  Taps are always read from the input: a filled pixel is no source.
+ *   d_filled: NULL or one int32 per pair, the number of pixels that were 0 and are no longer (0 without the flag).
+ *   d_in and d_out must not overlap: any overlap is refused (so is an output that overlaps the guide, and a d_filled
+ *     that overlaps a map).
+ * Arguments are checked before any device call; a refusal names the function.  The call runs in `stream` order and
+ * uses nothing the pipelined lanes use.  It needs no workspace and can always be captured; the weight table travels
+ * in the kernel's arguments, so in a captured graph its values are those at capture time.  Images smaller than the
+ * window are fine.                                                                                              */
+#define SM_WMED_FILL 1
+/* adds: the guided weighted median of d_in -> d_out (same type) */
+int sm_weighted_median(sm_plan *plan, const void *d_in, int map_type, const uint8_t *d_guide, int radius,
+                       const uint16_t weights[256], int flags, int fill_min_weight, int pairs,
+                       void *d_out, int32_t *d_filled, void *stream);
+
 /* ---- occlusion-aware interpolation: PARITY UNPINNED ----------------------- *
  * New work (no reference counterpart): Hirschmueller's discontinuity-preserving interpolation (PAMI
  * 2008) of the 0s the check and the speckle filter leave: cost -> check -> speckle / median -> interpolate -> step 3.

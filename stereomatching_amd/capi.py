@@ -20,6 +20,7 @@ SM_OK, SM_ERR_ARG, SM_ERR_HIP, SM_ERR_NOMEM, SM_ERR_ZERO_DIV = range(5)
 SM_TOROIDAL, SM_GHOST = 0, 1
 SM_WEB_I32, SM_WEB_U16, SM_WEB_U8 = 0, 1, 2
 SM_MAP_I32, SM_MAP_I16 = 0, 1
+SM_WMED_FILL = 1
 SM_CLASS_VALID, SM_CLASS_OCCLUDED, SM_CLASS_MISMATCHED = 0, 1, 2
 SM_RMAP_FRAC_BITS = 5
 SM_RMAP_ABS32, SM_RMAP_REL16 = 0, 1
@@ -46,6 +47,8 @@ _vp, _int, _sz, _dbl, _flt = C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_fl
 _intp = C.POINTER(C.c_int)
 _dblp = C.POINTER(C.c_double)      # a reprojection matrix: an instance of Q16 (or None)
 Q16 = C.c_double * 16
+_u16p = C.POINTER(C.c_uint16)      # a weight table of the weighted median: an instance of W256 (or None)
+W256 = C.c_uint16 * 256
 
 class Geometry(C.Structure):
     """sm_geometry of include/stereo_hip.h"""
@@ -171,6 +174,7 @@ _SIGNATURES = {
     "sm_speckle_filter": (_int, [_vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sm_sub_mask": (_int, [_vp, _vp, _vp, _int, _vp]),
     "sm_plan_reserve_filter": (_int, [_vp]),
+    "sm_weighted_median": (_int, [_vp, _vp, _int, _vp, _int, _u16p, _int, _int, _int, _vp, _vp, _vp]),
     "sm_occlusion_classify": (_int, [_vp, _vp, _vp, _int, _vp, _vp]),
     "sm_interpolate": (_int, [_vp, _vp, _int, _vp, _int, _vp, _vp, _vp]),
     "sm_plan_reserve_interp": (_int, [_vp]),
@@ -193,6 +197,18 @@ def q16(q) -> "Q16":
     if len(flat) != 16:
         raise ValueError(f"q: need 16 numbers (or 4 rows of 4), got {len(flat)}")
     return Q16(*(float(v) for v in flat))
+
+
+def w256(weights) -> "W256":
+    """A weight table as the c_uint16 * 256 the C ABI takes: 256 integers in 0 .. 65535 (a list, numpy, torch)"""
+    if isinstance(weights, W256):
+        return weights
+    flat = weights.tolist() if hasattr(weights, "tolist") else list(weights)
+    if len(flat) != 256 or any(isinstance(v, (list, tuple)) for v in flat):
+        raise ValueError(f"weights: need 256 numbers, got {len(flat)}")
+    if any(int(v) != v or not 0 <= v <= 65535 for v in flat):
+        raise ValueError("weights: need integers in 0 .. 65535")
+    return W256(*(int(v) for v in flat))
 
 
 def _load() -> C.CDLL:

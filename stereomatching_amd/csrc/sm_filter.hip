@@ -419,3 +419,6 @@ extern "C" int sm_valid_mask(sm_plan *plan, void *d_map, int map_type, const uin
     SM_LAUNCH_CHECK("k_valid_mask");
     return SM_OK;
 }
+
+// the guided weighted median, a source file of its own built in this unit
+#include "sm_wmedian.hip"

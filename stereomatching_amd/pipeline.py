@@ -12,6 +12,7 @@ import ctypes as C
 from dataclasses import dataclass
 from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import capi
@@ -67,6 +68,12 @@ def reprojection_matrix(first_calib, second_calib, baseline):
     q = capi.Q16()
     check(lib.sm_reproject_q(C.byref(calibs[0]), C.byref(calibs[1]), float(baseline), q))
     return list(q)
+
+
+def guide_weights(sigma, peak=1024):
+    """A weight table for StereoPlan.weighted_median -> 256 uint16: max(1, round(peak * exp(-delta / sigma))) for a
+    gray difference delta = 0 .. 255 (numpy's exp and round-half-even; no C counterpart: the table is the interface)"""
+    return np.maximum(1, np.rint(peak * np.exp(-np.arange(256) / sigma))).astype(np.uint16)
 
 
 class StereoPlan:
@@ -564,6 +571,25 @@ class StereoPlan:
             raise ValueError(f"sub: {sub.shape[0]} maps for {web.shape[0]} pairs")
         check(lib.sm_sub_mask(self._h, _ptr(web), _ptr(sub), web.shape[0], self._stream()))
         return sub
+
+    # ---- guided weighted median (between the speckle filter and the interpolation) ---
+    def weighted_median(self, map, guide, radius, weights, fill=False, fill_min_weight=1, out=None, want_filled=False):
+        """Guided weighted median (sm_weighted_median) of an int32 web map or an int16 sub map -> the filtered map, or
+        (map, filled pixels per pair) with want_filled.  guide: uint8 images of the map's shape (the rectified left
+        image); weights: 256 integers, the weight of a tap by the gray difference between it and the centre in the
+        guide (guide_weights).  A valid pixel becomes the lower weighted median of the valid pixels of its
+        (2 radius + 1)^2 window; 0 stays 0 unless fill is set and the window's weights sum to fill_min_weight or more."""
+        map = self._filter_map(map, "map")
+        pairs = map.shape[0]
+        guide = self._images(guide, torch.uint8, "guide")
+        if guide.shape[0] != pairs:
+            raise ValueError(f"guide: {guide.shape[0]} images for {pairs} pairs")
+        out = self._out(out, pairs, "out", map.dtype)
+        filled = torch.empty(pairs, dtype=torch.int32, device=self._dev) if want_filled else None
+        check(lib.sm_weighted_median(self._h, _ptr(map), MAP_TYPES[map.dtype], _ptr(guide), int(radius), capi.w256(weights),
+                                     capi.SM_WMED_FILL if fill else 0, int(fill_min_weight), pairs, _ptr(out), _ptr(filled),
+                                     self._stream()))
+        return (out, filled) if want_filled else out
 
     # ---- occlusion-aware interpolation (between the post-filters and step 3) -----
     def reserve_interp(self):
