@@ -58,6 +58,8 @@ stereomatching_amd/obj/product/%.o: $(CSRC)/%.hip $(CSRC)/sm_internal.h $(CSRC)/
 stereomatching_amd/obj/product/sm_rectify.o: $(CSRC)/sm_reproject.hip
 # (... and the guided weighted median in the post-filters')
 stereomatching_amd/obj/product/sm_filter.o: $(CSRC)/sm_wmedian.hip
+# (... and the half-resolution path beside it)
+stereomatching_amd/obj/product/sm_filter.o: $(CSRC)/sm_pyramid.hip
 $(DEVLIB): $(DEVOBJ)
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC $^ -o $@
 

@@ -614,6 +614,52 @@ int sm_weighted_median(sm_plan *plan, const void *d_in, int map_type, const uint
                        const uint16_t weights[256], int flags, int fill_min_weight, int pairs,
                        void *d_out, int32_t *d_filled, void *stream);
 
+/* ---- half-resolution path: PARITY UNPINNED -------------------------------- *
+ * New work (no reference counterpart): SGM on a large pair costs a volume of W x H x shifts.  Matching
+ * at half the size with half the shifts is an eighth of it; the coarse map is then brought back to the fine size
+ * along the edges of the fine image (joint upsampling: Kopf et al., SIGGRAPH 2007, with the weighted median of the
+ * section above in place of the mean).  reduce both sides -> any matcher on a plan of the coarse size with half the
+ * shifts -> check / filters at the coarse size -> upsample -> filters at the fine size -> interpolate -> reproject.
+ * Both calls take the plan of the FINE size W x H.  The coarse size is fixed by it: cw = (W + 1) >> 1, ch = (H + 1) >> 1;
+ * the coarse matcher runs on a second plan of cw x ch that the caller makes.  Nothing wraps, in either border mode;
+ * pairs are independent.
+ *   sm_reduce_half: d_src u8 [images][H][W] -> d_dst u8 [images][ch][cw]; images is 1 .. 2 * max_pairs, so both sides
+ *     of a batch go in one call.  Exact integers, with cx(u) = min(max(u, 0), W - 1) and cy likewise (replicate):
+ *       SM_REDUCE_BOX:      dst(X, Y) = (sum{i, j in 0..1} src(cx(2X + i), cy(2Y + j)) + 2) >> 2
+ *       SM_REDUCE_BINOMIAL: k = [1, 3, 3, 1]; dst(X, Y) = (sum{i, j in 0..3} k_i k_j src(cx(2X - 1 + i), cy(2Y - 1 + j)) + 32) >> 6
+ *     Both are centred on the 2 x 2 block: coarse pixel (X, Y) stands for the fine pixels (2X .. 2X + 1, 2Y .. 2Y + 1),
+ *     and a fine shift d is a coarse shift d / 2.
+ *   sm_upsample_double: d_in [pairs][ch][cw] -> d_out [pairs][H][W], both SM_MAP_I32 or both SM_MAP_I16; a pixel is
+ *     valid iff its value != 0.  d_guide: u8 [pairs][H][W]; d_guide_coarse: u8 [pairs][ch][cw], typically
+ *     sm_reduce_half of d_guide.  weights: 256 uint16_t ON THE HOST, every one >= 1 (no tap is the centre here, so a 0
+ *     anywhere could leave a valid pixel without weight: it is refused).
+ *     Values change scale, web = 1 + shift and sub = 16 web + fraction:
+ *       SM_MAP_I32: v(c) = 2 in(c) - 1, computed in 64 bits and clamped to int32
+ *       SM_MAP_I16: v(c) = 2 in(c) - 16, clamped to int16.  An input of 8 becomes 0, which reads as invalid; the
+ *         sub values the library writes are >= 16.
+ *     For the fine pixel p = (x, y): home (X, Y) = (x >> 1, y >> 1), px = x & 1, py = y & 1.  The taps are the coarse
+ *     pixels c = (X + i, Y + j), i, j in {-1, 0, 1}, that lie in the coarse image and have in(c) != 0.  Tap c has the
+ *     weight w_c = weights[|g(p) - gc(c)|] * s(i, px) * s(j, py), where s(i, 0) = 2, 4, 1 and s(i, 1) = 1, 4, 2 for
+ *     i = -1, 0, 1 (4, 2, 1 by the distance |4i + 1 - 2px| = 1, 3, 5 of the tap's centre, in quarter coarse pixels).
+ *     T = the sum of the w_c (at most 49 * 65535).  wmed(p) = the smallest v(c), in signed order, with
+ *     2 * sum{w_c' : v(c') <= v(c)} >= T: the lower weighted median.
+ *       flags = 0:          out(p) = 0 where in(home) = 0; otherwise wmed(p)
+ *       flags = SM_UP_FILL: where in(home) = 0, out(p) = wmed(p) if p has a tap, otherwise 0
+ *     Taps are always read from the input.
+ *   An output that overlaps an input or a guide is refused.
+ * Arguments are checked before any device call; a refusal names the function.  The calls run in `stream` order and
+ * use nothing the pipelined lanes use.  They need no workspace and can always be captured; the weight table travels
+ * in the kernel's arguments, so in a captured graph its values are those at capture time.                        */
+#define SM_REDUCE_BOX 0
+#define SM_REDUCE_BINOMIAL 1
+#define SM_UP_FILL 1
+/* adds: images of the plan's size reduced by two in each direction */
+int sm_reduce_half(sm_plan *plan, const uint8_t *d_src, int filter, int images, uint8_t *d_dst, void *stream);
+/* adds: a map of the half size brought to the plan's size along the edges of d_guide */
+int sm_upsample_double(sm_plan *plan, const void *d_in, int map_type, const uint8_t *d_guide,
+                       const uint8_t *d_guide_coarse, const uint16_t weights[256], int flags, int pairs,
+                       void *d_out, void *stream);
+
 /* ---- occlusion-aware interpolation: PARITY UNPINNED ----------------------- *
  * New work (no reference counterpart): Hirschmueller's discontinuity-preserving interpolation (PAMI
  * 2008) of the 0s the check and the speckle filter leave: cost -> check -> speckle / median -> interpolate -> step 3.

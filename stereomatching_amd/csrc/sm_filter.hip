@@ -422,3 +422,5 @@ extern "C" int sm_valid_mask(sm_plan *plan, void *d_map, int map_type, const uin
 
 // the guided weighted median, a source file of its own built in this unit
 #include "sm_wmedian.hip"
+// ... and the half-resolution path (it takes the weight table as the weighted median does)
+#include "sm_pyramid.hip"

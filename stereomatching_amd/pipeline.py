@@ -54,6 +54,7 @@ class SGMLRResult(NamedTuple):
 
 WEB_TYPES = {torch.int32: capi.SM_WEB_I32, torch.uint16: capi.SM_WEB_U16, torch.uint8: capi.SM_WEB_U8}
 MAP_TYPES = {torch.int32: capi.SM_MAP_I32, torch.int16: capi.SM_MAP_I16}
+REDUCE_FILTERS = {"box": capi.SM_REDUCE_BOX, "binomial": capi.SM_REDUCE_BINOMIAL}
 
 
 def _ptr(t):
@@ -590,6 +591,59 @@ class StereoPlan:
                                      capi.SM_WMED_FILL if fill else 0, int(fill_min_weight), pairs, _ptr(out), _ptr(filled),
                                      self._stream()))
         return (out, filled) if want_filled else out
+
+    # ---- half-resolution path (reduce -> a matcher on a plan of half_shape() -> upsample) ---
+    def half_shape(self):
+        """(cw, ch) = ((W + 1) >> 1, (H + 1) >> 1): the size reduce_half writes and upsample_double reads; the coarse
+        matcher runs on a second plan, StereoPlan(cw, ch, num_shifts // 2, ...), that the caller makes"""
+        return (self.width + 1) >> 1, (self.height + 1) >> 1
+
+    def _coarse(self, t, dtype, name):
+        cw, ch = self.half_shape()
+        if t.device != self._dev or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"{name}: need a contiguous {dtype} tensor on {self._dev}, got {t.dtype} on {t.device}")
+        if t.dim() == 2:
+            t = t.unsqueeze(0)
+        if t.dim() != 3 or t.shape[1] != ch or t.shape[2] != cw:
+            raise ValueError(f"{name}: shape {tuple(t.shape)} is not (pairs, {ch}, {cw})")
+        return t
+
+    def reduce_half(self, images, filter="binomial", out=None):
+        """Images of the plan's size reduced by two in each direction (sm_reduce_half) -> uint8 (images, ch, cw).
+        images: uint8 (n, H, W), n up to 2 * max_pairs (both sides of a batch in one call); filter: "binomial"
+        ([1, 3, 3, 1] in each direction) or "box" (the 2 x 2 mean), both centred on the 2 x 2 block and rounded."""
+        if filter not in REDUCE_FILTERS:
+            raise ValueError(f"filter: {filter!r} is not one of {sorted(REDUCE_FILTERS)}")
+        images = self._images(images, torch.uint8, "images")
+        n = images.shape[0]
+        if out is None:
+            cw, ch = self.half_shape()
+            out = torch.empty((n, ch, cw), dtype=torch.uint8, device=self._dev)
+        else:
+            out = self._coarse(out, torch.uint8, "out")
+            if out.shape[0] < n:
+                raise ValueError(f"out: room for {out.shape[0]} images, {n} given")
+        check(lib.sm_reduce_half(self._h, _ptr(images), REDUCE_FILTERS[filter], n, _ptr(out), self._stream()))
+        return out
+
+    def upsample_double(self, map, guide, guide_coarse, weights, fill=False, out=None):
+        """A map of half_shape() brought to the plan's size along the edges of the guide (sm_upsample_double) -> the fine
+        map, of the coarse map's type (int32 web: 2 v - 1; int16 sub: 2 v - 16).  guide: uint8 images of the plan's
+        size; guide_coarse: the same reduced (reduce_half); weights: 256 integers >= 1 (guide_weights).  A fine pixel
+        becomes the lower weighted median of the valid coarse pixels among its home and the eight around it; where
+        the home is invalid it stays 0 unless fill is set."""
+        if map.dtype not in MAP_TYPES:
+            raise ValueError(f"map: need an int32 (web) or int16 (sub) map, got {map.dtype}")
+        map = self._coarse(map, map.dtype, "map")
+        pairs = map.shape[0]
+        guide = self._images(guide, torch.uint8, "guide")
+        guide_coarse = self._coarse(guide_coarse, torch.uint8, "guide_coarse")
+        if guide.shape[0] != pairs or guide_coarse.shape[0] != pairs:
+            raise ValueError(f"guide, guide_coarse: {guide.shape[0]} and {guide_coarse.shape[0]} images for {pairs} pairs")
+        out = self._out(out, pairs, "out", map.dtype)
+        check(lib.sm_upsample_double(self._h, _ptr(map), MAP_TYPES[map.dtype], _ptr(guide), _ptr(guide_coarse),
+                                     capi.w256(weights), capi.SM_UP_FILL if fill else 0, pairs, _ptr(out), self._stream()))
+        return out
 
     # ---- occlusion-aware interpolation (between the post-filters and step 3) -----
     def reserve_interp(self):
