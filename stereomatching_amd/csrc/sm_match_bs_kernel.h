@@ -13,7 +13,7 @@
 // at a time):
 //   x_i   = L(x+i) ^ R(x+i+d)                      mismatch bit of window column i
 //   Hx    = sum_i x_i        carry-save adder tree  (N inputs -> HB planes)
-//   Sx   += Hx(new row) - Hx(old row)               signed difference, one ripple add on SB planes
+//   Sx   += sum_i x_i(new row) - sum_i x_i(old row)   one signed carry-save network (sm_bs_network.h)
 //   upd   = centre_match & (Sx <= B)                borrow chain of B - Sx
 //   B     = upd ? Sx : B ;  arg = upd ? d : arg     v_bitop3 selects
 // Scores are kept as MISMATCH counts: the reference's score is
@@ -79,12 +79,7 @@ __device__ __forceinline__ u32 bop(u32 a, u32 b, u32 c)
 {
     return __builtin_amdgcn_bitop3_b32(a, b, c, IMM);   // bit (a<<2|b<<1|c) of IMM
 }
-#define BOP_XOR3 0x96      // a ^ b ^ c
-#define BOP_MAJ 0xE8       // majority(a, b, c)
-#define BOP_BORROW 0x8E    // majority(~a, b, c): borrow out of a - b - c
-#define BOP_SEL 0xCA       // a ? b : c
-#define BOP_XOR_AND 0x28   // (a ^ b) & c
-#define BOP_UPD 0x41       // ~(a ^ b) & ~c
+#include "sm_bs_ops.h"         // the immediates (BOP_*) and bits_for, shared with sm_bs_network.h
 
 __device__ __forceinline__ u32 alignbit(u32 hi, u32 lo, u32 sh)
 {
@@ -143,8 +138,6 @@ __device__ __forceinline__ void store_map4(i32 *p, v4i v)
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
 }
 
-constexpr int bits_for(int v) { int b = 0; while ((1 << b) <= v) b++; return b; }   // v < 2^b
-
 // s += h  (s: SB planes, h: HB planes, HB <= SB; the sum is known to fit)
 template <int SB, int HB>
 __device__ __forceinline__ void add_planes(u32 (&s)[SB], const u32 (&h)[HB])
@@ -190,9 +183,8 @@ __device__ __forceinline__ void add_planes(u32 (&s)[SB], const u32 (&h)[HB])
 // s_nop behind each alignbit 2.7.  SM_SYNC() emits that s_nop (fewer of them: measured in
 // profiles/r02/ab_nop_levels.txt).
 #define SM_SYNC() do { asm volatile("s_nop 0"); SM_PIN(); } while (0)
-#define BOP_ANDN 0x0C      // ~a & b
-#define BOP_ORN 0xCF       // ~a | b   (a ? b : all ones)
-#define BOP_XNOR 0xC3      // ~(a ^ b)            (c ignored)
+
+#include "sm_bs_network.h"   // the steady-state row step: S += (entering row) - (leaving row) in one network
 
 // carry-save trees: N one-bit inputs -> their count on HB planes, for IT counters side by side.
 // Inputs come from xin(item, i), made when first used
@@ -276,49 +268,6 @@ __device__ __forceinline__ void add_lockstep(u32 (&S)[DS][SB], int dd0, const u3
             if (k < HB) S[dd0 + g][k] = bop<BOP_XOR3>(S[dd0 + g][k], h[g][k], c[g]);
             else S[dd0 + g][k] ^= c[g];
             SM_PIN();
-        }
-#pragma unroll
-        for (int g = 0; g < GS; g++) c[g] = cn[g];
-        SM_SYNC();
-    }
-}
-
-// S[dd0 + g] += hn[g] - ho[g] for g < GS side by side: the HB-plane differences in two's
-// complement (sign = borrow out), then one ripple add of the sign-extended differences
-template <int SB, int HB, int GS, int DS>
-__device__ __forceinline__ void addsub_lockstep(u32 (&S)[DS][SB], int dd0, const u32 (&hn)[GS][HB],
-                                                const u32 (&ho)[GS][HB])
-{
-    u32 dl[GS][HB], b[GS];
-#pragma unroll
-    for (int g = 0; g < GS; g++) { b[g] = bop<BOP_ANDN>(hn[g][0], ho[g][0], 0u); SM_PIN(); }
-#pragma unroll
-    for (int g = 0; g < GS; g++) { dl[g][0] = hn[g][0] ^ ho[g][0]; SM_PIN(); }
-#pragma unroll
-    for (int k = 1; k < HB; k++) {
-#pragma unroll
-        for (int g = 0; g < GS; g++) { dl[g][k] = bop<BOP_XOR3>(hn[g][k], ho[g][k], b[g]); SM_PIN(); }
-#pragma unroll
-        for (int g = 0; g < GS; g++) { b[g] = bop<BOP_BORROW>(hn[g][k], ho[g][k], b[g]); SM_PIN(); }
-        SM_SYNC();
-    }
-    u32 c[GS];
-#pragma unroll
-    for (int g = 0; g < GS; g++) { c[g] = S[dd0 + g][0] & dl[g][0]; SM_PIN(); }
-#pragma unroll
-    for (int g = 0; g < GS; g++) { S[dd0 + g][0] ^= dl[g][0]; SM_PIN(); }
-#pragma unroll
-    for (int k = 1; k < SB; k++) {
-        u32 cn[GS];
-#pragma unroll
-        for (int g = 0; g < GS; g++) {
-            const u32 a = k < HB ? dl[g][k] : b[g];
-            if (k + 1 < SB) { cn[g] = bop<BOP_MAJ>(S[dd0 + g][k], a, c[g]); SM_PIN(); } else cn[g] = 0;
-        }
-#pragma unroll
-        for (int g = 0; g < GS; g++) {
-            const u32 a = k < HB ? dl[g][k] : b[g];
-            S[dd0 + g][k] = bop<BOP_XOR3>(S[dd0 + g][k], a, c[g]); SM_PIN();
         }
 #pragma unroll
         for (int g = 0; g < GS; g++) c[g] = cn[g];
@@ -513,7 +462,7 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
     };
 
     constexpr int GW = DS >= 4 ? 4 : DS;      // shifts side by side in a warm-up row
-    constexpr int GS = 2;                     // ... in a steady-state row (2 x {row in, row out})
+    constexpr int GS = DS >= 4 ? 4 : DS;      // ... in a steady-state row
     static_assert(DS % GW == 0 && DS % GS == 0, "shift groups");
     // warm-up: one window row into all sums, GW shifts side by side
     auto slide_in = [&](int srow) {
@@ -538,7 +487,9 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
             add_lockstep<SB, HB, GW, DS>(S, dd0, h);
         }
     };
-    // steady state: one row in and one row out, GS shifts x {in, out} side by side
+    // steady state: one row in and one row out, GS shifts side by side; the N entering and the N
+    // leaving mismatch bits of a shift and its SB sum planes go through one signed carry-save
+    // network (sm_bs_network.h), which resolves to the new planes once
     auto slide_views = [&](const RowViews &vn, const RowViews &vo) {
         u32 rn[N + GS - 1], ro[N + GS - 1];
 #pragma unroll
@@ -553,20 +504,15 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
                 ro[N - 1 + m] = rview(vo, dd0 + N - 1 + m); SM_PIN();
             }
             SM_SYNC();
-            u32 h[2 * GS][HB];                // item 2g = shift dd0 + g row in, 2g + 1 = row out
-            count_lockstep<N, HB, 2 * GS>([&](int it, int i) -> u32 {
-                const u32 l = (it & 1) ? vo.lv[i] : vn.lv[i];
-                const u32 r = (it & 1) ? ro[(it >> 1) + i] : rn[(it >> 1) + i];
-                const u32 x = GHOST ? bop<BOP_XOR_AND>(l, r, cvv[i]) : (l ^ r);
+            // input i < N: column i of the entering row, N + i: column i of the leaving row
+            network_lockstep<N, SB, GS, DS>(S, dd0, [&](int it, int i) -> u32 {
+                const int col = i < N ? i : i - N;
+                const u32 l = i < N ? vn.lv[col] : vo.lv[col];
+                const u32 r = i < N ? rn[it + col] : ro[it + col];
+                const u32 x = GHOST ? bop<BOP_XOR_AND>(l, r, cvv[col]) : (l ^ r);
                 SM_PIN();
                 return x;
-            }, h);
-            u32 hn[GS][HB], ho[GS][HB];
-#pragma unroll
-            for (int gq = 0; gq < GS; gq++)
-#pragma unroll
-                for (int k = 0; k < HB; k++) { hn[gq][k] = h[2 * gq][k]; ho[gq][k] = h[2 * gq + 1][k]; }
-            addsub_lockstep<SB, HB, GS, DS>(S, dd0, hn, ho);
+            });
             SM_SYNC();
         }
     };
