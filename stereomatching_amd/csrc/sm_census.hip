@@ -28,6 +28,7 @@
 //                       equiangular fit.
 
 #include "sm_device.h"
+#include "sm_plan_model.h"
 
 typedef unsigned long long u64;
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
@@ -536,8 +537,7 @@ static int wta_launch(const sm_plan *plan, int cw, bool mirror, int pairs, i32 *
         g.dc = min(SMN_DCHUNK, g.D - dlo);
         g.first = dlo == 0;
         g.last = dlo + g.dc >= g.D;
-        g.nl = 1; g.log2nl = 0;
-        while (g.nl * SMN_DS < g.dc) { g.nl <<= 1; g.log2nl++; }
+        g.nl = sm_lanes_for(g.dc, SMN_DS, &g.log2nl);
         // column groups: up to 64 (256 columns) and 512 threads, fewer while the LDS request exceeds 64 KiB; at least one
         // output group between the halo groups
         g.cg = min(64, SMN_THREADS / g.nl);
@@ -557,9 +557,7 @@ static int wta_launch(const sm_plan *plan, int cw, bool mirror, int pairs, i32 *
             return sm_fail(SM_ERR_HIP, "census: internal tiling error (pf %d, %zu bytes of LDS)", g.pf, lds);
         g.tw = 4 * (g.cg - 2 * g.hg);
         g.tiles_x = (g.w + g.tw - 1) / g.tw;
-        int th = 64;
-        while (th > 8 && (long long)g.tiles_x * ((g.h + th - 1) / th) * pairs < 1024) th >>= 1;
-        g.th = min(th, g.h);
+        g.th = min(sm_rows_for_grid(g.tiles_x, g.h, pairs), g.h);
         g.tiles_y = (g.h + g.th - 1) / g.th;
         void *args[] = {(void *)&plan->d_census, (void *)&d_web, (void *)&d_best, (void *)&g};
         const hipError_t e = hipLaunchKernel(fn, dim3(g.tiles_x, g.tiles_y, pairs), dim3(T), args, lds, st);

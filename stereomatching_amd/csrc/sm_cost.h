@@ -3,24 +3,18 @@
 // sm_cost_mfma.hip: SSD on the matrix cores; sm_cost_strip.hip: the ghost-border strip).
 #pragma once
 #include "sm_internal.h"
+#include "sm_geom.h"
+#include "sm_plan_model.h"
 
-struct SadGeom {
-    int w, h, D;
-    int ghost;
-    int tile_h, tw;          // output rows / columns per (one-wave) workgroup
-    int nl, log2nl;          // lanes that split the shift range of one pixel group
-    int nql, px;             // shift quads and pixels per lane (the kernel's template arguments)
-    int tiles_x, tiles_y;
-    int padl;                // bytes left of the tile in a staged row (multiple of 4, >= half + 3)
-    int lrow, rrow;          // bytes per staged row, left / right (multiples of 8)
-    int nsr;                 // staged rows = tile_h + n - 1
-    int q_tail;              // first quad of a lane that may hold shifts >= D
-    int q_last;              // last quad in which some lane has a shift < D
-    int fast_stage;          // image rows are dword-aligned and w % 4 == 0
-    int tbl_pad;             // k_ssd_mfma: dwords between the staged rows and its (16-byte aligned) RR table
-    int lds_bytes;
-    int waves;               // k_sad_pc: waves per workgroup (they share the staged rows; the other kernels: 1)
-};
+// what the cost planners of sm_plan_model.h take of a plan and of a launch's images
+static inline PlanShape sm_cost_shape(const sm_plan *plan)
+{
+    return {plan->width, plan->height, plan->num_shifts, plan->square_width, plan->border, plan->max_pairs, plan->opt};
+}
+static inline bool sm_cost_aligned4(const void *d_left, const void *d_right)
+{
+    return ((uintptr_t)d_left & 3) == 0 && ((uintptr_t)d_right & 3) == 0;
+}
 
 #ifdef __HIPCC__
 // Stage rows ty0 - half .. ty0 - half + nsr - 1 of one pair's two gray images into LDS, [nsr][lrow]

@@ -262,8 +262,7 @@ static int launch_general(sm_plan *plan, const uint8_t *d_gray_left, const uint8
     g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts;
     g.half = plan->square_width / 2; g.n = 2 * g.half + 1;
     SM_TRY(sm_check_reach(plan, 512, "sm_cost_wta"));
-    g.nl = 1; g.log2nl = 0;
-    while (g.nl * SMC_DS < g.D) { g.nl <<= 1; g.log2nl++; }
+    g.nl = sm_lanes_for(g.D, SMC_DS, &g.log2nl);
     // 256 threads = 256 / nl pixel groups per workgroup
     g.groups = 256 / g.nl;
     g.tw = g.groups * SMC_PX;
@@ -274,8 +273,7 @@ static int launch_general(sm_plan *plan, const uint8_t *d_gray_left, const uint8
     g.lrow = 4 * ((g.pad + g.tw + 4 * (nwd + 1) + 3) / 4);
     g.rrow = 4 * ((g.pad + g.tw + g.nl * SMC_DS + 4 * (nwd + 4) + 3) / 4);
     g.tiles_x = (g.w + g.tw - 1) / g.tw;
-    int th = 64;
-    while (th > 8 && (long long)g.tiles_x * ((g.h + th - 1) / th) * pairs < 1024) th >>= 1;
+    int th = sm_rows_for_grid(g.tiles_x, g.h, pairs);
     while ((th + g.n - 1) * (g.lrow + g.rrow) > 60 * 1024 && th > 1) th >>= 1;
     th = th < g.h ? th : g.h;
     g.tile_h = th;

@@ -42,9 +42,7 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ u32 sdot4(u32 a, u32 b, u32 acc) { return (u32)__builtin_amdgcn_sdot4((int)a, (int)b, (int)acc, false); }
 
-// waves per SIMD the register count allows: the NB x 16 accumulators are most of it
-constexpr int mfma_waves(int nb) { return nb <= 3 ? 4 : nb <= 5 ? 3 : 2; }
-
+// (mfma_waves(NB), the waves per SIMD the register count allows: sm_plan_model.h, where the planner reads it too)
 template <int N, int NB>
 __global__ __launch_bounds__(256, mfma_waves(NB)) void k_ssd_mfma(const u8 *__restrict__ left, const u8 *__restrict__ right,
                                                     i32 *__restrict__ web, i32 *__restrict__ best,
@@ -267,79 +265,18 @@ static const void *mfma_ptr(int nb)
     return nullptr;
 }
 
-// fills g and returns the kernel, or nullptr if this shape is not built (caller falls back)
+// fills g and returns the kernel, or nullptr if this shape is not built (caller falls back): the geometry is
+// sm_plan_ssd_mfma's (sm_plan_model.h), here only its key becomes a function
 const void *sm_ssd_mfma_configure(const sm_plan *plan, int pairs, const void *d_left, const void *d_right, SadGeom *out)
 {
-    SadGeom g;
-    g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts; g.waves = 1;
-    const int half = plan->square_width / 2, n = 2 * half + 1;
-    g.ghost = plan->border == SM_GHOST;
-    if (n < 3 || n > 11 || g.D > 256 || plan->opt.cost_kernel == 1) return nullptr;
-    const int nb = (g.D + 31 + 31) / 32;                // right positions 0 .. D + 30
-    g.nl = 1; g.log2nl = 0; g.nql = 0; g.px = 1; g.q_tail = 0; g.q_last = 0;
-    g.padl = 4 * ((half + 3 + 3) / 4);
-    const int per_simd = mfma_waves(nb);
-    const int slots = 256 * 4 * per_simd;
-    // workgroup width (1, 2 or 4 waves sharing the staged rows) and tile height together: whole rounds of the waves
-    // the registers allow per SIMD; rows + warm-up (a warm-up row costs ~0.6 of an output row) + staging per wave
-    auto shape = [&](int wv, int *lrow, int *rrow, int *tbl) {
-        // a lane reads 5 dwords from dword (padl + 32 wave + xl - half) / 4 (+ 8 b in the right row)
-        *lrow = 8 * ((g.padl + 32 * wv + 24 + 7) / 8);
-        *rrow = 8 * ((g.padl + 32 * (nb + wv - 1) + 24 + 7) / 8);
-        *tbl = wv * (4 * 32 * nb + 16);      // the tables: 32 nb entries per wave, 16-byte aligned behind the staged rows
-    };
-    // (the plan's own choice is between ONE and FOUR waves: two were measured no better than one at equal tile heights and
-    // slower at the taller tiles the model gives them -- C5: 0.427 / 0.447 / 0.391 ms at 1 / 2 / 4 waves,
-    // profiles/r05/ab_ssd_workgroup_waves.txt -- for a reason that was not found; an explicit 2 is honoured)
-    int best_th = 0, best_wv = 1; double best_cost = 0;
-    auto search = [&](int only) {           // only: the one width to consider; 0: the plan's own choice
-        for (int wv = 1; wv <= 4; wv *= 2) {
-            if (only ? only != wv : wv == 2) continue;
-            int lrow, rrow, tbl;
-            shape(wv, &lrow, &rrow, &tbl);
-            if (wv > 1 && 32 * wv / 2 >= g.w) break;
-            if (lrow + rrow > 4 * 4 * 64 * wv) continue;         // (the fast staging path's reach)
-            const int tiles_x = (g.w + 32 * wv - 1) / (32 * wv);
-            for (int th = 8; th <= 128; th += 4) {
-                const size_t lds = (size_t)(th + n - 1) * (lrow + rrow) + tbl;
-                if (lds > (size_t)wv * (160 * 1024 / (4 * per_simd)) || lds > 64 * 1024) break;
-                const long long waves = (long long)tiles_x * ((g.h + th - 1) / th) * pairs * wv;
-                const long long rounds = (waves + slots - 1) / slots;
-                const double cost = (double)rounds * (th + 0.6 * (n - 1) + 2.0);
-                if (!best_th || cost < best_cost * (wv > best_wv ? 0.97 : 1.0)) { best_th = th; best_wv = wv; best_cost = cost; }
-            }
-        }
-    };
-    // an explicit width where it applies; one that does not (not 1, 2 or 4, or wider than the image) is ignored, as
-    // k_sad_pc ignores it.  The plan's own choice always finds the one-wave shape (D <= 256: at most ~8 KB of LDS).
-    search(plan->opt.cost_workgroup_waves);
-    if (!best_th) search(0);
-    if (!best_th) return nullptr;
-    g.waves = best_wv;
-    int tbl_bytes;
-    shape(g.waves, &g.lrow, &g.rrow, &tbl_bytes);
-    g.tw = 32 * g.waves;
-    g.tiles_x = (g.w + g.tw - 1) / g.tw;
-    if (plan->opt.cost_tile_h > 0) {         // an explicit tile height, clamped to what a workgroup's LDS holds
-        best_th = plan->opt.cost_tile_h;
-        while (best_th > 1 && (size_t)(best_th + n - 1) * (g.lrow + g.rrow) + tbl_bytes > 64 * 1024) best_th--;
+    const CostKernelKey k = sm_plan_ssd_mfma(sm_cost_shape(plan), pairs, sm_cost_aligned4(d_left, d_right), out);
+    if (k.family != SM_COST_KERNEL_SSD_MFMA) return nullptr;
+    switch (k.n) {
+    case 3: return mfma_ptr<3>(k.nb);
+    case 5: return mfma_ptr<5>(k.nb);
+    case 7: return mfma_ptr<7>(k.nb);
+    case 9: return mfma_ptr<9>(k.nb);
+    case 11: return mfma_ptr<11>(k.nb);
     }
-    g.tile_h = best_th < g.h ? best_th : g.h;
-    g.tiles_y = (g.h + g.tile_h - 1) / g.tile_h;
-    g.nsr = g.tile_h + n - 1;
-    g.fast_stage = g.w % 4 == 0 && ((uintptr_t)d_left & 3) == 0 && ((uintptr_t)d_right & 3) == 0 &&
-                   g.lrow + g.rrow <= 4 * 4 * 64 * g.waves;
-    // dwords between the end of the staged rows and the table: whatever makes the table 16-byte aligned
-    g.tbl_pad = (4 - (g.nsr * ((g.lrow + g.rrow) >> 2)) % 4) % 4;
-    g.lds_bytes = g.nsr * (g.lrow + g.rrow) + tbl_bytes;
-    const void *fn = nullptr;
-    switch (n) {
-    case 3: fn = mfma_ptr<3>(nb); break;
-    case 5: fn = mfma_ptr<5>(nb); break;
-    case 7: fn = mfma_ptr<7>(nb); break;
-    case 9: fn = mfma_ptr<9>(nb); break;
-    case 11: fn = mfma_ptr<11>(nb); break;
-    }
-    *out = g;
-    return fn;
+    return nullptr;
 }

@@ -355,104 +355,20 @@ static const void *sad_pc_ptr(int nql)
     return nullptr;
 }
 
-// fills g and returns the kernel, or nullptr if this shape is not built (caller falls back to k_sad_qs, then the general kernel)
+// fills g and returns the kernel, or nullptr if this shape is not built (caller falls back to k_sad_qs, then the general
+// kernel): the geometry is sm_plan_sad_pc's (sm_plan_model.h), here only its key becomes a function
 const void *sm_sad_pc_configure(const sm_plan *plan, int pairs, const void *d_left, const void *d_right, SadGeom *out)
 {
-    SadGeom g;
-    g.tbl_pad = 0;                          // (the SSD kernel's)
-    g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts;
-    const int half = plan->square_width / 2, n = 2 * half + 1;
-    g.ghost = plan->border == SM_GHOST;
-    if (n < 3 || n > 15 || g.D > 512 || plan->opt.cost_kernel == 1) return nullptr;
-    const int nq = (g.D + 3 + 3) / 4;               // quads that cover shifts -3 .. D-1
-    const int px = 4;
-    const int nql = nq <= 5 ? 5 : nq <= 9 ? 9 : 17;
-    g.nl = 1; g.log2nl = 0;
-    while (g.nl * nql < nq) { g.nl <<= 1; g.log2nl++; }
-    if (g.nl > 16) return nullptr;
-    const int ng = n / 4 + 1;
-    g.padl = 4 * ((half + 3 + 3) / 4);
-    g.q_tail = (g.D - 4 * (g.nl - 1) * nql) / 4;
-    if (g.q_tail < 0) g.q_tail = 0;
-    g.q_last = g.nl > 1 ? nql - 1 : (g.D + 2) / 4;
-    if (g.q_last > nql - 1) g.q_last = nql - 1;
-    // Workgroup = 1, 2 or 4 waves side by side (each its own 64 / nl pixel groups) sharing the staged rows: with many
-    // shifts a lone wave's tile is narrow (64 pixels at 256 shifts) under a right-image span of 4 (nl nql + ..) bytes,
-    // its 20 KB of LDS hold few rows and the n - 1 warm-up rows weigh a quarter of the launch (C5: 16-row tiles);
-    // four waves share one span and slide 64 rows.  Tile height and workgroup width together: whole rounds of two
-    // waves per SIMD, rows + warm-up (a warm-up row costs ~0.41 of an output row here) + staging per workgroup.
-    const int slots = 256 * 4 * 2;
-    int best_th = 0, best_wv = 0; double best_cost = 0;
-    auto row_bytes = [&](int wv, int *lrow, int *rrow) {
-        const int tw = 4 * px * (16 / g.nl) * wv;
-        // left row: dwords up to bL2 + PX - 1 (<= bL + FG + PX) of the last pixel group; right: aligned up to
-        // bR + NQL - 1 + max(NG, PX - 1) + 1, shifted up to bR + NQL - 1 + FG + PX - 1 + 1 (+1: the bytes they are cut from)
-        *lrow = 8 * ((g.padl + tw + 4 * (ng + 3) + 7) / 8);
-        *rrow = 8 * ((g.padl + tw + 4 * (g.nl * nql + ng + px + 2) + 7) / 8);
-        return tw;
-    };
-    for (int wv = 1; wv <= 4; wv *= 2) {
-        int lrow, rrow;
-        const int tw = row_bytes(wv, &lrow, &rrow);
-        if (wv > 1 && tw / 2 >= g.w) break;              // (a workgroup wider than the image)
-        if (lrow + rrow > 4 * 4 * 64 * wv) continue;     // (the fast staging path's reach)
-        const int tiles_x = (g.w + tw - 1) / tw;
-        for (int th = 8; th <= 128; th += 4) {
-            const size_t lds = (size_t)(th + n - 1) * (lrow + rrow) + 4 * (size_t)rrow;
-            if (lds > (size_t)wv * 160 * 1024 / 8) break;
-            const long long waves = (long long)tiles_x * ((g.h + th - 1) / th) * pairs * wv;
-            const long long rounds = (waves + slots - 1) / slots;
-            const double cost = (double)rounds * (th + 0.41 * (n - 1) + 2.0);
-            if (!best_th || cost < best_cost * (wv > best_wv ? 0.97 : 1.0)) { best_th = th; best_wv = wv; best_cost = cost; }
-        }
+    const CostKernelKey k = sm_plan_sad_pc(sm_cost_shape(plan), pairs, sm_cost_aligned4(d_left, d_right), out);
+    if (k.family != SM_COST_KERNEL_SAD_PC) return nullptr;
+    switch (k.n) {
+    case 3: return sad_pc_ptr<3>(k.nql);
+    case 5: return sad_pc_ptr<5>(k.nql);
+    case 7: return sad_pc_ptr<7>(k.nql);
+    case 9: return sad_pc_ptr<9>(k.nql);
+    case 11: return sad_pc_ptr<11>(k.nql);
+    case 13: return sad_pc_ptr<13>(k.nql);
+    case 15: return sad_pc_ptr<15>(k.nql);
     }
-    if (!best_th) return nullptr;
-    int forced_wv = 0;
-    if (plan->opt.cost_workgroup_waves == 1 || plan->opt.cost_workgroup_waves == 2 || plan->opt.cost_workgroup_waves == 4) {
-        int lrow, rrow;                       // an explicit width applies where the staging path reaches it
-        row_bytes(plan->opt.cost_workgroup_waves, &lrow, &rrow);
-        if (lrow + rrow <= 4 * 4 * 64 * plan->opt.cost_workgroup_waves) forced_wv = plan->opt.cost_workgroup_waves;
-    }
-    if (forced_wv && forced_wv != best_wv) {
-        // (the height the model gives that width)
-        int lrow, rrow;
-        const int tw = row_bytes(forced_wv, &lrow, &rrow);
-        const int tiles_x = (g.w + tw - 1) / tw;
-        best_th = 0;
-        for (int th = 8; th <= 128; th += 4) {
-            const size_t lds = (size_t)(th + n - 1) * (lrow + rrow) + 4 * (size_t)rrow;
-            if (lds > (size_t)forced_wv * 160 * 1024 / 8) break;
-            const long long waves = (long long)tiles_x * ((g.h + th - 1) / th) * pairs * forced_wv;
-            const long long rounds = (waves + slots - 1) / slots;
-            const double cost = (double)rounds * (th + 0.41 * (n - 1) + 2.0);
-            if (!best_th || cost < best_cost) { best_th = th; best_cost = cost; }
-        }
-        if (!best_th) best_th = 8;
-        best_wv = forced_wv;
-    }
-    g.waves = best_wv;
-    g.tw = row_bytes(g.waves, &g.lrow, &g.rrow);
-    g.tiles_x = (g.w + g.tw - 1) / g.tw;
-    const size_t lds_cap = (size_t)g.waves * 160 * 1024 / 8;      // (beyond 64 KB: sm_cost_wta raises the kernel's limit)
-    if (plan->opt.cost_tile_h > 0) best_th = plan->opt.cost_tile_h;      // an explicit tile height, clamped to what a workgroup's LDS holds
-    while (best_th > 1 && (size_t)(best_th + n - 1) * (g.lrow + g.rrow) + 4 * (size_t)g.rrow > lds_cap) best_th--;
-    g.tile_h = best_th < g.h ? best_th : g.h;
-    g.tiles_y = (g.h + g.tile_h - 1) / g.tile_h;
-    g.nsr = g.tile_h + n - 1;
-    g.fast_stage = g.w % 4 == 0 && ((uintptr_t)d_left & 3) == 0 && ((uintptr_t)d_right & 3) == 0 &&
-                   g.lrow + g.rrow <= 4 * 4 * 64 * g.waves;
-    g.lds_bytes = g.nsr * (g.lrow + g.rrow) + 4 * g.rrow;
-    g.nql = nql; g.px = px;
-    const void *fn = nullptr;
-    switch (n) {
-    case 3: fn = sad_pc_ptr<3>(nql); break;
-    case 5: fn = sad_pc_ptr<5>(nql); break;
-    case 7: fn = sad_pc_ptr<7>(nql); break;
-    case 9: fn = sad_pc_ptr<9>(nql); break;
-    case 11: fn = sad_pc_ptr<11>(nql); break;
-    case 13: fn = sad_pc_ptr<13>(nql); break;
-    case 15: fn = sad_pc_ptr<15>(nql); break;
-    }
-    *out = g;
-    return fn;
+    return nullptr;
 }

@@ -309,66 +309,16 @@ static const void *sad_qs_ptr(int nql, int px)
     return nullptr;
 }
 
-// fills g and returns the kernel, or nullptr if this shape is not built (caller falls back)
+// fills g and returns the kernel, or nullptr if this shape is not built (caller falls back): the geometry is
+// sm_plan_sad_qs's (sm_plan_model.h), here only its key becomes a function
 const void *sm_sad_qs_configure(const sm_plan *plan, int pairs, const void *d_left, const void *d_right, SadGeom *out)
 {
-    SadGeom g;
-    g.tbl_pad = 0;                          // (the SSD kernel's)
-    g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts; g.waves = 1;
-    const int half = plan->square_width / 2, n = 2 * half + 1;
-    g.ghost = plan->border == SM_GHOST;
-    // (8 key bits for the shift: up to 240 shifts)
-    if (n < 17 || n > 21 || g.D > 240 || plan->opt.cost_kernel == 1) return nullptr;
-    const int nq = (g.D + 3 + 3) / 4;               // quads that cover shifts -3 .. D-1
-    int nql, px;
-    if (nq <= 5) { nql = 5; px = 4; }
-    else if (nq <= 9) { nql = 9; px = 2; }
-    else { nql = 17; px = 2; }
-    g.nl = 1; g.log2nl = 0;
-    while (g.nl * nql < nq) { g.nl <<= 1; g.log2nl++; }
-    g.tw = 4 * px * (16 / g.nl);
-    g.tiles_x = (g.w + g.tw - 1) / g.tw;
-    const int ng = n / 4 + 1;
-    g.padl = 4 * ((half + 3 + 3) / 4);
-    // left row: dwords bL .. bL + NG + PX - 1 of the last pixel group; right: up to bR + NQL - 1 + NG + PX - 1 (+1 for the pair)
-    g.lrow = 8 * ((g.padl + g.tw + 4 * (ng + 1) + 7) / 8);
-    g.rrow = 8 * ((g.padl + g.tw + 4 * (g.nl * nql + ng + 2) + 7) / 8);
-    // last quad (of the last shift-lane) whose four shifts are all below D for every lane: rho <= 3
-    g.q_tail = (g.D - 4 * (g.nl - 1) * nql) / 4;
-    if (g.q_tail < 0) g.q_tail = 0;
-    // ... and the last quad that holds a shift below D for some lane (rho = 3); with several
-    // shift-lanes the lower ones need all their quads
-    g.q_last = g.nl > 1 ? nql - 1 : (g.D + 2) / 4;
-    if (g.q_last > nql - 1) g.q_last = nql - 1;
-    // tile height: whole rounds of two waves per SIMD; rows + warm-up + staging per workgroup
-    const int slots = 256 * 4 * 2;
-    int best_th = 0; double best_cost = 0;
-    for (int th = 8; th <= 128; th += 4) {
-        const size_t lds = (size_t)(th + n - 1) * (g.lrow + g.rrow) + 2 * (size_t)g.rrow;
-        if (lds > 160 * 1024 / 8) break;
-        const long long tiles = (long long)g.tiles_x * ((g.h + th - 1) / th) * pairs;
-        const long long rounds = (tiles + slots - 1) / slots;
-        const double cost = (double)rounds * (th + 0.45 * (n - 1) + 2.0);
-        if (!best_th || cost < best_cost) { best_th = th; best_cost = cost; }
+    const CostKernelKey k = sm_plan_sad_qs(sm_cost_shape(plan), pairs, sm_cost_aligned4(d_left, d_right), out);
+    if (k.family != SM_COST_KERNEL_SAD_QS) return nullptr;
+    switch (k.n) {
+    case 17: return sad_qs_ptr<17>(k.nql, k.px);
+    case 19: return sad_qs_ptr<19>(k.nql, k.px);
+    case 21: return sad_qs_ptr<21>(k.nql, k.px);
     }
-    if (!best_th) return nullptr;
-    if (plan->opt.cost_tile_h > 0) {         // an explicit tile height, clamped to what a workgroup's LDS holds
-        best_th = plan->opt.cost_tile_h;
-        while (best_th > 1 && (size_t)(best_th + n - 1) * (g.lrow + g.rrow) + 2 * (size_t)g.rrow > 64 * 1024) best_th--;
-    }
-    g.tile_h = best_th < g.h ? best_th : g.h;
-    g.tiles_y = (g.h + g.tile_h - 1) / g.tile_h;
-    g.nsr = g.tile_h + n - 1;
-    g.fast_stage = g.w % 4 == 0 && ((uintptr_t)d_left & 3) == 0 && ((uintptr_t)d_right & 3) == 0 &&
-                   g.lrow + g.rrow <= 4 * 256;
-    g.lds_bytes = g.nsr * (g.lrow + g.rrow) + 2 * g.rrow;
-    g.nql = nql; g.px = px;
-    const void *fn = nullptr;
-    switch (n) {
-    case 17: fn = sad_qs_ptr<17>(nql, px); break;
-    case 19: fn = sad_qs_ptr<19>(nql, px); break;
-    case 21: fn = sad_qs_ptr<21>(nql, px); break;
-    }
-    *out = g;
-    return fn;
+    return nullptr;
 }

@@ -8,6 +8,7 @@
 #include <stdio.h>
 
 #include "stereo_hip.h"
+#include "sm_geom.h"
 
 typedef uint32_t u32;
 typedef uint8_t u8;
@@ -28,47 +29,6 @@ typedef int32_t i32;
 // the needed extents include the D-shift, the window halo and tile round-up.
 // Workspace layout: [pair][side: 0 = left, 1 = right][ext_rows][ext_words].
 // ---------------------------------------------------------------------------
-
-enum { SM_KERNEL_A = 0, SM_KERNEL_B = 1, SM_KERNEL_C = 2, SM_KERNEL_GENERIC = 3, SM_KERNEL_BS = 4 };
-
-#define SM_DSET 16   // shifts per lane in the tiled kernels
-#define SM_P 8       // pixels per lane
-#define SM_PADT 32   // left pad of a tile's LDS rows, in pixels
-#define SM_KEY_DBITS 10  // low bits of the winner key hold the shift
-
-struct MatchGeom {
-    int w, h;            // image size
-    int D;               // number of shifts
-    int n, half;         // window side (odd) and its half
-    int ext_words;       // u32 words per ext row
-    int ext_rows;        // ext rows per image
-    long long ext_image_words;  // ext_words * ext_rows
-    int pad_l;           // pixels of left pad in the ext image (multiple of 32)
-    // tiled kernels only
-    int tile_h;          // output rows per workgroup
-    int tw;              // output columns per workgroup (= 8 * runs)
-    int runs;            // pixel runs (of 8) per workgroup
-    int ds;              // shifts per lane (16; 8 or 16 in the bit-sliced kernel)
-    int nl, log2nl;      // lanes that split the shift range of one run
-    int threads;         // runs * nl
-    int plw, prw;        // words per staged LDS row, left / right
-    int nsr;             // staged rows = tile_h + n - 1
-    int tiles_x, tiles_y;
-    int vec_ok;          // rows are 16-byte aligned -> int4 stores
-    int lds_bytes;
-    int cap2;            // bit-sliced kernel: launch the two-waves-per-SIMD variant
-    int duo;             // bit-sliced kernel: two-wave workgroups of 2 * tile_h rows (shared warm-up)
-    int unused[4];       // (where the retired priority fields were: the kernel arguments 16 bytes shorter measured
-                         //  2 % slower in the C1 step, edges + match, same device; no kernel reads these words)
-    int xmerge;          // bit-sliced kernel: the shift lanes of a word are merged through LDS every 4 rows (nl >= 4)
-    int xm_off;          // ... word offset in LDS where the exchange slots of a two-wave workgroup meet and the
-                         //     merge buffers lie (wave 0's from here up, wave 1's from here down; a lone wave's from here up)
-    int xm_words;        // ... words of one wave's merge buffer
-    int web_bytes;       // bytes per element of the web map of THIS launch: 4 (int32), 2, 1
-    // ext words per row that can reach a valid output pixel (left image: columns up to W - 1 + half;
-    // right: + D - 1 more); the edge kernels compute no others (the tile round-up stays zero)
-    int edge_words_l, edge_words_r;
-};
 
 struct sm_plan {
     int device;
@@ -248,9 +208,8 @@ int sm_census_descriptors(sm_plan *plan, int cw, const uint8_t *left, const uint
 // sm_filter.hip, for sm_sgm_lr: k_sgm_sub_mask, sub = 0 where web = 0, over n elements
 int sm_sub_mask_launch(const i32 *web, int16_t *sub, long long n, hipStream_t st);
 
-// sm_match_bs.hip (bit-sliced kernel; nullptr if not built for this window)
+// sm_match_bs.hip (bit-sliced kernel; nullptr if not built for this window: sm_bs_built of sm_plan_model.h says which are)
 const void *sm_bs_kernel_ptr(int n, int ds, bool fulld, bool ghost, bool cap2, bool duo = false);
-int sm_bs_default_ds(int n);
 // what ONE launch adds to the plan's geometry: passed by value, the plan is not modified
 struct MatchLaunch {
     MatchGeom g;                        // plan->g with vec_ok / web_bytes of this launch

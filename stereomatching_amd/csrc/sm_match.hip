@@ -47,6 +47,7 @@
 // kernel at the bottom (correct for every input, not tuned).
 
 #include "sm_internal.h"
+#include "sm_plan_model.h"
 
 #include <algorithm>
 #include <cmath>
@@ -453,8 +454,6 @@ __global__ __launch_bounds__(256) void k_match_wta_generic(const u32 *__restrict
 // host side: geometry and launch
 // ---------------------------------------------------------------------------
 
-static int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
 static bool tiled_fulld(const MatchGeom &g) { return g.nl * g.ds == g.D; }
 
 static const void *tiled_kernel_ptr(int mode, bool fulld, bool ghost)
@@ -470,289 +469,49 @@ static const void *tiled_kernel_ptr(int mode, bool fulld, bool ghost)
 #undef SM_ROW
 }
 
+// The one place where the planner's table of builds (sm_kernel_built, sm_plan_model.h) meets the functions: the
+// kernel of key `k`, or an error that names it where the table says "built" and there is no function, or the reverse.
+static int match_kernel_ptr(const KernelKey &k, const void **fn)
+{
+    *fn = k.family == SM_KERNEL_BS ? sm_bs_kernel_ptr(k.n, k.ds, k.fulld, k.ghost, k.cap2, k.duo)
+        : k.family >= SM_KERNEL_A && k.family <= SM_KERNEL_C ? tiled_kernel_ptr(k.family, k.fulld, k.ghost) : nullptr;
+    if ((*fn != nullptr) == sm_kernel_built(k)) return SM_OK;
+    return sm_fail(SM_ERR_ARG, "match kernel (family %d, n = %d, %d shifts/lane, %s D, %s%s%s) is %s", k.family, k.n, k.ds,
+                   k.fulld ? "full" : "partial", k.ghost ? "ghost" : "toroidal", k.cap2 ? ", 2 waves/SIMD variant" : "",
+                   k.duo ? ", two-wave workgroups" : "",
+                   *fn ? "compiled but not in the planner's table of builds" : "in the planner's table of builds but not compiled");
+}
+
+// PlanDevice::occupancy over the runtime; ctx: an int that keeps the first error
+static int match_occupancy(void *ctx, const KernelKey &k, int threads, int lds_bytes)
+{
+    const void *fn;
+    int per_cu = 0;
+    if (int rc = match_kernel_ptr(k, &fn)) {
+        if (!*(int *)ctx) *(int *)ctx = rc;
+        return 0;
+    }
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds_bytes) == hipSuccess ? per_cu : 0;
+}
+
+// fills plan->kernel / plan->g / plan->describe: sm_plan_match (sm_plan_model.h) on this plan's shape, with the
+// device's CU count and the runtime's occupancy answers as the device's facts
 int sm_match_configure(sm_plan *plan)
 {
-    MatchGeom &g = plan->g;
-    const int W = plan->width, H = plan->height, D = plan->num_shifts;
-    g.w = W; g.h = H; g.D = D;
-    g.half = plan->square_width / 2;
-    g.n = 2 * g.half + 1;
-
-    int kernel;
-    if (D > (1 << SM_KEY_DBITS) || g.n > 25) kernel = SM_KERNEL_GENERIC;
-    else if (g.n <= 9) kernel = SM_KERNEL_A;
-    else if (g.n <= 16) kernel = SM_KERNEL_B;
-    else kernel = SM_KERNEL_C;
-    // the bit-sliced kernel where it is built (common windows, D <= 512);
-    // sm_plan_options.kernel_family = 1 keeps the general kernels (A/B testing)
-    const bool ghost = plan->border == SM_GHOST;
-    auto nl_for = [&](int ds, int &log2nl) { int nl = 1; log2nl = 0; while (nl * ds < D) { nl <<= 1; log2nl++; } return nl; };
-    {
-        const bool want_bs = plan->opt.kernel_family != 1;
-        int l2;
-        const int ds0 = sm_bs_default_ds(g.n);
-        if (want_bs && kernel != SM_KERNEL_GENERIC && ds0 && nl_for(ds0, l2) <= 32)
-            kernel = SM_KERNEL_BS;
-    }
-    plan->kernel = kernel;
-
-    if (kernel == SM_KERNEL_GENERIC) {
-        g.pad_l = 32 * ceil_div(std::max(g.half, 1), 32);
-        // word() reads 2 words starting at bit x+d+pad_l with x <= W-1+half
-        g.ext_words = (g.pad_l + W + g.half + D + 31) / 32 + 2;
-        g.ext_rows = H + 2 * g.half;
-        g.ext_image_words = (long long)g.ext_words * g.ext_rows;
-        g.tile_h = g.tw = g.runs = g.nl = g.log2nl = g.threads = g.ds = 0;
-        g.plw = g.prw = g.nsr = g.tiles_x = g.tiles_y = g.vec_ok = g.lds_bytes = g.cap2 = g.duo = 0;
-        g.xmerge = g.xm_off = g.xm_words = 0;
-        g.edge_words_l = g.edge_words_r = g.ext_words;
-        snprintf(plan->describe, sizeof plan->describe,
-                 "generic kernel (n=%d, D=%d): 1 lane/pixel, direct window sums", g.n, D);
-        return SM_OK;
-    }
-
-    g.pad_l = SM_PADT;
-    const bool bs = kernel == SM_KERNEL_BS;
-    int cus = 256, th_env = 0, ds_env = 0;
-    {
+    const PlanShape shape = {plan->width, plan->height, plan->num_shifts, plan->square_width, plan->border,
+                             plan->max_pairs, plan->opt};
+    int rc = SM_OK;
+    PlanDevice dev = {256, match_occupancy, &rc};
+    if (sm_plan_family(shape) != SM_KERNEL_GENERIC) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, plan->device) == hipSuccess && prop.multiProcessorCount > 0)
-            cus = prop.multiProcessorCount;
-        th_env = plan->opt.tile_h;              // sm_plan_create_ex: tuning / tests only
-        ds_env = plan->opt.shifts_per_lane;
+            dev.cus = prop.multiProcessorCount;
     }
-
-    // ---- geometry for `ds` shifts per lane, with the tile height chosen by a cost
-    // model.  Tall tiles amortise the n-1 warm-up rows, but the grid should fill the
-    // chip's resident slots in whole rounds: a tail round with a third of the CUs busy
-    // costs as much as a full one.  Model: a workgroup puts threads/256 waves on each
-    // SIMD; a SIMD issues one wave-instruction per 2 cycles, a single wave at most one
-    // per 4; rounds run back to back; the work of a lane-row is proportional to ds.
-    auto configure = [&](int ds, MatchGeom &o, int &rows_words_o, bool duo = false) -> double {
-        o = g;
-        o.ds = ds;
-        o.duo = duo ? 1 : 0;
-        o.nl = nl_for(ds, o.log2nl);
-        int rows_words;
-        if (bs) {
-            // one wave per workgroup: 64/nl words of 32 pixels, nl shift-lanes each
-            o.runs = 64 / o.nl;
-            o.threads = duo ? 128 : 64;     // duo: two waves, the upper and the lower half of the tile
-            o.tw = o.runs * 32;
-            o.plw = o.runs + 2;
-            o.prw = o.runs + (o.nl * ds + 31) / 32 + 4;
-            rows_words = o.plw + o.prw;
-        } else {
-            o.runs = o.nl == 1 ? 64 : (o.nl <= 8 ? 32 : 256 / o.nl);
-            o.threads = o.runs * o.nl;
-            o.tw = o.runs * SM_P;
-            o.plw = (SM_PADT + o.tw + o.half + 31) / 32 + 1;
-            o.prw = (SM_PADT + o.tw + o.half + o.nl * ds + 31) / 32 + 1;
-            rows_words = (o.plw + o.prw) * 3;     // plain + spread
-        }
-        rows_words_o = rows_words;
-        o.tiles_x = ceil_div(W, o.tw);
-        const bool fulld = o.nl * ds == D;
-        const void *kfn = bs ? sm_bs_kernel_ptr(o.n, ds, fulld, ghost, false, duo) : tiled_kernel_ptr(kernel, fulld, ghost);
-        const double wps = o.threads / 256.0;            // waves per SIMD per workgroup
-        // warm-up rows are cheaper than output rows (no arg-max, no output); the constant is
-        // the per-workgroup overhead (staging, lane set-up) in output-row units.  Refit on
-        // same-device tile-height sweeps (tools/tune_tile_h.py, C2 / C3 / C4 x 8).
-        // (duo: half the window rows + 1, and the exchange of the partial sums)
-        const double warm = duo ? 0.42 * (o.half + 1) + 2.3
-                          : bs ? 0.42 * (o.n - 1) + 1.8 : 0.4 * (o.n - 1) + 1.0;
-        // lane-row work relative to ds = 16: the per-row shared views and one more merge level
-
-        // duo: 2 * th rows per workgroup, and behind the staged rows the exchange block
-        // [2 halves of the shifts][ds / 2 * SB / 2 plane pairs][64 lanes] of 8 bytes
-        int sb = 0;
-        while ((1 << sb) <= o.n * o.n) sb++;
-        const int rows_per_wg = duo ? 2 : 1;
-        // lane merge through LDS (k_match_bs, g.xmerge): where at least 4 lanes share a word; per wave
-        // 4 x NPG blocks of 1 KB behind the staged rows, in a two-wave workgroup over the exchange slots
-        const int ab = ds == 16 ? 4 : ds == 8 ? 3 : 2;
-        const int npg = (sb + ab + 3) / 4;
-        // Taken where it pays: 16 shifts per lane and at least 8 lanes per word (C3: -4.3 % of the launch's
-        // VALU instructions, -3 % of its time; C5: -10 %).  With 4 lanes per word there are only two DPP levels
-        // to save and the batch's bursts of stores cost more than that (C4 x 8: +5 %); the 8-shifts-per-lane
-        // builds run 4- to 9-row tiles, whose last batch is mostly empty.  lane_merge = 2 forces it wherever
-        // it is possible (tests, measurements), 1 forbids it.  profiles/r04/ab_lane_merge.txt
-        const bool xm_possible = bs && o.log2nl >= 2 && o.nl <= 32;
-        o.xmerge = xm_possible && plan->opt.lane_merge != 1 &&
-                   (plan->opt.lane_merge == 2 || ((ds == 16 || ds == 4) && o.log2nl >= 3));
-        // lane-row work relative to ds = 16: the per-row shared views and the merge levels weigh more the fewer
-        // shifts a lane carries (fitted to same-device timings: profiles/r02/ds8_small_grids_sweep.txt, r04/ab_ds4.txt)
-        // (round 4, tools/ds_choice_check.py over 14 shapes: 8 shifts per lane was the best of the three ONCE and
-        // was chosen seven times -- its weight went from 0.55 to 0.65, the LDS-merged 4-shift build's from 0.36 to
-        // 0.33, and a 16-shift row whose lanes are merged through LDS counts 0.95)
-        const double work = ds == 16 ? (o.xmerge ? 0.95 : 1.0) : ds == 8 ? 0.5 * 1.30
-                          : o.xmerge ? 0.25 * 1.32 : 0.25 * (1.30 + 0.15 * o.log2nl);
-        const int mb_words = o.xmerge ? npg * 1024 : 0;
-        auto lds_words = [&](int th, int &xm_off) {
-            const int staged = ((rows_per_wg * th + o.n - 1) * rows_words + 3) & ~3;
-            if (!bs) { xm_off = 0; return (rows_per_wg * th + o.n - 1) * rows_words; }
-            if (duo) {
-                const int slot = ds * sb * 32;                    // words of one exchange slot
-                const int half = std::max(slot, mb_words);
-                xm_off = staged + half;
-                return staged + 2 * half;
-            }
-            xm_off = staged;
-            return staged + mb_words;
-        };
-        auto lds_of = [&](int th) { int off; return lds_words(th, off) * 4; };
-        int th = 0;
-        double best_cost = 0;
-        for (int c = 2; c <= 256; c++) {
-            if (c > H && c != 2) break;
-            const int cand = std::min(c, H);
-            if (lds_of(cand) > 64 * 1024) break;
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, o.threads, lds_of(cand)) != hipSuccess
-                || per_cu < 1)
-                per_cu = 1;
-            const long long tiles = (long long)o.tiles_x * ceil_div(H, rows_per_wg * cand) * plan->max_pairs;
-            const long long slots = (long long)cus * per_cu;
-            double cost = 0;
-            for (long long left = tiles; left > 0; left -= slots) {
-                const long long m = std::min(left, slots);
-                // the busiest SIMD of this round hosts j waves; measured: one wave alone
-                // retires an instruction every ~5.5 cycles (popcount kernels; ~4.3 for the
-                // bit-sliced kernel), two co-resident waves ~5.5 each, beyond that they
-                // share ~2.5 cycles/instr
-                const long long wg_per_cu = (m + cus - 1) / cus;
-                const int j = std::max(1, (int)std::ceil((double)wg_per_cu * wps - 1e-9));
-                const double cpi = bs ? (j <= 1 ? 4.3 : std::max(5.5, 2.5 * j)) : std::max(5.5, 2.5 * j);
-                cost += (cand + warm) * work * cpi;
-            }
-            if (th == 0 || cost < best_cost * 0.999) { th = cand; best_cost = cost; }
-        }
-        if (th == 0) th = 1;
-        if (th_env > 0) th = std::min(th_env, H);
-        while (lds_of(th) > 64 * 1024 && th > 1) th--;
-        o.tile_h = th;
-        o.tiles_y = ceil_div(H, rows_per_wg * th);
-        o.nsr = rows_per_wg * th + o.n - 1;
-        o.lds_bytes = lds_words(th, o.xm_off) * 4;
-        o.xm_words = mb_words;
-        // A grid that fits the chip in one round must also be SPREAD evenly: where the
-        // registers allow more resident workgroups than the round needs (7x7: 3 waves
-        // per SIMD, 2 needed) the dispatcher may stack 3 waves on some SIMDs and leave
-        // others with 1, and the launch then lasts as long as the crowded ones (measured
-        // at 8 x 1080p: 89 us spread evenly, 117 us not).  Two caps:
-        //  * per SIMD: a grid that fits at two waves per SIMD launches the kernel's
-        //    two-wave variant (k_match_bs<..., CAP2>), where one exists;
-        //  * per CU: an LDS request larger than the tile needs -- LDS per workgroup in
-        //    (160 KB / (cap + 1), 160 KB / cap] admits exactly `cap` workgroups per CU.
-        o.cap2 = 0;
-        if (bs) {
-            const long long tiles = (long long)o.tiles_x * o.tiles_y * plan->max_pairs;
-            const int cap = (int)((tiles + cus - 1) / cus);
-            const void *kcap = sm_bs_kernel_ptr(o.n, ds, fulld, ghost, true, duo);
-            const void *kuse = kfn;
-            if (kcap && cap <= 8 && !plan->opt.no_two_wave_cap) { o.cap2 = 1; kuse = kcap; }
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kuse, o.threads, o.lds_bytes) == hipSuccess
-                && cap >= 2 && cap < per_cu) {
-                const int lds_cu = 160 * 1024, granule = 1280;
-                int want = std::min(64 * 1024, lds_cu / cap / granule * granule);
-                int got = 0;
-                if (want > o.lds_bytes &&
-                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&got, kuse, o.threads, want) == hipSuccess &&
-                    got == cap)
-                    o.lds_bytes = want;
-            }
-        }
-        o.ext_words = (o.tiles_x - 1) * (o.tw / 32) + o.prw;
-        o.ext_rows = o.tiles_y * rows_per_wg * th + o.n - 1;
-        o.ext_image_words = (long long)o.ext_words * o.ext_rows;
-        o.vec_ok = (W % 4) == 0;
-        return best_cost;
-    };
-
-    // shifts per lane: 16 for the popcount kernels; for the bit-sliced kernel what is
-    // built for this window (16 where it exists: measured faster than 8, fewer shared
-    // views and merge levels), sm_plan_options.shifts_per_lane overrides for tuning
-    int ds = 16;
-    MatchGeom gsel;
-    int rws = 0;
-    // Two-wave workgroups with a shared warm-up (k_match_bs<..., DUO>): HALF + 1 warm-up rows
-    // per wave instead of N, for an exchange through LDS.  Measured on one device at the same
-    // tile height (tools/ab_duo.sh): C3 95.3 -> 92.1 us, C4 x 8 83.6 -> 80.5, C5 197.9 -> 185.9,
-    // C2 20.5 -> 19.4, 21 x 21 at 4K 88.5 -> 77.4, C1 9.9 -> 10.0: taken wherever the cost
-    // model says so (sm_plan_options.workgroup_waves overrides: tuning, tests).
-    int duo_env = -1;
-    if (plan->opt.workgroup_waves) duo_env = plan->opt.workgroup_waves == 2;
-    auto duo_built = [&](int d) {
-        int l2;
-        return sm_bs_kernel_ptr(g.n, d, nl_for(d, l2) * d == D, ghost, false, true) != nullptr;
-    };
-    // lower-cost geometry of the two workgroup shapes for `d` shifts per lane
-    auto configure_best = [&](int d, MatchGeom &o, int &r) -> double {
-        const bool can = bs && duo_built(d);
-        double c1 = 0, c2 = 0;
-        MatchGeom o2;
-        int r2 = 0;
-        if (!(can && duo_env == 1)) c1 = configure(d, o, r, false);
-        if (can && duo_env != 0) {
-            c2 = configure(d, o2, r2, true);
-            if (duo_env == 1 || c2 < c1) { o = o2; r = r2; return c2; }
-        }
-        return c1;
-    };
-    if (bs) {
-        ds = sm_bs_default_ds(g.n);
-        int l2;
-        const bool has8 = sm_bs_kernel_ptr(g.n, 8, true, ghost, false) && nl_for(8, l2) <= 32;
-        if ((ds_env == 4 || ds_env == 8 || ds_env == 16) && sm_bs_kernel_ptr(g.n, ds_env, true, ghost, false) &&
-            nl_for(ds_env, l2) <= 32) {
-            ds = ds_env;
-        } else {
-            // A grid that leaves most SIMDs with ONE wave (a single 1080p pair at 16 shifts per lane: 864
-            // workgroups) runs at the rate of a lone wave; with 8 -- or 4 -- shifts per lane the same job is
-            // more workgroups of less work each, on narrower tiles that can be taller for the same number of
-            // waves (less warm-up per output row).  The cost model decides, with 5 % in favour of the wider
-            // lane.  Measured: C2 29.6 (16) -> 19.1 (8) -> 16.5 us (4, lanes merged through LDS), C1 18.4 ->
-            // 9.8 -> 7.2 us; the full-chip configurations stay at 16 (profiles/r04/ab_ds4.txt).
-            // What the model cannot see -- the narrow lanes win by latency hiding on grids that leave the chip
-            // partly empty, not by instruction count -- is put in as a rule taken from tools/ds_choice_check.py
-            // (14 shapes, profiles/r04/ds_choice_*.txt): below 0.3 G pixel-shifts per launch, or for windows of
-            // 13 x 13 and more (their warm-up weighs less on narrow, tall tiles), all three are candidates; above
-            // it a window that has a 16-shift build takes it (the worst miss of this rule: 5 %).
-            const double pxshifts = (double)W * H * D * plan->max_pairs;
-            const bool small_or_tall = pxshifts <= 0.3e9 || g.n >= 13;
-            const bool has4 = plan->opt.no_four_shift_lanes == 0 && small_or_tall &&
-                              sm_bs_kernel_ptr(g.n, 4, true, ghost, false) && nl_for(4, l2) <= 32;
-            double cbest = 0;
-            int dbest = 0;
-            for (int d : {16, 8, 4}) {
-                if (d == 16 && ds != 16) continue;          // (windows whose 16-shift build does not exist)
-                if (d == 8 && (!has8 || (ds == 16 && !small_or_tall))) continue;
-                if (d == 4 && !has4) continue;
-                MatchGeom gd;
-                int rd = 0;
-                const double c = configure_best(d, gd, rd);
-                if (!dbest || c < 0.95 * cbest) { dbest = d; cbest = c; }
-            }
-            if (dbest) ds = dbest;
-        }
-    }
-    configure_best(ds, gsel, rws);
-    g = gsel;
-    g.edge_words_l = std::min(g.ext_words, (g.pad_l + W + g.half - 1) / 32 + 1);
-    g.edge_words_r = std::min(g.ext_words, (g.pad_l + W + g.half + D - 2) / 32 + 1);
-
-    snprintf(plan->describe, sizeof plan->describe,
-             "%s (n=%d, D=%d, %s): tile %dx%d px, %d threads "
-             "(%d runs x %d shift-lanes of %d), grid %dx%d, LDS %d B/wg%s%s, ext %dx%d words",
-             bs ? "bit-sliced kernel" : kernel == SM_KERNEL_A ? "tiled kernel A"
-                : kernel == SM_KERNEL_B ? "tiled kernel B" : "tiled kernel C",
-             g.n, D, ghost ? "ghost" : "toroidal",
-             g.tw, g.duo ? 2 * g.tile_h : g.tile_h, g.threads, g.runs, g.nl, g.ds, g.tiles_x, g.tiles_y, g.lds_bytes,
-             g.duo ? ", two-wave workgroups" : g.cap2 ? ", 2 waves/SIMD variant" : "",
-             g.xmerge ? ", lanes merged through LDS" : "",
-             g.ext_words, g.ext_rows);
-    return SM_OK;
+    plan->kernel = sm_plan_match(shape, dev, &plan->g, plan->describe, sizeof plan->describe);
+    const void *fn;
+    if (!rc && plan->kernel != SM_KERNEL_GENERIC)
+        rc = match_kernel_ptr(sm_match_kernel_key(plan->kernel, plan->g, plan->border == SM_GHOST), &fn);
+    return rc;
 }
 
 template <int MODE>
@@ -777,7 +536,7 @@ int sm_match_launch(const sm_plan *plan, const MatchLaunch &l, int pairs, i32 *d
     case SM_KERNEL_B: launch_tiled<SM_KERNEL_B>(plan, g, pairs, d_web, d_best, st); break;
     case SM_KERNEL_C: launch_tiled<SM_KERNEL_C>(plan, g, pairs, d_web, d_best, st); break;
     default: {
-        const dim3 grid(ceil_div(g.w, 256), g.h, pairs), block(256);
+        const dim3 grid(sm_ceil_div(g.w, 256), g.h, pairs), block(256);
         hipLaunchKernelGGL(k_match_wta_generic, grid, block, 0, st, plan->d_ext, d_web, d_best,
                            g, plan->border == SM_GHOST ? 1 : 0);
     }

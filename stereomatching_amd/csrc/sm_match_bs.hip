@@ -29,6 +29,8 @@ extern "C" int sm_debug_set_stamps(void *buf)
 // host side
 // ---------------------------------------------------------------------------
 
+// The launch side's mapping from a kernel key to a function.  The planner asks sm_bs_built (sm_plan_model.h), the
+// same table as a predicate; sm_match.hip checks that the two agree when a plan's kernel is resolved.
 // Built combinations.  16 shifts per lane up to 11 x 11 (the 16 x SB sum planes fit
 // two waves per SIMD); 8 per lane for the larger windows (9 planes per sum) and, for the
 // smaller ones, as the alternative for grids that would leave SIMDs with a single wave.
@@ -54,14 +56,6 @@ const void *sm_bs_kernel_ptr(int n, int ds, bool fulld, bool ghost, bool cap2, b
         }
     }
     return nullptr;
-}
-
-// shifts per lane the plan should use for this window (0: not built)
-int sm_bs_default_ds(int n)
-{
-    if (sm_bs_kernel_ptr(n, 16, true, false, false)) return 16;
-    if (sm_bs_kernel_ptr(n, 8, true, false, false)) return 8;
-    return 0;
 }
 
 // One launch of the plan's kernel that does nothing (web == nullptr): the runtime loads a

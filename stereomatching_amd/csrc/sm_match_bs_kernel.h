@@ -308,7 +308,7 @@ __device__ __forceinline__ u32 from_partner(u32 v)
 // kernel finds the SIMDs empty and the dispatcher stacks three waves on some of them
 // while others get one -- 117 us instead of 89; behind a launch of the same kernel
 // the waves inherit the previous, even placement.  A per-CU cap (the LDS request in
-// sm_match_configure) cannot prevent it, a per-SIMD one does.
+// match_spread, sm_plan_model.h) cannot prevent it, a per-SIMD one does.
 //
 // DUO: workgroups of TWO waves that share their warm-up.  The workgroup owns 2 * tile_h
 // rows; wave 1 starts at the middle row m and slides DOWN, wave 0 starts at row m - 1 and
