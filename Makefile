@@ -60,6 +60,8 @@ stereomatching_amd/obj/product/sm_rectify.o: $(CSRC)/sm_reproject.hip
 stereomatching_amd/obj/product/sm_filter.o: $(CSRC)/sm_wmedian.hip
 # (... and the half-resolution path beside it)
 stereomatching_amd/obj/product/sm_filter.o: $(CSRC)/sm_pyramid.hip
+# (... and the guided census re-search in the census mode's unit)
+stereomatching_amd/obj/product/sm_census.o: $(CSRC)/sm_census_near.hip
 $(DEVLIB): $(DEVOBJ)
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC $^ -o $@
 

@@ -508,6 +508,33 @@ int sm_census_refine(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d
                      int pairs, const int32_t *d_web, int16_t *d_sub, int32_t *d_costs, void *stream);
 /* adds: allocates the census workspace now; idempotent */
 int sm_plan_reserve_census(sm_plan *plan);
+/* ---- census cost mode, guided re-search: PARITY UNPINNED ---- *
+ * The second step of a coarse-to-fine search: sm_census_wta's arg-min, but only over the shifts within `radius` of a
+ * prior map -- the upsampled map of the half-resolution path, whose shifts are all even (sm_upsample_double).
+ *   d_prior: an int32 web map [pairs][H][W], 1 + shift, 0 = invalid; any int32 value is legal.  radius r in 1..4.
+ *   K(p) = { d : 0 <= d <= D - 1, |d - (prior(p) - 1)| <= r }; empty for prior(p) = 0 and for every prior so far
+ *     outside 1 - r .. D + r that no d qualifies.
+ *   K(p) empty: web = best = 0.  Otherwise best = min over K(p) of A_d(p), A_d sm_census_wta's window cost (all n x n
+ *     taps with p's own d: the priors of the neighbours play no part), web = 1 + the least d of K(p) reaching it.
+ *   So wherever |prior - sm_census_wta's web| <= r the two calls agree in web and best, and best is never smaller.
+ *   right reference: mirror(near(mirror(R), mirror(L), mirror(prior_right))): the cost of right pixel u at d is
+ *     popcount(C_R(u) XOR C_L(u - d)), toroidal u - d mod W, ghost C_L = 0 for u - d < 0.
+ *   sm_census_near_lr: the descriptors once, both searches, then sm_lr_check's rule; NULL and overlap rules of
+ *     sm_census_lr.  Subpixel: sm_census_refine takes the result as it takes any web map.
+ * Both border modes, windows, shifts, workspace (sm_plan_reserve_census, nothing added) and STREAM CAPTURE as for the
+ * calls above.  Refused before any device call: a NULL plan or required pointer, census_width, radius, pairs, the
+ * window and shift limits, and an output that overlaps an image, a prior or another output (no in-place operation). */
+/* adds: the left re-search -> d_web (and, d_best non-NULL, the window costs) */
+int sm_census_wta_near(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+                       int pairs, const int32_t *d_prior, int radius, int32_t *d_web, int32_t *d_best, void *stream);
+/* adds: the right-reference re-search around d_prior_right (a right-reference map), natural order */
+int sm_census_wta_near_right(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+                             int pairs, const int32_t *d_prior_right, int radius, int32_t *d_web_right,
+                             int32_t *d_best_right, void *stream);
+/* adds: both re-searches and the check: d_web = checked map; d_best / d_web_right / d_rejected may be NULL */
+int sm_census_near_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+                      int pairs, const int32_t *d_prior, const int32_t *d_prior_right, int radius, int max_diff,
+                      int32_t *d_web, int32_t *d_best, int32_t *d_web_right, int32_t *d_rejected, void *stream);
 
 /* ---- semi-global matching over the census data term: PARITY UNPINNED ------ *
  * New work (no reference counterpart).  The census window cost aggregated along 4 or 8 image lines

@@ -23,8 +23,9 @@ SOURCES = ["sm_match_bs_ds8.hip", "sm_match_bs.hip", "sm_match_bs_duo8.hip", "sm
            "sm_api.hip", "sm_edges.hip", "sm_run.hip", "sm_step3.hip", "sm_match.hip", "sm_cost.hip", "sm_cost_qs.hip", "sm_cost_pc.hip", "sm_cost_mfma.hip", "sm_cost_strip.hip", "sm_gather.hip", "sm_lr.hip",
            "sm_subpix.hip", "sm_census.hip", "sm_sgm.hip", "sm_filter.hip", "sm_interp.hip", "sm_rectify.hip"]
 # files a source includes beside HEADERS: the reprojection stage is built in the rectification's unit, the guided
-# weighted median and the half-resolution path in the post-filters'
-INCLUDED = {"sm_rectify.hip": [CSRC / "sm_reproject.hip"], "sm_filter.hip": [CSRC / "sm_wmedian.hip", CSRC / "sm_pyramid.hip"]}
+# weighted median and the half-resolution path in the post-filters', the guided census re-search in the census mode's
+INCLUDED = {"sm_rectify.hip": [CSRC / "sm_reproject.hip"], "sm_filter.hip": [CSRC / "sm_wmedian.hip", CSRC / "sm_pyramid.hip"],
+            "sm_census.hip": [CSRC / "sm_census_near.hip"]}
 HEADERS = [CSRC / "sm_internal.h", CSRC / "sm_match_bs_kernel.h", CSRC / "sm_bs_network.h", CSRC / "sm_bs_ops.h", CSRC / "sm_cost.h", CSRC / "sm_device.h", CSRC / "sm_geom.h", CSRC / "sm_plan_model.h", ROOT / "include" / "stereo_hip.h"]
 OBJDIR = PKG / "obj"
 HIPCC_FLAGS = [

@@ -168,6 +168,9 @@ _SIGNATURES = {
     "sm_census_lr": (_int, [_vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "sm_census_refine": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp]),
     "sm_plan_reserve_census": (_int, [_vp]),
+    "sm_census_wta_near": (_int, [_vp, _vp, _vp, _int, _int, _vp, _int, _vp, _vp, _vp]),
+    "sm_census_wta_near_right": (_int, [_vp, _vp, _vp, _int, _int, _vp, _int, _vp, _vp, _vp]),
+    "sm_census_near_lr": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "sm_sgm_wta": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     "sm_sgm_wta_right": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sm_sgm_lr": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),

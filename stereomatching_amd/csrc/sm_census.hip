@@ -659,3 +659,6 @@ extern "C" int sm_census_refine(sm_plan *plan, const uint8_t *d_gray_left, const
     if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_census_refine failed: %s", hipGetErrorString(e));
     return SM_OK;
 }
+
+// the guided re-search (sm_census_wta_near and its kin), built in this unit: DESIGN.md 21
+#include "sm_census_near.hip"

@@ -483,6 +483,52 @@ class StereoPlan:
                                    _ptr(costs), self._stream()))
         return out, costs
 
+    def _prior(self, prior, pairs, name):
+        prior = self._images(prior, torch.int32, name)
+        if prior.shape[0] != pairs:
+            raise ValueError(f"{name}: {prior.shape[0]} maps for {pairs} pairs")
+        return prior
+
+    def census_wta_near(self, left, right, prior, census=7, radius=1, want_best=True, web=None, best=None):
+        """Guided census re-search (sm_census_wta_near) -> (web, best): census_wta's arg-min over the shifts within
+        `radius` (1..4) of the int32 web map `prior` (1 + shift, 0 invalid) only -- the upsampled map of the
+        half-resolution path; web = best = 0 where the prior leaves no shift."""
+        left, right, pairs = self._census_pair(left, right)
+        prior = self._prior(prior, pairs, "prior")
+        web = self._out(web, pairs, "web")
+        best = self._out(best, pairs, "best") if want_best else None
+        check(lib.sm_census_wta_near(self._h, _ptr(left), _ptr(right), int(census), pairs, _ptr(prior), int(radius),
+                                     _ptr(web), _ptr(best), self._stream()))
+        return web, best
+
+    def census_wta_near_right(self, left, right, prior_right, census=7, radius=1, want_best=True, web_right=None,
+                              best_right=None):
+        """The right-reference re-search (sm_census_wta_near_right) -> (web_right, best_right), around a
+        right-reference prior map."""
+        left, right, pairs = self._census_pair(left, right)
+        prior_right = self._prior(prior_right, pairs, "prior_right")
+        web_right = self._out(web_right, pairs, "web_right")
+        best_right = self._out(best_right, pairs, "best_right") if want_best else None
+        check(lib.sm_census_wta_near_right(self._h, _ptr(left), _ptr(right), int(census), pairs, _ptr(prior_right),
+                                           int(radius), _ptr(web_right), _ptr(best_right), self._stream()))
+        return web_right, best_right
+
+    def census_near_lr(self, left, right, prior, prior_right, census=7, radius=1, max_diff=0, want_right=False,
+                       want_best=False, web=None, web_right=None, best=None) -> LRResult:
+        """Both re-searches and the check in one call (sm_census_near_lr) -> LRResult(web, rejected, web_right, best),
+        shaped like census_lr's."""
+        left, right, pairs = self._census_pair(left, right)
+        prior = self._prior(prior, pairs, "prior")
+        prior_right = self._prior(prior_right, pairs, "prior_right")
+        web = self._out(web, pairs, "web")
+        web_right = self._out(web_right, pairs, "web_right") if want_right else None
+        best = self._out(best, pairs, "best") if want_best else None
+        rejected = torch.empty(pairs, dtype=torch.int32, device=self._dev)
+        check(lib.sm_census_near_lr(self._h, _ptr(left), _ptr(right), int(census), pairs, _ptr(prior),
+                                    _ptr(prior_right), int(radius), int(max_diff), _ptr(web), _ptr(best),
+                                    _ptr(web_right), _ptr(rejected), self._stream()))
+        return LRResult(web, rejected, web_right, best)
+
     # ---- semi-global matching over the census data term ------------------------
     def reserve_sgm(self):
         """The SGM workspace (the census workspace, and the data-term and aggregate volumes of one pair), allocated now:
