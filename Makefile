@@ -52,7 +52,7 @@ $(DEVSTAMP): FORCE
 	@mkdir -p $(dir $@)
 	@if [ "$$(cat $@ 2>/dev/null)" != "$(HIPFLAGS_BARE)" ]; then rm -f $(dir $@)*.o; echo "$(HIPFLAGS_BARE)" > $@; fi
 FORCE:
-stereomatching_amd/obj/product/%.o: $(CSRC)/%.hip $(CSRC)/sm_internal.h $(CSRC)/sm_match_bs_kernel.h $(CSRC)/sm_bs_network.h $(CSRC)/sm_bs_ops.h $(CSRC)/sm_cost.h $(CSRC)/sm_device.h $(CSRC)/sm_geom.h $(CSRC)/sm_plan_model.h include/stereo_hip.h $(DEVSTAMP)
+stereomatching_amd/obj/product/%.o: $(CSRC)/%.hip $(CSRC)/sm_internal.h $(CSRC)/sm_entry.h $(CSRC)/sm_match_bs_kernel.h $(CSRC)/sm_bs_network.h $(CSRC)/sm_bs_ops.h $(CSRC)/sm_cost.h $(CSRC)/sm_device.h $(CSRC)/sm_geom.h $(CSRC)/sm_plan_model.h include/stereo_hip.h $(DEVSTAMP)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 # (the reprojection stage is built in the rectification's unit, which includes it)
 stereomatching_amd/obj/product/sm_rectify.o: $(CSRC)/sm_reproject.hip

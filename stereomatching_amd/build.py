@@ -26,7 +26,7 @@ SOURCES = ["sm_match_bs_ds8.hip", "sm_match_bs.hip", "sm_match_bs_duo8.hip", "sm
 # weighted median and the half-resolution path in the post-filters', the guided census re-search in the census mode's
 INCLUDED = {"sm_rectify.hip": [CSRC / "sm_reproject.hip"], "sm_filter.hip": [CSRC / "sm_wmedian.hip", CSRC / "sm_pyramid.hip"],
             "sm_census.hip": [CSRC / "sm_census_near.hip"]}
-HEADERS = [CSRC / "sm_internal.h", CSRC / "sm_match_bs_kernel.h", CSRC / "sm_bs_network.h", CSRC / "sm_bs_ops.h", CSRC / "sm_cost.h", CSRC / "sm_device.h", CSRC / "sm_geom.h", CSRC / "sm_plan_model.h", ROOT / "include" / "stereo_hip.h"]
+HEADERS = [CSRC / "sm_internal.h", CSRC / "sm_entry.h", CSRC / "sm_match_bs_kernel.h", CSRC / "sm_bs_network.h", CSRC / "sm_bs_ops.h", CSRC / "sm_cost.h", CSRC / "sm_device.h", CSRC / "sm_geom.h", CSRC / "sm_plan_model.h", ROOT / "include" / "stereo_hip.h"]
 OBJDIR = PKG / "obj"
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",

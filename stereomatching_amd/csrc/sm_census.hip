@@ -28,6 +28,7 @@
 //                       equiangular fit.
 
 #include "sm_device.h"
+#include "sm_entry.h"
 #include "sm_plan_model.h"
 
 typedef unsigned long long u64;
@@ -514,13 +515,6 @@ int sm_census_descriptors(sm_plan *plan, int cw, const uint8_t *left, const uint
     return transform_launch(plan, cw, cw == 7 ? 2 : 1, left, pairs, right, pairs, plan->d_census, side, st);
 }
 
-template <int NW>
-static const void *wta_ptr(bool ghost, bool mirror)
-{
-    return ghost ? (mirror ? (const void *)k_census_wta<NW, true, true> : (const void *)k_census_wta<NW, true, false>)
-                 : (mirror ? (const void *)k_census_wta<NW, false, true> : (const void *)k_census_wta<NW, false, false>);
-}
-
 // the arg-min over the plan's shifts from the workspace's descriptors, in launches of at most SMN_DCHUNK shifts
 static int wta_launch(const sm_plan *plan, int cw, bool mirror, int pairs, i32 *d_web, i32 *d_best, hipStream_t st)
 {
@@ -531,7 +525,8 @@ static int wta_launch(const sm_plan *plan, int cw, bool mirror, int pairs, i32 *
     g.hg = (g.half + 3) / 4;
     g.side = (long long)plan->max_pairs * g.w * g.h;
     g.vec_ok = g.w % 4 == 0 && (((uintptr_t)d_web | (uintptr_t)d_best) & 15) == 0;
-    const void *fn = nw == 2 ? wta_ptr<2>(plan->border == SM_GHOST, mirror) : wta_ptr<1>(plan->border == SM_GHOST, mirror);
+    const bool ghost = plan->border == SM_GHOST;
+    const void *fn = nw == 2 ? SM_PASS_KERNEL(k_census_wta, 2, ghost, mirror) : SM_PASS_KERNEL(k_census_wta, 1, ghost, mirror);
     for (int dlo = 0; dlo < g.D; dlo += SMN_DCHUNK) {
         g.dlo = dlo;
         g.dc = min(SMN_DCHUNK, g.D - dlo);
@@ -580,59 +575,39 @@ extern "C" int sm_census_transform(sm_plan *plan, const uint8_t *d_gray, int cen
     return transform_launch(plan, census_width, 2, d_gray, images, nullptr, 0, (u32 *)d_desc, 0, (hipStream_t)stream);
 }
 
+// the mode as the entry driver sees it (sm_entry.h)
+struct CensusMode : sm_mode {
+    static constexpr const sm_ws_set &ws = SM_WS_SET_CENSUS;
+    int cw;
+    explicit CensusMode(int census_width) : cw(census_width) {}
+    int args(const sm_call &c) const { return census_args(c.plan, cw, c.pairs, c.me); }
+    int prepare(const sm_call &c) const { return sm_census_descriptors(c.plan, cw, c.left, c.right, c.pairs, c.st); }
+    int pass(const sm_call &c, bool mirror, i32 *web, i32 *best, int16_t *) const
+    {
+        return wta_launch(c.plan, cw, mirror, c.pairs, web, best, c.st);
+    }
+};
+
 extern "C" int sm_census_wta(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
                              int pairs, int32_t *d_web, int32_t *d_best, void *stream)
 {
-    const char *me = "sm_census_wta";
-    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
-    if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
-    SM_TRY(census_args(plan, census_width, pairs, me));
-    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
-    if (d_best && overlap(d_web, d_best, map)) return sm_fail(SM_ERR_ARG, "%s: d_web and d_best overlap", me);
-    SM_TRY(sm_use_device(plan->device));
-    hipStream_t st = (hipStream_t)stream;
-    SM_TRY(sm_ws_need(plan, SM_WS_SET_CENSUS, st, me));
-    SM_TRY(sm_census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
-    return wta_launch(plan, census_width, false, pairs, d_web, d_best, st);
+    return sm_entry_one({"sm_census_wta", plan, d_gray_left, d_gray_right, pairs, (hipStream_t)stream},
+                        CensusMode(census_width), false, d_web, d_best, nullptr);
 }
 
 extern "C" int sm_census_wta_right(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right,
                                    int census_width, int pairs, int32_t *d_web_right, int32_t *d_best_right, void *stream)
 {
-    const char *me = "sm_census_wta_right";
-    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
-    if (!d_web_right) return sm_fail(SM_ERR_ARG, "%s: d_web_right is NULL", me);
-    SM_TRY(census_args(plan, census_width, pairs, me));
-    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
-    if (d_best_right && overlap(d_web_right, d_best_right, map))
-        return sm_fail(SM_ERR_ARG, "%s: d_web_right and d_best_right overlap", me);
-    SM_TRY(sm_use_device(plan->device));
-    hipStream_t st = (hipStream_t)stream;
-    SM_TRY(sm_ws_need(plan, SM_WS_SET_CENSUS, st, me));
-    SM_TRY(sm_census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
-    return wta_launch(plan, census_width, true, pairs, d_web_right, d_best_right, st);
+    return sm_entry_one({"sm_census_wta_right", plan, d_gray_left, d_gray_right, pairs, (hipStream_t)stream},
+                        CensusMode(census_width), true, d_web_right, d_best_right, nullptr);
 }
 
 extern "C" int sm_census_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
                             int pairs, int max_diff, int32_t *d_web, int32_t *d_best, int32_t *d_web_right,
                             int32_t *d_rejected, void *stream)
 {
-    const char *me = "sm_census_lr";
-    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
-    if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
-    if (max_diff < 0) return sm_fail(SM_ERR_ARG, "%s: max_diff %d is negative", me, max_diff);
-    SM_TRY(census_args(plan, census_width, pairs, me));
-    SM_TRY(sm_check_lr_maps(plan, pairs, d_web, d_best, d_web_right, nullptr, d_rejected, me));
-    SM_TRY(sm_use_device(plan->device));
-    hipStream_t st = (hipStream_t)stream;
-    SM_TRY(sm_ws_need(plan, SM_WS_SET_CENSUS, st, me));
-    // the descriptors once for both directions; the right-reference map in natural order (the caller's, or the
-    // plan's mirrored-order map used as scratch), then the check, which gathers from it
-    i32 *right = d_web_right ? d_web_right : plan->d_web_lr;
-    SM_TRY(sm_census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
-    SM_TRY(wta_launch(plan, census_width, false, pairs, d_web, d_best, st));
-    SM_TRY(wta_launch(plan, census_width, true, pairs, right, nullptr, st));
-    return sm_lr_check_natural(plan, d_web, right, d_web, d_rejected, max_diff, pairs, st);
+    return sm_entry_lr({"sm_census_lr", plan, d_gray_left, d_gray_right, pairs, (hipStream_t)stream},
+                       CensusMode(census_width), max_diff, d_web, d_best, d_web_right, d_rejected, nullptr);
 }
 
 extern "C" int sm_census_refine(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right,

@@ -229,13 +229,6 @@ __global__ __launch_bounds__(256) void k_census_near(const u32 *__restrict__ des
     }
 }
 
-template <int NW>
-static const void *near_ptr(bool ghost, bool mirror)
-{
-    return ghost ? (mirror ? (const void *)k_census_near<NW, true, true> : (const void *)k_census_near<NW, true, false>)
-                 : (mirror ? (const void *)k_census_near<NW, false, true> : (const void *)k_census_near<NW, false, false>);
-}
-
 // the re-search from the workspace's descriptors
 static int near_launch(const sm_plan *plan, int cw, bool mirror, int pairs, const i32 *d_prior, int radius, i32 *d_web,
                        i32 *d_best, hipStream_t st)
@@ -253,7 +246,8 @@ static int near_launch(const sm_plan *plan, int cw, bool mirror, int pairs, cons
     const size_t lds = 4 * 16 + 2 * ((size_t)((total + 1) & ~1) + (size_t)g.sh * 64);
     if (total > 256 * SMN_NQ || lds > 64 * 1024)
         return sm_fail(SM_ERR_HIP, "census near: internal tiling error (%d positions, %zu bytes of LDS)", total, lds);
-    const void *fn = cw == 7 ? near_ptr<2>(plan->border == SM_GHOST, mirror) : near_ptr<1>(plan->border == SM_GHOST, mirror);
+    const bool ghost = plan->border == SM_GHOST;
+    const void *fn = cw == 7 ? SM_PASS_KERNEL(k_census_near, 2, ghost, mirror) : SM_PASS_KERNEL(k_census_near, 1, ghost, mirror);
     void *args[] = {(void *)&plan->d_census, (void *)&d_prior, (void *)&d_web, (void *)&d_best, (void *)&g};
     const hipError_t e = hipLaunchKernel(fn, dim3(g.tiles_x, g.tiles_y, pairs), dim3(256), args, lds, st);
     if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_census_near failed: %s", hipGetErrorString(e));
@@ -285,45 +279,45 @@ static int near_inputs_apart(const sm_plan *plan, int pairs, const uint8_t *left
     return SM_OK;
 }
 
+// the mode as the entry driver sees it (sm_entry.h): the census mode with a prior map for each direction the call runs
+struct CensusNearMode : CensusMode {
+    int radius;
+    const i32 *prior, *prior_right;
+    CensusNearMode(int census_width, int radius_, const i32 *p, const i32 *p_right)
+        : CensusMode(census_width), radius(radius_), prior(p), prior_right(p_right) {}
+    int inputs(const sm_call &c, bool left, bool right) const
+    {
+        if (left && right)
+            return prior && prior_right ? SM_OK : sm_fail(SM_ERR_ARG, "%s: prior map pointer is NULL", c.me);
+        return (right ? prior_right : prior) ? SM_OK
+               : sm_fail(SM_ERR_ARG, "%s: %s is NULL", c.me, right ? "d_prior_right" : "d_prior");
+    }
+    int args(const sm_call &c) const { return near_args(c.plan, cw, c.pairs, radius, c.me); }
+    int apart(const sm_call &c, const i32 *const *outs, int n_outs, const i32 *rejected) const
+    {
+        return near_inputs_apart(c.plan, c.pairs, c.left, c.right, prior, prior_right, outs, n_outs, rejected, c.me);
+    }
+    int pass(const sm_call &c, bool mirror, i32 *web, i32 *best, int16_t *) const
+    {
+        return near_launch(c.plan, cw, mirror, c.pairs, mirror ? prior_right : prior, radius, web, best, c.st);
+    }
+};
+
 extern "C" int sm_census_wta_near(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right,
                                   int census_width, int pairs, const int32_t *d_prior, int radius, int32_t *d_web,
                                   int32_t *d_best, void *stream)
 {
-    const char *me = "sm_census_wta_near";
-    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
-    if (!d_prior) return sm_fail(SM_ERR_ARG, "%s: d_prior is NULL", me);
-    if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
-    SM_TRY(near_args(plan, census_width, pairs, radius, me));
-    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
-    if (d_best && overlap(d_web, d_best, map)) return sm_fail(SM_ERR_ARG, "%s: d_web and d_best overlap", me);
-    const i32 *outs[] = {d_web, d_best};
-    SM_TRY(near_inputs_apart(plan, pairs, d_gray_left, d_gray_right, d_prior, nullptr, outs, 2, nullptr, me));
-    SM_TRY(sm_use_device(plan->device));
-    hipStream_t st = (hipStream_t)stream;
-    SM_TRY(sm_ws_need(plan, SM_WS_SET_CENSUS, st, me));
-    SM_TRY(sm_census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
-    return near_launch(plan, census_width, false, pairs, d_prior, radius, d_web, d_best, st);
+    return sm_entry_one({"sm_census_wta_near", plan, d_gray_left, d_gray_right, pairs, (hipStream_t)stream},
+                        CensusNearMode(census_width, radius, d_prior, nullptr), false, d_web, d_best, nullptr);
 }
 
 extern "C" int sm_census_wta_near_right(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right,
                                         int census_width, int pairs, const int32_t *d_prior_right, int radius,
                                         int32_t *d_web_right, int32_t *d_best_right, void *stream)
 {
-    const char *me = "sm_census_wta_near_right";
-    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
-    if (!d_prior_right) return sm_fail(SM_ERR_ARG, "%s: d_prior_right is NULL", me);
-    if (!d_web_right) return sm_fail(SM_ERR_ARG, "%s: d_web_right is NULL", me);
-    SM_TRY(near_args(plan, census_width, pairs, radius, me));
-    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
-    if (d_best_right && overlap(d_web_right, d_best_right, map))
-        return sm_fail(SM_ERR_ARG, "%s: d_web_right and d_best_right overlap", me);
-    const i32 *outs[] = {d_web_right, d_best_right};
-    SM_TRY(near_inputs_apart(plan, pairs, d_gray_left, d_gray_right, d_prior_right, nullptr, outs, 2, nullptr, me));
-    SM_TRY(sm_use_device(plan->device));
-    hipStream_t st = (hipStream_t)stream;
-    SM_TRY(sm_ws_need(plan, SM_WS_SET_CENSUS, st, me));
-    SM_TRY(sm_census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
-    return near_launch(plan, census_width, true, pairs, d_prior_right, radius, d_web_right, d_best_right, st);
+    return sm_entry_one({"sm_census_wta_near_right", plan, d_gray_left, d_gray_right, pairs, (hipStream_t)stream},
+                        CensusNearMode(census_width, radius, nullptr, d_prior_right), true, d_web_right, d_best_right,
+                        nullptr);
 }
 
 extern "C" int sm_census_near_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right,
@@ -331,23 +325,7 @@ extern "C" int sm_census_near_lr(sm_plan *plan, const uint8_t *d_gray_left, cons
                                  int radius, int max_diff, int32_t *d_web, int32_t *d_best, int32_t *d_web_right,
                                  int32_t *d_rejected, void *stream)
 {
-    const char *me = "sm_census_near_lr";
-    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
-    if (!d_prior || !d_prior_right) return sm_fail(SM_ERR_ARG, "%s: prior map pointer is NULL", me);
-    if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
-    if (max_diff < 0) return sm_fail(SM_ERR_ARG, "%s: max_diff %d is negative", me, max_diff);
-    SM_TRY(near_args(plan, census_width, pairs, radius, me));
-    SM_TRY(sm_check_lr_maps(plan, pairs, d_web, d_best, d_web_right, nullptr, d_rejected, me));
-    const i32 *outs[] = {d_web, d_best, d_web_right};
-    SM_TRY(near_inputs_apart(plan, pairs, d_gray_left, d_gray_right, d_prior, d_prior_right, outs, 3, d_rejected, me));
-    SM_TRY(sm_use_device(plan->device));
-    hipStream_t st = (hipStream_t)stream;
-    SM_TRY(sm_ws_need(plan, SM_WS_SET_CENSUS, st, me));
-    // as sm_census_lr: the descriptors once, the right-reference map in natural order (the caller's, or the plan's
-    // mirrored-order map used as scratch), then the check
-    i32 *right = d_web_right ? d_web_right : plan->d_web_lr;
-    SM_TRY(sm_census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
-    SM_TRY(near_launch(plan, census_width, false, pairs, d_prior, radius, d_web, d_best, st));
-    SM_TRY(near_launch(plan, census_width, true, pairs, d_prior_right, radius, right, nullptr, st));
-    return sm_lr_check_natural(plan, d_web, right, d_web, d_rejected, max_diff, pairs, st);
+    return sm_entry_lr({"sm_census_near_lr", plan, d_gray_left, d_gray_right, pairs, (hipStream_t)stream},
+                       CensusNearMode(census_width, radius, d_prior, d_prior_right), max_diff, d_web, d_best,
+                       d_web_right, d_rejected, nullptr);
 }

@@ -199,14 +199,22 @@ void sm_lanes_release(sm_plan *plan);
 void sm_timing_free(sm_plan *plan);               // the timing events (sm_plan_time_kernels(plan, 0), sm_plan_destroy)
 
 // sm_lr.hip, for the other stages: the per-pair counts zeroed by k_lr_zero_counts (a kernel: a captured memset of them
-// replayed wrongly), and k_lr_check on a right-reference map in natural order (the rejection counts zeroed first)
+// replayed wrongly); k_lr_check on a right-reference map in natural or mirrored order (the rejection counts zeroed
+// first; mirrored: right_out, if not NULL, gets the map in natural order); k_lr_unmirror, which turns the maps of a
+// mirrored-order right-reference pass round in place
 int sm_lr_zero_counts(i32 *counts, int pairs, hipStream_t st);
-int sm_lr_check_natural(const sm_plan *plan, const i32 *web, const i32 *right, i32 *out, i32 *rejected, int max_diff,
-                        int pairs, hipStream_t st);
+int sm_lr_check_launch(const sm_plan *plan, bool mirrored, const i32 *web, const i32 *right, i32 *out, i32 *right_out,
+                       i32 *rejected, int max_diff, int pairs, hipStream_t st);
+int sm_lr_unmirror(const sm_plan *plan, int pairs, i32 *d_web_right, i32 *d_best_right, hipStream_t st);
 // sm_census.hip, for SGM: both images of `pairs` pairs into the census workspace (4-byte descriptors for c <= 5, 8 for 7)
 int sm_census_descriptors(sm_plan *plan, int cw, const uint8_t *left, const uint8_t *right, int pairs, hipStream_t st);
 // sm_filter.hip, for sm_sgm_lr: k_sgm_sub_mask, sub = 0 where web = 0, over n elements
 int sm_sub_mask_launch(const i32 *web, int16_t *sub, long long n, hipStream_t st);
+
+// the instantiation K<NW, GHOST, MIRROR> of a cost mode's pass kernel for a plan's border and a pass's direction
+#define SM_PASS_KERNEL(K, NW, ghost, mirror)                                                                  \
+    ((ghost) ? ((mirror) ? (const void *)K<NW, true, true> : (const void *)K<NW, true, false>)                \
+             : ((mirror) ? (const void *)K<NW, false, true> : (const void *)K<NW, false, false>))
 
 // sm_match_bs.hip (bit-sliced kernel; nullptr if not built for this window: sm_bs_built of sm_plan_model.h says which are)
 const void *sm_bs_kernel_ptr(int n, int ds, bool fulld, bool ghost, bool cap2, bool duo = false);

@@ -16,6 +16,7 @@
 // then the same k_lr_check.
 
 #include "sm_device.h"
+#include "sm_entry.h"
 
 #include <algorithm>
 
@@ -232,8 +233,8 @@ int sm_lr_zero_counts(i32 *counts, int pairs, hipStream_t st)
     return SM_OK;
 }
 
-static int lr_check_launch(const sm_plan *plan, bool mirrored, const i32 *web, const i32 *right, i32 *out,
-                           i32 *right_out, i32 *rejected, int max_diff, int pairs, hipStream_t st)
+int sm_lr_check_launch(const sm_plan *plan, bool mirrored, const i32 *web, const i32 *right, i32 *out, i32 *right_out,
+                       i32 *rejected, int max_diff, int pairs, hipStream_t st)
 {
     const int W = plan->width;
     const unsigned npx = (unsigned)W * plan->height;
@@ -252,7 +253,7 @@ static int lr_check_launch(const sm_plan *plan, bool mirrored, const i32 *web, c
 }
 
 // a right-reference launch wrote both maps in mirrored order: every row is turned round in place
-static int lr_unmirror(const sm_plan *plan, int pairs, i32 *d_web_right, i32 *d_best_right, hipStream_t st)
+int sm_lr_unmirror(const sm_plan *plan, int pairs, i32 *d_web_right, i32 *d_best_right, hipStream_t st)
 {
     const int W = plan->width;
     const unsigned half_w = (unsigned)(W + 1) / 2, half_px = half_w * plan->height;
@@ -279,7 +280,7 @@ extern "C" int sm_match_wta_right(sm_plan *plan, int pairs, int32_t *d_web_right
     SM_TRY(lr_mirror(plan, pairs, st));
     // the maps come out in mirrored order, and are turned round in place
     SM_TRY(lr_match(plan, plan->d_ext_lr, pairs, d_web_right, d_best_right, st));
-    return lr_unmirror(plan, pairs, d_web_right, d_best_right, st);
+    return sm_lr_unmirror(plan, pairs, d_web_right, d_best_right, st);
 }
 
 extern "C" int sm_lr_check(sm_plan *plan, const int32_t *d_web, const int32_t *d_web_right, int max_diff,
@@ -299,8 +300,8 @@ extern "C" int sm_lr_check(sm_plan *plan, const int32_t *d_web, const int32_t *d
                        overlap(d_rejected, d_web, counts, map)))
         return sm_fail(SM_ERR_ARG, "%s: d_rejected overlaps a map", me);
     SM_TRY(sm_use_device(plan->device));
-    return lr_check_launch(plan, false, d_web, d_web_right, d_web_out, nullptr, d_rejected, max_diff, pairs,
-                           (hipStream_t)stream);
+    return sm_lr_check_launch(plan, false, d_web, d_web_right, d_web_out, nullptr, d_rejected, max_diff, pairs,
+                              (hipStream_t)stream);
 }
 
 extern "C" int sm_run_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, double threshold,
@@ -326,7 +327,7 @@ extern "C" int sm_run_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_
     SM_TRY(lr_match(plan, plan->d_ext, pairs, d_web, d_best, st));
     SM_TRY(lr_mirror(plan, pairs, st));
     SM_TRY(lr_match(plan, plan->d_ext_lr, pairs, plan->d_web_lr, nullptr, st));
-    return lr_check_launch(plan, true, d_web, plan->d_web_lr, d_web, d_web_right, d_rejected, max_diff, pairs, st);
+    return sm_lr_check_launch(plan, true, d_web, plan->d_web_lr, d_web, d_web_right, d_rejected, max_diff, pairs, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -367,50 +368,34 @@ static int cost_lr_mirror(sm_plan *plan, const uint8_t *left, const uint8_t *rig
     return SM_OK;
 }
 
+// the mode as the entry driver sees it (sm_entry.h): nothing shared between the directions; the right-reference pass
+// is the plan's cost launch over the mirrored images, which leaves its maps in mirrored order
+struct CostMode : sm_mode {
+    static constexpr const sm_ws_set &ws = SM_WS_SET_COST_LR;
+    static constexpr bool right_mirrored = true;
+    int cost;
+    explicit CostMode(int cost_) : cost(cost_) {}
+    // (the modes differ here: sm_check_reach runs in cost_lr_args and again inside every sm_cost_wta of a pass)
+    int args(const sm_call &c) const { return cost_lr_args(c.plan, cost, c.pairs, c.me); }
+    int pass(const sm_call &c, bool mirror, i32 *web, i32 *best, int16_t *) const
+    {
+        const u8 *l = c.left, *r = c.right;
+        if (mirror) SM_TRY(cost_lr_mirror(c.plan, c.left, c.right, c.pairs, c.st, &l, &r));
+        return sm_cost_wta(c.plan, l, r, cost, c.pairs, web, best, c.st);
+    }
+};
+
 extern "C" int sm_cost_wta_right(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int cost,
                                  int pairs, int32_t *d_web_right, int32_t *d_best_right, void *stream)
 {
-    const char *me = "sm_cost_wta_right";
-    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
-    if (!d_web_right) return sm_fail(SM_ERR_ARG, "%s: d_web_right is NULL", me);
-    SM_TRY(cost_lr_args(plan, cost, pairs, me));
-    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
-    if (d_best_right && overlap(d_web_right, d_best_right, map))
-        return sm_fail(SM_ERR_ARG, "%s: d_web_right and d_best_right overlap", me);
-    SM_TRY(sm_use_device(plan->device));
-    hipStream_t st = (hipStream_t)stream;
-    SM_TRY(sm_ws_need(plan, SM_WS_SET_COST_LR, st, me));
-    const u8 *ml, *mr;
-    SM_TRY(cost_lr_mirror(plan, d_gray_left, d_gray_right, pairs, st, &ml, &mr));
-    // the plan's cost launch over the mirrored images writes the maps in mirrored order; they are turned round in place
-    SM_TRY(sm_cost_wta(plan, ml, mr, cost, pairs, d_web_right, d_best_right, stream));
-    return lr_unmirror(plan, pairs, d_web_right, d_best_right, st);
+    return sm_entry_one({"sm_cost_wta_right", plan, d_gray_left, d_gray_right, pairs, (hipStream_t)stream},
+                        CostMode(cost), true, d_web_right, d_best_right, nullptr);
 }
 
 extern "C" int sm_cost_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int cost, int pairs,
                           int max_diff, int32_t *d_web, int32_t *d_best, int32_t *d_web_right, int32_t *d_rejected,
                           void *stream)
 {
-    const char *me = "sm_cost_lr";
-    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
-    if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
-    if (max_diff < 0) return sm_fail(SM_ERR_ARG, "%s: max_diff %d is negative", me, max_diff);
-    SM_TRY(cost_lr_args(plan, cost, pairs, me));
-    SM_TRY(sm_check_lr_maps(plan, pairs, d_web, d_best, d_web_right, nullptr, d_rejected, me));
-    SM_TRY(sm_use_device(plan->device));
-    hipStream_t st = (hipStream_t)stream;
-    SM_TRY(sm_ws_need(plan, SM_WS_SET_COST_LR, st, me));
-    // the left cost launch (sm_cost_wta's maps exactly), the mirrored images, the right launch into the mirrored-order
-    // map, and the check, which gathers from that map
-    SM_TRY(sm_cost_wta(plan, d_gray_left, d_gray_right, cost, pairs, d_web, d_best, stream));
-    const u8 *ml, *mr;
-    SM_TRY(cost_lr_mirror(plan, d_gray_left, d_gray_right, pairs, st, &ml, &mr));
-    SM_TRY(sm_cost_wta(plan, ml, mr, cost, pairs, plan->d_web_lr, nullptr, stream));
-    return lr_check_launch(plan, true, d_web, plan->d_web_lr, d_web, d_web_right, d_rejected, max_diff, pairs, st);
-}
-
-int sm_lr_check_natural(const sm_plan *plan, const i32 *web, const i32 *right, i32 *out, i32 *rejected, int max_diff,
-                        int pairs, hipStream_t st)
-{
-    return lr_check_launch(plan, false, web, right, out, nullptr, rejected, max_diff, pairs, st);
+    return sm_entry_lr({"sm_cost_lr", plan, d_gray_left, d_gray_right, pairs, (hipStream_t)stream}, CostMode(cost),
+                       max_diff, d_web, d_best, d_web_right, d_rejected, nullptr);
 }

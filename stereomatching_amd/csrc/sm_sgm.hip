@@ -28,6 +28,7 @@
 
 
 #include "sm_device.h"
+#include "sm_entry.h"
 
 typedef unsigned long long u64;
 typedef unsigned short u16;
@@ -360,10 +361,7 @@ static int sgm_cost_launch(const sm_plan *plan, int cw, bool mirror, int pair, h
     u16 *hs = g.half ? (u16 *)((char *)plan->d_sgm + (size_t)2 * g.w * g.h * g.Dp) : A;
     const bool ghost = plan->border == SM_GHOST;
     const void *fn;
-#define SGM_H(NW) (ghost ? (mirror ? (const void *)k_sgm_cost_h<NW, true, true> : (const void *)k_sgm_cost_h<NW, true, false>) \
-                         : (mirror ? (const void *)k_sgm_cost_h<NW, false, true> : (const void *)k_sgm_cost_h<NW, false, false>))
-    fn = cw == 7 ? SGM_H(2) : SGM_H(1);
-#undef SGM_H
+    fn = cw == 7 ? SM_PASS_KERNEL(k_sgm_cost_h, 2, ghost, mirror) : SM_PASS_KERNEL(k_sgm_cost_h, 1, ghost, mirror);
     {
         void *args[] = {(void *)&plan->d_census, (void *)&hs, (void *)&g};
         const hipError_t e = hipLaunchKernel(fn, dim3((g.w + SGC_XR - 1) / SGC_XR, (g.h + 3) / 4, g.Dp / 64),
@@ -425,63 +423,40 @@ static int sgm_pass(const sm_plan *plan, int cw, int p1, int p2, int paths, bool
     return SM_OK;
 }
 
+// the mode as the entry driver sees it (sm_entry.h)
+struct SgmMode : sm_mode {
+    static constexpr const sm_ws_set &ws = SM_WS_SET_SGM;
+    static constexpr bool overlap_names_maps = false;
+    int cw, p1, p2, paths;
+    SgmMode(int census_width, int p1_, int p2_, int paths_) : cw(census_width), p1(p1_), p2(p2_), paths(paths_) {}
+    int args(const sm_call &c) const { return sgm_args(c.plan, cw, p1, p2, paths, c.pairs, c.me); }
+    int prepare(const sm_call &c) const { return sm_census_descriptors(c.plan, cw, c.left, c.right, c.pairs, c.st); }
+    int pass(const sm_call &c, bool mirror, i32 *web, i32 *best, int16_t *sub) const
+    {
+        return sgm_pass(c.plan, cw, p1, p2, paths, mirror, c.pairs, web, best, sub, c.st);
+    }
+};
+
 extern "C" int sm_sgm_wta(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
                           int p1, int p2, int paths, int pairs, int32_t *d_web, int32_t *d_best, int16_t *d_sub,
                           void *stream)
 {
-    const char *me = "sm_sgm_wta";
-    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
-    if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
-    SM_TRY(sgm_args(plan, census_width, p1, p2, paths, pairs, me));
-    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
-    if ((d_best && overlap(d_web, d_best, map)) || (d_sub && overlap(d_sub, d_web, map / 2, map)) ||
-        (d_sub && d_best && overlap(d_sub, d_best, map / 2, map)))
-        return sm_fail(SM_ERR_ARG, "%s: result maps overlap", me);
-    SM_TRY(sm_use_device(plan->device));
-    hipStream_t st = (hipStream_t)stream;
-    SM_TRY(sm_ws_need(plan, SM_WS_SET_SGM, st, me));
-    SM_TRY(sm_census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
-    return sgm_pass(plan, census_width, p1, p2, paths, false, pairs, d_web, d_best, d_sub, st);
+    return sm_entry_one({"sm_sgm_wta", plan, d_gray_left, d_gray_right, pairs, (hipStream_t)stream},
+                        SgmMode(census_width, p1, p2, paths), false, d_web, d_best, d_sub);
 }
 
 extern "C" int sm_sgm_wta_right(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right,
                                 int census_width, int p1, int p2, int paths, int pairs, int32_t *d_web_right,
                                 int32_t *d_best_right, void *stream)
 {
-    const char *me = "sm_sgm_wta_right";
-    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
-    if (!d_web_right) return sm_fail(SM_ERR_ARG, "%s: d_web_right is NULL", me);
-    SM_TRY(sgm_args(plan, census_width, p1, p2, paths, pairs, me));
-    const size_t map = (size_t)pairs * plan->width * plan->height * sizeof(i32);
-    if (d_best_right && overlap(d_web_right, d_best_right, map))
-        return sm_fail(SM_ERR_ARG, "%s: result maps overlap", me);
-    SM_TRY(sm_use_device(plan->device));
-    hipStream_t st = (hipStream_t)stream;
-    SM_TRY(sm_ws_need(plan, SM_WS_SET_SGM, st, me));
-    SM_TRY(sm_census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
-    return sgm_pass(plan, census_width, p1, p2, paths, true, pairs, d_web_right, d_best_right, nullptr, st);
+    return sm_entry_one({"sm_sgm_wta_right", plan, d_gray_left, d_gray_right, pairs, (hipStream_t)stream},
+                        SgmMode(census_width, p1, p2, paths), true, d_web_right, d_best_right, nullptr);
 }
 
 extern "C" int sm_sgm_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
                          int p1, int p2, int paths, int pairs, int max_diff, int32_t *d_web, int32_t *d_best,
                          int32_t *d_web_right, int32_t *d_rejected, int16_t *d_sub, void *stream)
 {
-    const char *me = "sm_sgm_lr";
-    if (!d_gray_left || !d_gray_right) return sm_fail(SM_ERR_ARG, "%s: input image pointer is NULL", me);
-    if (!d_web) return sm_fail(SM_ERR_ARG, "%s: d_web is NULL", me);
-    if (max_diff < 0) return sm_fail(SM_ERR_ARG, "%s: max_diff %d is negative", me, max_diff);
-    SM_TRY(sgm_args(plan, census_width, p1, p2, paths, pairs, me));
-    SM_TRY(sm_check_lr_maps(plan, pairs, d_web, d_best, d_web_right, d_sub, d_rejected, me));
-    SM_TRY(sm_use_device(plan->device));
-    hipStream_t st = (hipStream_t)stream;
-    SM_TRY(sm_ws_need(plan, SM_WS_SET_SGM, st, me));
-    // the descriptors once for both directions; the right-reference map in natural order (the caller's, or the
-    // plan's mirrored-order map used as scratch), then the check, which gathers from it
-    i32 *right = d_web_right ? d_web_right : plan->d_web_lr;
-    SM_TRY(sm_census_descriptors(plan, census_width, d_gray_left, d_gray_right, pairs, st));
-    SM_TRY(sgm_pass(plan, census_width, p1, p2, paths, false, pairs, d_web, d_best, d_sub, st));
-    SM_TRY(sgm_pass(plan, census_width, p1, p2, paths, true, pairs, right, nullptr, nullptr, st));
-    SM_TRY(sm_lr_check_natural(plan, d_web, right, d_web, d_rejected, max_diff, pairs, st));
-    if (!d_sub) return SM_OK;
-    return sm_sub_mask_launch(d_web, d_sub, (long long)pairs * plan->width * plan->height, st);
+    return sm_entry_lr({"sm_sgm_lr", plan, d_gray_left, d_gray_right, pairs, (hipStream_t)stream},
+                       SgmMode(census_width, p1, p2, paths), max_diff, d_web, d_best, d_web_right, d_rejected, d_sub);
 }

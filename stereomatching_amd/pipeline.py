@@ -344,6 +344,48 @@ class StereoPlan:
                             _ptr(best), _ptr(web_right), _ptr(rejected), self._stream()))
         return LRResult(web, rejected, web_right, best)
 
+    # ---- the cost modes' left, right and checked calls -------------------------
+    def _pair(self, left, right):
+        left = self._images(left, torch.uint8, "left")
+        right = self._images(right, torch.uint8, "right")
+        if right.shape[0] != left.shape[0]:
+            raise ValueError(f"right: {right.shape[0]} images for {left.shape[0]} pairs")
+        return left, right, left.shape[0]
+
+    def _prior(self, prior, pairs, name):
+        prior = self._images(prior, torch.int32, name)
+        if prior.shape[0] != pairs:
+            raise ValueError(f"{name}: {prior.shape[0]} maps for {pairs} pairs")
+        return prior
+
+    def _match_one(self, fn, mode, left, right, side, want_best, web, best, priors=(), want_sub=None, sub=None):
+        """One direction of a cost mode -> (web, best), with sub behind them where the mode has one (want_sub is not
+        None).  fn is the C function; mode(pairs, *prior pointers) gives its arguments from behind the images to before
+        the maps (evaluated last, as the call is made); side is "" or "_right", the suffix of the maps' names; priors
+        is (map, name) for every prior map the mode takes."""
+        left, right, pairs = self._pair(left, right)
+        priors = [_ptr(self._prior(p, pairs, name)) for p, name in priors]
+        maps = [self._out(web, pairs, "web" + side), self._out(best, pairs, "best" + side) if want_best else None]
+        if want_sub is not None:
+            maps.append(self._out(sub, pairs, "sub", torch.int16) if want_sub else None)
+        check(fn(self._h, _ptr(left), _ptr(right), *mode(pairs, *priors), *map(_ptr, maps), self._stream()))
+        return tuple(maps)
+
+    def _match_lr(self, fn, mode, left, right, max_diff, want_right, want_best, web, web_right, best, priors=(),
+                  want_sub=None, sub=None):
+        """Both directions of a cost mode and the check -> (web, rejected, web_right, best), with sub behind them where
+        the mode has one: the fields of LRResult / SGMLRResult.  fn, mode, priors: as _match_one's."""
+        left, right, pairs = self._pair(left, right)
+        priors = [_ptr(self._prior(p, pairs, name)) for p, name in priors]
+        web = self._out(web, pairs, "web")
+        web_right = self._out(web_right, pairs, "web_right") if want_right else None
+        best = self._out(best, pairs, "best") if want_best else None
+        subs = [] if want_sub is None else [self._out(sub, pairs, "sub", torch.int16) if want_sub else None]
+        rejected = torch.empty(pairs, dtype=torch.int32, device=self._dev)
+        check(fn(self._h, _ptr(left), _ptr(right), *mode(pairs, *priors), int(max_diff), _ptr(web), _ptr(best),
+                 _ptr(web_right), _ptr(rejected), *map(_ptr, subs), self._stream()))
+        return (web, rejected, web_right, best, *subs)
+
     def cost_wta(self, left, right, cost="sad", want_best=True, web=None, best=None):
         """SAD / SSD cost mode on the uint8 images (parity unpinned: the reference has no
         such mode) -> (web, best): arg-min over the shifts, first shift wins."""
@@ -361,33 +403,15 @@ class StereoPlan:
     def cost_wta_right(self, left, right, cost="sad", want_best=True, web_right=None, best_right=None):
         """The cost mode's right-reference map (sm_cost_wta_right) -> (web_right, best_right): web_right(u, y) = s'
         means right pixel u matched left pixel u - (s' - 1), best_right its window cost."""
-        left = self._images(left, torch.uint8, "left")
-        right = self._images(right, torch.uint8, "right")
-        pairs = left.shape[0]
-        if right.shape[0] != pairs:
-            raise ValueError(f"right: {right.shape[0]} images for {pairs} pairs")
-        web_right = self._out(web_right, pairs, "web_right")
-        best_right = self._out(best_right, pairs, "best_right") if want_best else None
-        check(lib.sm_cost_wta_right(self._h, _ptr(left), _ptr(right), {"sad": 1, "ssd": 2}[cost], pairs,
-                                    _ptr(web_right), _ptr(best_right), self._stream()))
-        return web_right, best_right
+        return self._match_one(lib.sm_cost_wta_right, lambda pairs: ({"sad": 1, "ssd": 2}[cost], pairs), left, right,
+                               "_right", want_best, web_right, best_right)
 
     def cost_lr(self, left, right, cost="sad", max_diff=0, want_right=False, want_best=False, web=None,
                 web_right=None, best=None) -> LRResult:
         """Left cost WTA, right cost WTA and check in one call (sm_cost_lr) -> LRResult(web, rejected, web_right,
         best); web is the checked map (0 = rejected), best the left window costs as cost_wta gives them."""
-        left = self._images(left, torch.uint8, "left")
-        right = self._images(right, torch.uint8, "right")
-        pairs = left.shape[0]
-        if right.shape[0] != pairs:
-            raise ValueError(f"right: {right.shape[0]} images for {pairs} pairs")
-        web = self._out(web, pairs, "web")
-        web_right = self._out(web_right, pairs, "web_right") if want_right else None
-        best = self._out(best, pairs, "best") if want_best else None
-        rejected = torch.empty(pairs, dtype=torch.int32, device=self._dev)
-        check(lib.sm_cost_lr(self._h, _ptr(left), _ptr(right), {"sad": 1, "ssd": 2}[cost], pairs, int(max_diff),
-                             _ptr(web), _ptr(best), _ptr(web_right), _ptr(rejected), self._stream()))
-        return LRResult(web, rejected, web_right, best)
+        return LRResult(*self._match_lr(lib.sm_cost_lr, lambda pairs: ({"sad": 1, "ssd": 2}[cost], pairs), left, right,
+                                        max_diff, want_right, want_best, web, web_right, best))
 
     def cost_refine(self, left, right, web, cost="sad", want_costs=False, out=None):
         """Subpixel refinement of a cost_wta map (sm_cost_refine) -> (sub, costs): sub is int16 in 1/16 of a shift
@@ -413,13 +437,6 @@ class StereoPlan:
         none yet), allocated now: keeps the allocation out of timed paths and out of stream captures."""
         check(lib.sm_plan_reserve_census(self._h))
 
-    def _census_pair(self, left, right):
-        left = self._images(left, torch.uint8, "left")
-        right = self._images(right, torch.uint8, "right")
-        if right.shape[0] != left.shape[0]:
-            raise ValueError(f"right: {right.shape[0]} images for {left.shape[0]} pairs")
-        return left, right, left.shape[0]
-
     def census_transform(self, images, census=7, out=None):
         """Census descriptors of uint8 gray images (sm_census_transform) -> int64 tensor of their bits, same shape:
         bit k = the k-th neighbour of the census x census window (row-major, centre skipped) is darker than the pixel."""
@@ -437,41 +454,27 @@ class StereoPlan:
     def census_wta(self, left, right, census=7, want_best=True, web=None, best=None):
         """Census cost mode (parity unpinned) -> (web, best): Hamming cost of census descriptors, n x n box sum,
         arg-min over the shifts, first shift wins."""
-        left, right, pairs = self._census_pair(left, right)
-        web = self._out(web, pairs, "web")
-        best = self._out(best, pairs, "best") if want_best else None
-        check(lib.sm_census_wta(self._h, _ptr(left), _ptr(right), int(census), pairs, _ptr(web), _ptr(best),
-                                self._stream()))
-        return web, best
+        return self._match_one(lib.sm_census_wta, lambda pairs: (int(census), pairs), left, right, "", want_best, web,
+                               best)
 
     def census_wta_right(self, left, right, census=7, want_best=True, web_right=None, best_right=None):
         """The census mode's right-reference map (sm_census_wta_right) -> (web_right, best_right): web_right(u, y) = s'
         means right pixel u matched left pixel u - (s' - 1)."""
-        left, right, pairs = self._census_pair(left, right)
-        web_right = self._out(web_right, pairs, "web_right")
-        best_right = self._out(best_right, pairs, "best_right") if want_best else None
-        check(lib.sm_census_wta_right(self._h, _ptr(left), _ptr(right), int(census), pairs, _ptr(web_right),
-                                      _ptr(best_right), self._stream()))
-        return web_right, best_right
+        return self._match_one(lib.sm_census_wta_right, lambda pairs: (int(census), pairs), left, right, "_right",
+                               want_best, web_right, best_right)
 
     def census_lr(self, left, right, census=7, max_diff=0, want_right=False, want_best=False, web=None,
                   web_right=None, best=None) -> LRResult:
         """Left and right census arg-min and the check in one call (sm_census_lr) -> LRResult(web, rejected, web_right,
         best); web is the checked map (0 = rejected), best the left window costs as census_wta gives them."""
-        left, right, pairs = self._census_pair(left, right)
-        web = self._out(web, pairs, "web")
-        web_right = self._out(web_right, pairs, "web_right") if want_right else None
-        best = self._out(best, pairs, "best") if want_best else None
-        rejected = torch.empty(pairs, dtype=torch.int32, device=self._dev)
-        check(lib.sm_census_lr(self._h, _ptr(left), _ptr(right), int(census), pairs, int(max_diff), _ptr(web),
-                               _ptr(best), _ptr(web_right), _ptr(rejected), self._stream()))
-        return LRResult(web, rejected, web_right, best)
+        return LRResult(*self._match_lr(lib.sm_census_lr, lambda pairs: (int(census), pairs), left, right, max_diff,
+                                        want_right, want_best, web, web_right, best))
 
     def census_refine(self, left, right, web, census=7, want_costs=False, out=None):
         """Subpixel refinement of a census map (sm_census_refine) -> (sub, costs): sub int16 in 1/16 of a shift by the
         equiangular fit over C(s-2), C(s-1), C(s) (0 where web is outside 1..D), costs (pairs, 3, H, W) int32 with -1
         where a shift has none, if wanted."""
-        left, right, pairs = self._census_pair(left, right)
+        left, right, pairs = self._pair(left, right)
         web = self._images(web, torch.int32, "web")
         if web.shape[0] != pairs:
             raise ValueError(f"web: {web.shape[0]} maps for {pairs} pairs")
@@ -483,51 +486,27 @@ class StereoPlan:
                                    _ptr(costs), self._stream()))
         return out, costs
 
-    def _prior(self, prior, pairs, name):
-        prior = self._images(prior, torch.int32, name)
-        if prior.shape[0] != pairs:
-            raise ValueError(f"{name}: {prior.shape[0]} maps for {pairs} pairs")
-        return prior
-
     def census_wta_near(self, left, right, prior, census=7, radius=1, want_best=True, web=None, best=None):
         """Guided census re-search (sm_census_wta_near) -> (web, best): census_wta's arg-min over the shifts within
         `radius` (1..4) of the int32 web map `prior` (1 + shift, 0 invalid) only -- the upsampled map of the
         half-resolution path; web = best = 0 where the prior leaves no shift."""
-        left, right, pairs = self._census_pair(left, right)
-        prior = self._prior(prior, pairs, "prior")
-        web = self._out(web, pairs, "web")
-        best = self._out(best, pairs, "best") if want_best else None
-        check(lib.sm_census_wta_near(self._h, _ptr(left), _ptr(right), int(census), pairs, _ptr(prior), int(radius),
-                                     _ptr(web), _ptr(best), self._stream()))
-        return web, best
+        return self._match_one(lib.sm_census_wta_near, lambda pairs, p: (int(census), pairs, p, int(radius)), left, right,
+                               "", want_best, web, best, priors=((prior, "prior"),))
 
     def census_wta_near_right(self, left, right, prior_right, census=7, radius=1, want_best=True, web_right=None,
                               best_right=None):
         """The right-reference re-search (sm_census_wta_near_right) -> (web_right, best_right), around a
         right-reference prior map."""
-        left, right, pairs = self._census_pair(left, right)
-        prior_right = self._prior(prior_right, pairs, "prior_right")
-        web_right = self._out(web_right, pairs, "web_right")
-        best_right = self._out(best_right, pairs, "best_right") if want_best else None
-        check(lib.sm_census_wta_near_right(self._h, _ptr(left), _ptr(right), int(census), pairs, _ptr(prior_right),
-                                           int(radius), _ptr(web_right), _ptr(best_right), self._stream()))
-        return web_right, best_right
+        return self._match_one(lib.sm_census_wta_near_right, lambda pairs, p: (int(census), pairs, p, int(radius)), left,
+                               right, "_right", want_best, web_right, best_right, priors=((prior_right, "prior_right"),))
 
     def census_near_lr(self, left, right, prior, prior_right, census=7, radius=1, max_diff=0, want_right=False,
                        want_best=False, web=None, web_right=None, best=None) -> LRResult:
         """Both re-searches and the check in one call (sm_census_near_lr) -> LRResult(web, rejected, web_right, best),
         shaped like census_lr's."""
-        left, right, pairs = self._census_pair(left, right)
-        prior = self._prior(prior, pairs, "prior")
-        prior_right = self._prior(prior_right, pairs, "prior_right")
-        web = self._out(web, pairs, "web")
-        web_right = self._out(web_right, pairs, "web_right") if want_right else None
-        best = self._out(best, pairs, "best") if want_best else None
-        rejected = torch.empty(pairs, dtype=torch.int32, device=self._dev)
-        check(lib.sm_census_near_lr(self._h, _ptr(left), _ptr(right), int(census), pairs, _ptr(prior),
-                                    _ptr(prior_right), int(radius), int(max_diff), _ptr(web), _ptr(best),
-                                    _ptr(web_right), _ptr(rejected), self._stream()))
-        return LRResult(web, rejected, web_right, best)
+        return LRResult(*self._match_lr(
+            lib.sm_census_near_lr, lambda pairs, p, q: (int(census), pairs, p, q, int(radius)), left, right, max_diff,
+            want_right, want_best, web, web_right, best, priors=((prior, "prior"), (prior_right, "prior_right"))))
 
     # ---- semi-global matching over the census data term ------------------------
     def reserve_sgm(self):
@@ -542,40 +521,24 @@ class StereoPlan:
         larger jump, arg-min over the shifts (first shift wins), best = the minimum aggregate, sub int16 in 1/16 of a
         shift (parabola fit on the aggregates).  Outputs not wanted are None.  The default penalties suit a 1 x 1
         window (the pixelwise census cost, at most 48); window costs grow with n^2, so scale p1 and p2 with it."""
-        left, right, pairs = self._census_pair(left, right)
-        web = self._out(web, pairs, "web")
-        best = self._out(best, pairs, "best") if want_best else None
-        sub = self._out(sub, pairs, "sub", torch.int16) if want_sub else None
-        check(lib.sm_sgm_wta(self._h, _ptr(left), _ptr(right), int(census), int(p1), int(p2), int(paths), pairs,
-                             _ptr(web), _ptr(best), _ptr(sub), self._stream()))
-        return web, best, sub
+        return self._match_one(lib.sm_sgm_wta, lambda pairs: (int(census), int(p1), int(p2), int(paths), pairs), left,
+                               right, "", want_best, web, best, want_sub=want_sub, sub=sub)
 
     def sgm_wta_right(self, left, right, census=7, p1=10, p2=120, paths=8, want_best=True, web_right=None,
                       best_right=None):
         """The SGM right-reference map (sm_sgm_wta_right) -> (web_right, best_right): web_right(u, y) = s' means right
         pixel u matched left pixel u - (s' - 1)."""
-        left, right, pairs = self._census_pair(left, right)
-        web_right = self._out(web_right, pairs, "web_right")
-        best_right = self._out(best_right, pairs, "best_right") if want_best else None
-        check(lib.sm_sgm_wta_right(self._h, _ptr(left), _ptr(right), int(census), int(p1), int(p2), int(paths), pairs,
-                                   _ptr(web_right), _ptr(best_right), self._stream()))
-        return web_right, best_right
+        return self._match_one(lib.sm_sgm_wta_right, lambda pairs: (int(census), int(p1), int(p2), int(paths), pairs),
+                               left, right, "_right", want_best, web_right, best_right)
 
     def sgm_lr(self, left, right, census=7, p1=10, p2=120, paths=8, max_diff=0, want_right=False, want_best=False,
                want_sub=False, web=None, web_right=None, best=None, sub=None) -> SGMLRResult:
         """Left and right SGM and the check in one call (sm_sgm_lr) -> SGMLRResult(web, rejected, web_right, best,
         sub); web is the checked map (0 = rejected), best the left minima, sub the left subpixel map with 0 where
         rejected."""
-        left, right, pairs = self._census_pair(left, right)
-        web = self._out(web, pairs, "web")
-        web_right = self._out(web_right, pairs, "web_right") if want_right else None
-        best = self._out(best, pairs, "best") if want_best else None
-        sub = self._out(sub, pairs, "sub", torch.int16) if want_sub else None
-        rejected = torch.empty(pairs, dtype=torch.int32, device=self._dev)
-        check(lib.sm_sgm_lr(self._h, _ptr(left), _ptr(right), int(census), int(p1), int(p2), int(paths), pairs,
-                            int(max_diff), _ptr(web), _ptr(best), _ptr(web_right), _ptr(rejected), _ptr(sub),
-                            self._stream()))
-        return SGMLRResult(web, rejected, web_right, best, sub)
+        return SGMLRResult(*self._match_lr(
+            lib.sm_sgm_lr, lambda pairs: (int(census), int(p1), int(p2), int(paths), pairs), left, right, max_diff,
+            want_right, want_best, web, web_right, best, want_sub=want_sub, sub=sub))
 
     # ---- disparity post-filters (between the check and step 3) ------------------
     def reserve_filter(self):
