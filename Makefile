@@ -26,7 +26,7 @@ CFLAGS := -std=gnu11 -Wall -Wextra -pedantic -Wno-unused-parameter -Iinclude -Io
 
 HOSTDIR := stereomatching_amd/host
 CSRC    := stereomatching_amd/csrc
-KERNELS := sm_match_bs_ds8 sm_match_bs sm_match_bs_duo8 sm_match_bs_duo sm_match_bs_ds4 sm_api sm_edges sm_run sm_step3 sm_match sm_cost sm_cost_qs sm_cost_pc sm_cost_mfma sm_cost_strip sm_gather sm_lr sm_subpix sm_census sm_sgm sm_filter sm_interp sm_rectify
+KERNELS := sm_match_bs_ds8 sm_match_bs sm_match_bs_duo8 sm_match_bs_duo sm_match_bs_ds4 sm_api sm_edges sm_run sm_step3 sm_match sm_cost sm_cost_qs sm_cost_pc sm_cost_mfma sm_cost_strip sm_gather sm_lr sm_subpix sm_census sm_census_near sm_sgm sm_filter sm_wmedian sm_pyramid sm_interp sm_rectify sm_reproject
 DEVOBJ  := $(addprefix stereomatching_amd/obj/product/,$(addsuffix .o,$(KERNELS)))
 # (the same flags, in the same order, as HIPCC_FLAGS of stereomatching_amd/build.py: the two share
 #  stereomatching_amd/obj/product and its flags.txt stamp, so neither rebuilds what the other built)
@@ -52,16 +52,8 @@ $(DEVSTAMP): FORCE
 	@mkdir -p $(dir $@)
 	@if [ "$$(cat $@ 2>/dev/null)" != "$(HIPFLAGS_BARE)" ]; then rm -f $(dir $@)*.o; echo "$(HIPFLAGS_BARE)" > $@; fi
 FORCE:
-stereomatching_amd/obj/product/%.o: $(CSRC)/%.hip $(CSRC)/sm_internal.h $(CSRC)/sm_entry.h $(CSRC)/sm_match_bs_kernel.h $(CSRC)/sm_bs_network.h $(CSRC)/sm_bs_ops.h $(CSRC)/sm_cost.h $(CSRC)/sm_device.h $(CSRC)/sm_geom.h $(CSRC)/sm_plan_model.h include/stereo_hip.h $(DEVSTAMP)
+stereomatching_amd/obj/product/%.o: $(CSRC)/%.hip $(CSRC)/sm_internal.h $(CSRC)/sm_entry.h $(CSRC)/sm_match_bs_kernel.h $(CSRC)/sm_bs_network.h $(CSRC)/sm_bs_ops.h $(CSRC)/sm_cost.h $(CSRC)/sm_census.h $(CSRC)/sm_device.h $(CSRC)/sm_geom.h $(CSRC)/sm_plan_model.h include/stereo_hip.h $(DEVSTAMP)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-# (the reprojection stage is built in the rectification's unit, which includes it)
-stereomatching_amd/obj/product/sm_rectify.o: $(CSRC)/sm_reproject.hip
-# (... and the guided weighted median in the post-filters')
-stereomatching_amd/obj/product/sm_filter.o: $(CSRC)/sm_wmedian.hip
-# (... and the half-resolution path beside it)
-stereomatching_amd/obj/product/sm_filter.o: $(CSRC)/sm_pyramid.hip
-# (... and the guided census re-search in the census mode's unit)
-stereomatching_amd/obj/product/sm_census.o: $(CSRC)/sm_census_near.hip
 $(DEVLIB): $(DEVOBJ)
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC $^ -o $@
 

@@ -21,12 +21,9 @@ LIB = PKG / "libstereo_hip.so"
 # compile side by side (one unit: ~2 min; four beside the rest: ~50 s on 8 cores)
 SOURCES = ["sm_match_bs_ds8.hip", "sm_match_bs.hip", "sm_match_bs_duo8.hip", "sm_match_bs_duo.hip", "sm_match_bs_ds4.hip",
            "sm_api.hip", "sm_edges.hip", "sm_run.hip", "sm_step3.hip", "sm_match.hip", "sm_cost.hip", "sm_cost_qs.hip", "sm_cost_pc.hip", "sm_cost_mfma.hip", "sm_cost_strip.hip", "sm_gather.hip", "sm_lr.hip",
-           "sm_subpix.hip", "sm_census.hip", "sm_sgm.hip", "sm_filter.hip", "sm_interp.hip", "sm_rectify.hip"]
-# files a source includes beside HEADERS: the reprojection stage is built in the rectification's unit, the guided
-# weighted median and the half-resolution path in the post-filters', the guided census re-search in the census mode's
-INCLUDED = {"sm_rectify.hip": [CSRC / "sm_reproject.hip"], "sm_filter.hip": [CSRC / "sm_wmedian.hip", CSRC / "sm_pyramid.hip"],
-            "sm_census.hip": [CSRC / "sm_census_near.hip"]}
-HEADERS = [CSRC / "sm_internal.h", CSRC / "sm_entry.h", CSRC / "sm_match_bs_kernel.h", CSRC / "sm_bs_network.h", CSRC / "sm_bs_ops.h", CSRC / "sm_cost.h", CSRC / "sm_device.h", CSRC / "sm_geom.h", CSRC / "sm_plan_model.h", ROOT / "include" / "stereo_hip.h"]
+           "sm_subpix.hip", "sm_census.hip", "sm_census_near.hip", "sm_sgm.hip", "sm_filter.hip", "sm_wmedian.hip", "sm_pyramid.hip", "sm_interp.hip",
+           "sm_rectify.hip", "sm_reproject.hip"]
+HEADERS = [CSRC / "sm_internal.h", CSRC / "sm_entry.h", CSRC / "sm_match_bs_kernel.h", CSRC / "sm_bs_network.h", CSRC / "sm_bs_ops.h", CSRC / "sm_cost.h", CSRC / "sm_census.h", CSRC / "sm_device.h", CSRC / "sm_geom.h", CSRC / "sm_plan_model.h", ROOT / "include" / "stereo_hip.h"]
 OBJDIR = PKG / "obj"
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
@@ -78,7 +75,7 @@ def _compile_and_link(out: Path, objdir: Path, flags=(), verbose: bool = False, 
 
     def one(src: str) -> Path:
         obj = objdir / (Path(src).stem + ".o")
-        if not _stale(obj, [CSRC / src, *INCLUDED.get(src, []), *HEADERS]):
+        if not _stale(obj, [CSRC / src, *HEADERS]):
             return obj
         cmd = [_hipcc(), *common, "-c", str(CSRC / src), "-o", str(obj)]
         if verbose:
@@ -94,7 +91,7 @@ def _compile_and_link(out: Path, objdir: Path, flags=(), verbose: bool = False, 
 
 
 def build_hip(force: bool = False, verbose: bool = False) -> Path:
-    deps = [CSRC / s for s in SOURCES] + [f for fs in INCLUDED.values() for f in fs] + HEADERS
+    deps = [CSRC / s for s in SOURCES] + HEADERS
     if force or _stale(LIB, deps):
         _compile_and_link(LIB, OBJDIR / "product", verbose=verbose)
     return LIB
@@ -105,7 +102,7 @@ def build_diag(verbose: bool = False, name: str = "stamps", flags=()) -> Path:
     time stamps); a diagnostic build, loaded only by tools/wave_timeline.py."""
     out = ROOT / "tools" / "diag" / f"libstereo_hip_{name}.so"
     out.parent.mkdir(parents=True, exist_ok=True)
-    deps = [CSRC / s for s in SOURCES] + [f for fs in INCLUDED.values() for f in fs] + HEADERS
+    deps = [CSRC / s for s in SOURCES] + HEADERS
     if _stale(out, deps):
         _compile_and_link(out, OBJDIR / f"diag_{name}", ["-DSM_STAMPS", *flags], verbose)
     return out

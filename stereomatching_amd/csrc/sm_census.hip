@@ -28,14 +28,11 @@
 //                       equiangular fit.
 
 #include "sm_device.h"
-#include "sm_entry.h"
+#include "sm_census.h"
 #include "sm_plan_model.h"
 
-typedef unsigned long long u64;
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
-#define SMN_TX 64          // transform: columns per workgroup
-#define SMN_TR 16          // transform: rows per workgroup (4 per lane)
 #define SMN_DS 8           // wta: shifts per lane
 #define SMN_DCHUNK 128     // wta: shifts per launch at most
 #define SMN_PFMAX 9        // wta: descriptors one lane fetches per ring row at most (checked by the host)
@@ -477,7 +474,7 @@ extern "C" int sm_plan_reserve_census(sm_plan *plan)
 }
 
 // what every census entry checks besides its pointers (before any device call)
-static int census_args(const sm_plan *plan, int census_width, int pairs, const char *me)
+int sm_census_args(const sm_plan *plan, int census_width, int pairs, const char *me)
 {
     SM_TRY(sm_check_census_width(census_width, me));
     SM_TRY(sm_check_pairs(plan, pairs, me));
@@ -516,7 +513,7 @@ int sm_census_descriptors(sm_plan *plan, int cw, const uint8_t *left, const uint
 }
 
 // the arg-min over the plan's shifts from the workspace's descriptors, in launches of at most SMN_DCHUNK shifts
-static int wta_launch(const sm_plan *plan, int cw, bool mirror, int pairs, i32 *d_web, i32 *d_best, hipStream_t st)
+int sm_census_wta_launch(const sm_plan *plan, int cw, bool mirror, int pairs, i32 *d_web, i32 *d_best, hipStream_t st)
 {
     const int nw = cw == 7 ? 2 : 1;
     CensusGeom g;
@@ -575,19 +572,6 @@ extern "C" int sm_census_transform(sm_plan *plan, const uint8_t *d_gray, int cen
     return transform_launch(plan, census_width, 2, d_gray, images, nullptr, 0, (u32 *)d_desc, 0, (hipStream_t)stream);
 }
 
-// the mode as the entry driver sees it (sm_entry.h)
-struct CensusMode : sm_mode {
-    static constexpr const sm_ws_set &ws = SM_WS_SET_CENSUS;
-    int cw;
-    explicit CensusMode(int census_width) : cw(census_width) {}
-    int args(const sm_call &c) const { return census_args(c.plan, cw, c.pairs, c.me); }
-    int prepare(const sm_call &c) const { return sm_census_descriptors(c.plan, cw, c.left, c.right, c.pairs, c.st); }
-    int pass(const sm_call &c, bool mirror, i32 *web, i32 *best, int16_t *) const
-    {
-        return wta_launch(c.plan, cw, mirror, c.pairs, web, best, c.st);
-    }
-};
-
 extern "C" int sm_census_wta(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
                              int pairs, int32_t *d_web, int32_t *d_best, void *stream)
 {
@@ -616,7 +600,7 @@ extern "C" int sm_census_refine(sm_plan *plan, const uint8_t *d_gray_left, const
 {
     const char *me = "sm_census_refine";
     if (!d_gray_left || !d_gray_right || !d_web || !d_sub) return sm_fail(SM_ERR_ARG, "%s: NULL argument", me);
-    SM_TRY(census_args(plan, census_width, pairs, me));
+    SM_TRY(sm_census_args(plan, census_width, pairs, me));
     SM_TRY(sm_use_device(plan->device));
     hipStream_t st = (hipStream_t)stream;
     SM_TRY(sm_ws_need(plan, SM_WS_SET_CENSUS, st, me));
@@ -634,6 +618,3 @@ extern "C" int sm_census_refine(sm_plan *plan, const uint8_t *d_gray_left, const
     if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_census_refine failed: %s", hipGetErrorString(e));
     return SM_OK;
 }
-
-// the guided re-search (sm_census_wta_near and its kin), built in this unit: DESIGN.md 21
-#include "sm_census_near.hip"

@@ -1,7 +1,6 @@
 // sm_census_near.hip -- census cost mode, guided re-search: the arg-min of sm_census_wta over the shifts within
-// `radius` of a prior map (the upsampled map of the half-resolution path), DESIGN.md 21.  Built in sm_census.hip's
-// unit (its last line includes this file): it uses that unit's census_args, sm_census_descriptors and descriptor
-// layout.
+// `radius` of a prior map (the upsampled map of the half-resolution path), DESIGN.md 21.  It uses the census mode's
+// argument checks, descriptors and descriptor layout (sm_census.h; the workspace is filled by sm_census_descriptors).
 //
 // PARITY UNPINNED.  Definition (A_d: sm_census_wta's window cost; prior: a web map, 1 + shift, 0 invalid; r = radius):
 //   K(p) = { d : 0 <= d <= D - 1, |d - (prior(p) - 1)| <= r }, empty for prior(p) = 0;
@@ -23,6 +22,9 @@
 // of a lane and slides the window down the image), and is still exact.  LDS: (64 + n - 1)(16 + n - 1) + 64 (16 + n - 1)
 // u16 and the mask, 12.2 KB at n = 25: the tile is 64 wide for every window.
 //   MIRROR: the right-reference pass, as in k_census_wta: the pass's columns are read and written mirrored.
+
+#include "sm_device.h"
+#include "sm_census.h"
 
 #define SMN_NQ 14          // near: positions per lane at most ((64 + 24) * (16 + 24) / 256, rounded up)
 #define SMN_NR 10          // near: rows of positions per wave at most ((16 + 24) / 4)
@@ -254,12 +256,12 @@ static int near_launch(const sm_plan *plan, int cw, bool mirror, int pairs, cons
     return SM_OK;
 }
 
-// what the three entries check besides their pointers: the radius (which needs no plan) and census_args; then every
+// what the three entries check besides their pointers: the radius (which needs no plan) and sm_census_args; then every
 // output against the images and the priors
 static int near_args(const sm_plan *plan, int census_width, int pairs, int radius, const char *me)
 {
     if (radius < 1 || radius > 4) return sm_fail(SM_ERR_ARG, "%s: radius %d outside 1..4", me, radius);
-    return census_args(plan, census_width, pairs, me);
+    return sm_census_args(plan, census_width, pairs, me);
 }
 
 static int near_inputs_apart(const sm_plan *plan, int pairs, const uint8_t *left, const uint8_t *right,

@@ -36,6 +36,23 @@ __device__ __forceinline__ void lr_count(i32 *rejected, int cnt)
     }
 }
 
+// The post-filters' tile (sm_filter.hip, sm_wmedian.hip, sm_pyramid.hip): 64 columns x 16 rows per workgroup of 256 lanes
+#define FLT_TW 64
+#define FLT_TH 16
+#define FLT_PX (FLT_TW * FLT_TH)
+
+// the weight table of the guided filters, passed by value in the kernel's arguments (k_wmedian, k_upsample_double)
+struct WmedTable {
+    uint16_t w[256];
+};
+
+static inline WmedTable wmed_table(const uint16_t weights[256])
+{
+    WmedTable table;
+    for (int i = 0; i < 256; i++) table.w[i] = weights[i];
+    return table;
+}
+
 // Batcher's merge exchange (Knuth 5.2.2 M) for N elements: the comparators in order (the median, k_itp_combine)
 template <int N>
 struct FltNet {

@@ -1,5 +1,5 @@
 // sm_entry.h -- one driver for the left, right and checked entry points of every cost mode.
-// Included by the units that define a mode (sm_census.hip with sm_census_near.hip, sm_sgm.hip, sm_lr.hip); an entry
+// Included by the units that define a mode (sm_census.hip and sm_census_near.hip through sm_census.h, sm_sgm.hip, sm_lr.hip); an entry
 // point is one call of sm_entry_one or sm_entry_lr with the call's arguments and the mode's description.
 #pragma once
 

@@ -37,10 +37,6 @@
 
 #include <algorithm>
 
-#define FLT_TW 64
-#define FLT_TH 16
-#define FLT_PX (FLT_TW * FLT_TH)
-
 // ---------------------------------------------------------------------------
 // median (the exchange network, flt_sort, is in sm_device.h: the interpolation sorts its candidates with it)
 // ---------------------------------------------------------------------------
@@ -419,8 +415,3 @@ extern "C" int sm_valid_mask(sm_plan *plan, void *d_map, int map_type, const uin
     SM_LAUNCH_CHECK("k_valid_mask");
     return SM_OK;
 }
-
-// the guided weighted median, a source file of its own built in this unit
-#include "sm_wmedian.hip"
-// ... and the half-resolution path (it takes the weight table as the weighted median does)
-#include "sm_pyramid.hip"

@@ -32,8 +32,6 @@
 //                          owns a column of the tile and four of its rows.  Nine values and nine weights in registers;
 //                          every tap sums the weights of the taps <= it (81 compare-adds) and the least tap that
 //                          reaches half of T is the result: no bisection, no sort.
-//
-// This file is compiled as part of sm_filter.hip's translation unit (its last line includes it): see INTEGRATION.md.
 
 #include "sm_device.h"
 
@@ -226,8 +224,7 @@ extern "C" int sm_upsample_double(sm_plan *plan, const void *d_in, int map_type,
         return sm_fail(SM_ERR_ARG, "%s: a guide overlaps the output map", me);
     SM_TRY(sm_use_device(plan->device));
     hipStream_t st = (hipStream_t)stream;
-    WmedTable table;
-    for (int i = 0; i < 256; i++) table.w[i] = weights[i];
+    const WmedTable table = wmed_table(weights);
     const dim3 grid((W + FLT_TW - 1) / FLT_TW, (H + FLT_TH - 1) / FLT_TH, pairs), block(256);
     const int fill = (flags & SM_UP_FILL) != 0;
     if (map_type == SM_MAP_I32)

@@ -316,6 +316,3 @@ extern "C" int sm_rectify_map_build(sm_plan *plan, const sm_rectify_calib *calib
                        "not a map)", me);
     return SM_OK;
 }
-
-// the stage at the other end of the chain, built in this unit: disparity -> depth, XYZ and point clouds
-#include "sm_reproject.hip"

@@ -20,8 +20,6 @@
 // 16-byte depth store, three 16-byte stores for the 48 contiguous bytes of its four triples.  Other widths and
 // alignments take one pixel per lane (V = 1).  The cloud reads one element per lane and iteration (the order of the
 // records is the order of the lanes) and computes the arithmetic twice instead of storing a dense XYZ map in between.
-//
-// This file is compiled as part of sm_rectify.hip's translation unit (its last line includes it): see INTEGRATION.md.
 
 #include "sm_device.h"
 

@@ -29,17 +29,11 @@
 //                    the compiler keeps the first pass's loads alive over the bisection (256 registers at R = 5, one
 //                    wave per SIMD), and 225 taps do not fit a lane's registers at all.
 //                    Filled pixels are counted as the other stages count (lr_count: one atomic per workgroup).
-//
-// This file is compiled as part of sm_filter.hip's translation unit (its last line includes it): see INTEGRATION.md.
 
 #include "sm_device.h"
 
 #define WMED_MAX_R 7
 #define WMED_REG_R 3       // up to this radius a lane keeps its window in registers (49 values, 49 weights)
-
-struct WmedTable {
-    uint16_t w[256];
-};
 
 // the smallest x in lo .. hi with 2 * cum(x) >= total, where cum(hi) = total (so one exists)
 template <typename Cum>
@@ -188,8 +182,7 @@ extern "C" int sm_weighted_median(sm_plan *plan, const void *d_in, int map_type,
         return sm_fail(SM_ERR_ARG, "%s: d_filled overlaps a map", me);
     SM_TRY(sm_use_device(plan->device));
     hipStream_t st = (hipStream_t)stream;
-    WmedTable table;
-    for (int i = 0; i < 256; i++) table.w[i] = weights[i];
+    const WmedTable table = wmed_table(weights);
     if (d_filled) SM_TRY(sm_lr_zero_counts(d_filled, pairs, st));
     // (without the flag nothing is filled: the counts stay 0 and the kernel counts nothing)
     i32 *filled = fill ? d_filled : nullptr;
