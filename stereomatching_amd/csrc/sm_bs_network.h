@@ -22,6 +22,15 @@
 // host (-DSM_BS_NETWORK_HOST: bop<IMM> in plain C++), where tests/helpers/bs_network_check.cpp
 // runs it against integer arithmetic.  net_plan also counts the operations, next to those of the
 // forms it replaces (two count_lockstep trees + addsub_lockstep): net_ops / net_ops_separate.
+//
+// GROUPED inputs (GR).  The sum bit of a first cell over three columns c, c + 1, c + 2 of ONE row,
+//     s = x_c ^ x_c+1 ^ x_c+2 = (L_c ^ L_c+1 ^ L_c+2) ^ (R_c+d ^ R_c+1+d ^ R_c+2+d) = LX_c ^ RX_c+d,
+// needs none of the three mismatch bits: LX is shared by every shift of the row and RX_u by every (c, d) with
+// c + d = u.  Its carry needs two of them, maj(x_c, x_c+1, x_c+2) = maj(x_c, x_c+1, ~s).  So of every three
+// columns of a row side the third input is the PARITY of the group, handed in like a bit, and a carry-only cell
+// turns (x_c, x_c+1, parity) into the wire of weight 2; the parity itself is the wire of weight 1.  Both carry the
+// sign of their row.  floor(N / 3) groups per row side, the N mod 3 columns left over stay single bits: one
+// operation fewer per group, net_ops<N, true>() == net_ops<N>() - 2 * (N / 3).
 #pragma once
 
 #ifdef SM_BS_NETWORK_HOST
@@ -48,10 +57,13 @@ inline u32 bop(u32 a, u32 b, u32 c)      // bit (a<<2|b<<1|c) of IMM, like v_bit
 
 // one cell: inputs a, b, c (wire numbers; c < 0: a half adder, b < 0 as well: none), the wire
 // of its sum and of its carry (< 0: not made), and the immediate of the carry
-struct NetCell { short a, b, c, s, cy; short imm; short w; };
+// grp: the carry-only cell of a group of three columns: a, b are two of its bits, c is its parity, which IS the
+// sum -- wire s is c under another number, no operation
+struct NetCell { short a, b, c, s, cy; short imm; short w; bool grp = false; };
 
 // Wire numbers: [0, N) entering bits, [N, 2N) leaving bits, [2N, 2N + SB) the planes of S,
-// from 2N + SB on the outputs of the cells in the order they are made.
+// from 2N + SB on the outputs of the cells in the order they are made.  Grouped: inputs 3g, 3g + 1 of a row
+// side are the first two bits of group g and input 3g + 2 is its parity, g < N / 3.
 template <int N, int SB>
 struct NetPlan {
     static constexpr int NIN = 2 * N + SB;
@@ -63,28 +75,48 @@ struct NetPlan {
     short out[SB] = {};         // the wire that is plane k of S'
 };
 
-template <int N, int SB>
+template <int N, int SB, bool GR = false>
 constexpr NetPlan<N, SB> net_make_plan()
 {
     NetPlan<N, SB> p;
+    constexpr int G = GR ? N / 3 : 0;
     // The wires of a weight are reduced as a CHAIN: a cell takes the sum of the cell before it and
     // two fresh wires, so one partial sum per weight is alive, not a level of a tree.
     short q[4 * N + 4 * SB] = {}, nx[2 * N + 2 * SB] = {};
     bool qneg[4 * N + 4 * SB] = {}, nxneg[2 * N + 2 * SB] = {};
+    short qgrp[4 * N + 4 * SB] = {};    // 1 + first input of a group whose carry-only cell is still to be made
     int head = 0, tail = 0, nn = 0;
     for (int w = 0; w < SB; w++) {
         const bool top = w == SB - 1;
         head = 0; tail = 0;
         q[tail] = (short)(2 * N + w); qneg[tail++] = false;          // plane w of S: ready from the start
-        if (w == 0)
-            for (int i = 0; i < N; i++) {                            // entering and leaving bits by turns
+        if (w == 0) {
+            for (int g = 0; g < G; g++) {                            // entering and leaving groups by turns
+                qgrp[tail] = (short)(1 + 3 * g); qneg[tail++] = false;
+                qgrp[tail] = (short)(1 + N + 3 * g); qneg[tail++] = true;
+            }
+            for (int i = 3 * G; i < N; i++) {                        // entering and leaving bits by turns
                 q[tail] = (short)i; qneg[tail++] = false;
                 q[tail] = (short)(N + i); qneg[tail++] = true;
             }
+        }
         for (int i = 0; i < nn; i++) { q[tail] = nx[i]; qneg[tail++] = nxneg[i]; }
         nn = 0;
         while (tail - head >= 2) {
             const int k = tail - head >= 3 ? 3 : 2;
+            // a group is opened right in front of the cell that takes its parity: its carry goes to the next
+            // weight with the sign of its row
+            for (int j = 0; j < k; j++)
+                if (qgrp[head + j]) {
+                    const short in0 = (short)(qgrp[head + j] - 1);
+                    NetCell gc = {in0, (short)(in0 + 1), (short)(in0 + 2), -1, -1, BOP_MAJ_NC, (short)w, true};
+                    gc.s = (short)p.nwires++;
+                    gc.cy = (short)p.nwires++;
+                    nx[nn] = gc.cy; nxneg[nn++] = qneg[head + j];
+                    p.nops++;
+                    q[head + j] = gc.s; qgrp[head + j] = 0;
+                    p.cell[p.ncell++] = gc;
+                }
             // the positive inputs first
             short in[3] = {-1, -1, -1};
             int np = 0, ng = 0;
@@ -138,15 +170,15 @@ constexpr NetPlan<N, SB> net_make_plan()
 }
 
 // the plan of a window, made once; the functions below take a copy of it as a constant of their own
-template <int N, int SB>
-struct NetPlanOf { static constexpr NetPlan<N, SB> value = net_make_plan<N, SB>(); };
+template <int N, int SB, bool GR = false>
+struct NetPlanOf { static constexpr NetPlan<N, SB> value = net_make_plan<N, SB, GR>(); };
 
 // the shortest distance, in operations of one item's instruction stream of IT items side by
 // side, between an operation and the operation that made one of its inputs
-template <int N, int SB>
+template <int N, int SB, bool GR = false>
 constexpr int net_min_distance(int it)
 {
-    const NetPlan<N, SB> p = NetPlanOf<N, SB>::value;
+    const NetPlan<N, SB> p = NetPlanOf<N, SB, GR>::value;
     int pos[NetPlan<N, SB>::NIN + 2 * NetPlan<N, SB>::MAXC] = {};
     for (int i = 0; i < NetPlan<N, SB>::NIN; i++) pos[i] = -(1 << 20);
     int at = 0, best = 1 << 20;
@@ -155,15 +187,16 @@ constexpr int net_min_distance(int it)
         const short in[3] = {c.a, c.b, c.c};
         for (int j = 0; j < 3; j++)
             if (in[j] >= 0 && at - pos[in[j]] < best) best = at - pos[in[j]];
-        pos[c.s] = at; at += it;
+        pos[c.s] = at;
+        if (!c.grp) at += it;       // (a group's parity is there before its carries are issued)
         if (c.cy >= 0) { pos[c.cy] = at; at += it; }
     }
     return best;
 }
 
 // operations of the network per item (the mismatch bits themselves not counted) ...
-template <int N>
-constexpr int net_ops() { return net_make_plan<N, bits_for(N * N)>().nops; }
+template <int N, bool GR = false>
+constexpr int net_ops() { return net_make_plan<N, bits_for(N * N), GR>().nops; }
 // ... and of the separate forms: two carry-save trees N -> HB planes, the HB-plane two's
 // complement difference, the ripple add of its sign extension into the SB planes
 constexpr int net_ops_count_tree(int n)
@@ -189,7 +222,8 @@ constexpr int net_ops_separate(int n) { return 2 * net_ops_count_tree(n) + net_o
 // ---------------------------------------------------------------------------
 // the network itself: S[dd0 + it] += sum_i xin(it, i) - sum_i xin(it, N + i), i < N, for
 // it < IT side by side.  Inputs are made when first used.  Every dependency has a distance
-// of at least IT operations: the sums of a cell for all items, then its carries.
+// of at least IT operations: the sums of a cell for all items, then its carries.  Grouped: xin(it, 3g + 2)
+// and xin(it, N + 3g + 2) are the parities of the groups, every other input is a mismatch bit as before.
 // ---------------------------------------------------------------------------
 template <int N, int SB, int IT, int DS, int NW, int ID, typename XF>
 SM_NET_FN u32 net_wire(const u32 (&S)[DS][SB], int dd0, XF &xin, const u32 (&wr)[IT][NW], int it)
@@ -199,10 +233,10 @@ SM_NET_FN u32 net_wire(const u32 (&S)[DS][SB], int dd0, XF &xin, const u32 (&wr)
     else return wr[it][ID - 2 * N - SB];
 }
 
-template <int N, int SB, int IT, int DS, int C, int NW, typename XF>
+template <int N, int SB, int IT, int DS, bool GR, int C, int NW, typename XF>
 SM_NET_FN void net_cells(u32 (&S)[DS][SB], int dd0, XF &xin, u32 (&wr)[IT][NW])
 {
-    constexpr NetPlan<N, SB> P = NetPlanOf<N, SB>::value;
+    constexpr NetPlan<N, SB> P = NetPlanOf<N, SB, GR>::value;
     if constexpr (C < P.ncell) {
         constexpr NetCell cl = P.cell[C];
         constexpr int NIN = 2 * N + SB;
@@ -217,9 +251,12 @@ SM_NET_UNROLL
         }
 SM_NET_UNROLL
         for (int it = 0; it < IT; it++) {
-            if constexpr (full) wr[it][cl.s - NIN] = bop<BOP_XOR3>(a[it], b[it], c[it]);
-            else wr[it][cl.s - NIN] = a[it] ^ b[it];
-            SM_PIN();
+            if constexpr (cl.grp) wr[it][cl.s - NIN] = c[it];
+            else {
+                if constexpr (full) wr[it][cl.s - NIN] = bop<BOP_XOR3>(a[it], b[it], c[it]);
+                else wr[it][cl.s - NIN] = a[it] ^ b[it];
+                SM_PIN();
+            }
         }
         if constexpr (cl.cy >= 0) {
 SM_NET_UNROLL
@@ -230,28 +267,28 @@ SM_NET_UNROLL
             }
         }
         SM_SYNC();
-        net_cells<N, SB, IT, DS, C + 1, NW>(S, dd0, xin, wr);
+        net_cells<N, SB, IT, DS, GR, C + 1, NW>(S, dd0, xin, wr);
     }
 }
 
-template <int N, int SB>
+template <int N, int SB, bool GR = false>
 constexpr bool net_planes_from_cells()
 {
-    constexpr NetPlan<N, SB> P = NetPlanOf<N, SB>::value;
+    constexpr NetPlan<N, SB> P = NetPlanOf<N, SB, GR>::value;
     for (int k = 0; k < SB; k++)
         if (P.out[k] < 2 * N + SB) return false;
     return true;
 }
 
-template <int N, int SB, int IT, int DS, typename XF>
+template <int N, int SB, int IT, int DS, bool GR = false, typename XF>
 SM_NET_FN void network_lockstep(u32 (&S)[DS][SB], int dd0, XF xin)
 {
-    constexpr NetPlan<N, SB> P = NetPlanOf<N, SB>::value;
+    constexpr NetPlan<N, SB> P = NetPlanOf<N, SB, GR>::value;
     constexpr int NIN = 2 * N + SB, NW = P.nwires - NIN;
-    static_assert(net_planes_from_cells<N, SB>(), "every plane of S' comes out of a cell");
-    static_assert(net_min_distance<N, SB>(IT) >= IT, "a cell reads a result made fewer than IT operations before");
+    static_assert(net_planes_from_cells<N, SB, GR>(), "every plane of S' comes out of a cell");
+    static_assert(net_min_distance<N, SB, GR>(IT) >= IT, "a cell reads a result made fewer than IT operations before");
     u32 wr[IT][NW];
-    net_cells<N, SB, IT, DS, 0, NW>(S, dd0, xin, wr);
+    net_cells<N, SB, IT, DS, GR, 0, NW>(S, dd0, xin, wr);
 SM_NET_UNROLL
     for (int k = 0; k < SB; k++)
 SM_NET_UNROLL

@@ -13,7 +13,8 @@
 // at a time):
 //   x_i   = L(x+i) ^ R(x+i+d)                      mismatch bit of window column i
 //   Hx    = sum_i x_i        carry-save adder tree  (N inputs -> HB planes)
-//   Sx   += sum_i x_i(new row) - sum_i x_i(old row)   one signed carry-save network (sm_bs_network.h)
+//   Sx   += sum_i x_i(new row) - sum_i x_i(old row)   one signed carry-save network (sm_bs_network.h); of every
+//                                                   three columns it takes two x_i and the parity LX ^ RX of the three
 //   upd   = centre_match & (Sx <= B)                borrow chain of B - Sx
 //   B     = upd ? Sx : B ;  arg = upd ? d : arg     v_bitop3 selects
 // Scores are kept as MISMATCH counts: the reference's score is
@@ -489,11 +490,40 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
     };
     // steady state: one row in and one row out, GS shifts side by side; the N entering and the N
     // leaving mismatch bits of a shift and its SB sum planes go through one signed carry-save
-    // network (sm_bs_network.h), which resolves to the new planes once
+    // network (sm_bs_network.h), which resolves to the new planes once.
+    //
+    // GROUPED (every border but the ghost one, whose taps are masked column by column): of every three
+    // window columns c, c + 1, c + 2 of a row the network takes two mismatch bits and the PARITY of the
+    // three, which is lx[c / 3] ^ rx[c + d]: lx = L_c ^ L_c+1 ^ L_c+2 once per row for all shifts, rx_u =
+    // R_u ^ R_u+1 ^ R_u+2 once per row for every (c, d) with c + d = u -- a window of 3 (G - 1) + GS values
+    // that slides along with rn[] / ro[], GS new ones per group of shifts.
+    // Taken where it saves operations as written: a slide of DS shifts saves 2 G per shift and pays 2 G for lx and
+    // 2 (RXK + DS) for rx, which is a loss of 2 without the reuse of rx from one group of GS shifts to the next (DS = 4:
+    // measured, c2 20.6 -> 21.1 us, profiles/r07/ab_groups.txt) and with a single group of columns (3 x 3, 5 x 5).  The
+    // two windows cost up to 2 * RXW registers: 19 x 19 and 21 x 21 at 8 shifts per lane would spill and keep the
+    // per-bit inputs as well (profiles/r07/resource_usage.txt).  That exception is what ONE compiler's resource report
+    // said: nothing fails at build time if another toolchain spills elsewhere, so the table is made again, and the
+    // exception derived again from it, whenever the compiler changes.
+    constexpr int G = N / 3, RXK = 3 * (G - 1), RXW = RXK + GS;
+    constexpr bool GROUPED = !GHOST && 2 * G * DS > 2 * G + 2 * (RXK + DS) && !(DS == 8 && N >= 19);
     auto slide_views = [&](const RowViews &vn, const RowViews &vo) {
         u32 rn[N + GS - 1], ro[N + GS - 1];
+        u32 lxn[G], lxo[G], rxn[RXW], rxo[RXW];
 #pragma unroll
         for (int m = 0; m < N - 1; m++) { rn[m + GS] = rview(vn, m); ro[m + GS] = rview(vo, m); }
+        if (GROUPED) {
+            SM_PIN(); SM_SYNC();
+#pragma unroll
+            for (int gq = 0; gq < G; gq++) {
+                lxn[gq] = bop<BOP_XOR3>(vn.lv[3 * gq], vn.lv[3 * gq + 1], vn.lv[3 * gq + 2]); SM_PIN();
+                lxo[gq] = bop<BOP_XOR3>(vo.lv[3 * gq], vo.lv[3 * gq + 1], vo.lv[3 * gq + 2]); SM_PIN();
+            }
+#pragma unroll
+            for (int m = 0; m < RXK; m++) {
+                rxn[m + GS] = bop<BOP_XOR3>(rn[m + GS], rn[m + GS + 1], rn[m + GS + 2]); SM_PIN();
+                rxo[m + GS] = bop<BOP_XOR3>(ro[m + GS], ro[m + GS + 1], ro[m + GS + 2]); SM_PIN();
+            }
+        }
 #pragma unroll
         for (int dd0 = 0; dd0 < DS; dd0 += GS) {
 #pragma unroll
@@ -504,9 +534,24 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
                 ro[N - 1 + m] = rview(vo, dd0 + N - 1 + m); SM_PIN();
             }
             SM_SYNC();
-            // input i < N: column i of the entering row, N + i: column i of the leaving row
-            network_lockstep<N, SB, GS, DS>(S, dd0, [&](int it, int i) -> u32 {
+            if (GROUPED) {
+#pragma unroll
+                for (int m = 0; m < RXK; m++) { rxn[m] = rxn[m + GS]; rxo[m] = rxo[m + GS]; }
+                // (the newest view an rx reads was cut at least GS operations before it)
+#pragma unroll
+                for (int m = 0; m < GS; m++) { rxn[RXK + m] = bop<BOP_XOR3>(rn[RXK + m], rn[RXK + m + 1], rn[RXK + m + 2]); SM_PIN(); }
+#pragma unroll
+                for (int m = 0; m < GS; m++) { rxo[RXK + m] = bop<BOP_XOR3>(ro[RXK + m], ro[RXK + m + 1], ro[RXK + m + 2]); SM_PIN(); }
+            }
+            // input i < N: column i of the entering row, N + i: column i of the leaving row; grouped: the
+            // third column of a group stands for the parity of the group
+            network_lockstep<N, SB, GS, DS, GROUPED>(S, dd0, [&](int it, int i) -> u32 {
                 const int col = i < N ? i : i - N;
+                if (GROUPED && col < 3 * G && col % 3 == 2) {
+                    const u32 p = (i < N ? lxn[col / 3] : lxo[col / 3]) ^ (i < N ? rxn[it + col - 2] : rxo[it + col - 2]);
+                    SM_PIN();
+                    return p;
+                }
                 const u32 l = i < N ? vn.lv[col] : vo.lv[col];
                 const u32 r = i < N ? rn[it + col] : ro[it + col];
                 const u32 x = GHOST ? bop<BOP_XOR_AND>(l, r, cvv[col]) : (l ^ r);
