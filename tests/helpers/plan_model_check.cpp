@@ -5,6 +5,7 @@
 //   plan_model_check stats     how many of the match cases reach each branch of the planner
 //   plan_model_check time      10^5 calls of each cost planner, five repetitions: ns per call
 //   plan_model_check case K N  the inputs of case N of list K (0 match, 1 cost)
+//   plan_model_check strips    the ghost-border strip kernels that some cost launch reaches, one name a line
 //
 // g++ -std=c++17 -Wall -Wextra; tests/test_plan_model_cpu.py builds and runs it.
 #include <stdlib.h>
@@ -239,6 +240,39 @@ static int time_cost()
     return 0;
 }
 
+// The strip kernel k_cost_strip<half, SSD, NS> runs behind a fast cost kernel on a ghost-border plan, NS = 1 up to 256
+// shifts and 2 beyond (sm_cost_wta, sm_cost_strip_launch).  Every window and shift count the cost mode accepts, on a few
+// sizes, batch sizes, alignments and workgroup widths, planned in sm_cost_wta's order: SAD by k_sad_pc, else k_sad_qs;
+// SSD by k_ssd_mfma.  Whatever this does not print, no plan launches (tests/golden/kernel_waivers.json).
+static int strips()
+{
+    bool reached[11][2][3] = {};
+    for (int n = 1; n <= 25; n += 2)
+        for (int D = 1; D <= 1100; D++)
+            for (const auto &sz : PLAN_SIZES)
+                for (int pairs : {1, 8, 64})
+                    for (int aligned4 = 0; aligned4 < 2; aligned4++)
+                        for (int waves : {0, 1, 2, 4}) {
+                            PlanCase c = plan_case(sz[0], sz[1], D, n, SM_GHOST, pairs, 256);
+                            c.s.opt.cost_workgroup_waves = waves;
+                            const int half = c.s.square_width / 2;
+                            if (half < 1 || half > 10) continue;
+                            SadGeom q;
+                            bool sad = sm_plan_sad_pc(c.s, pairs, aligned4 != 0, &q).family != SM_COST_KERNEL_NONE;
+                            if (!sad) sad = sm_plan_sad_qs(c.s, pairs, aligned4 != 0, &q).family != SM_COST_KERNEL_NONE;
+                            const bool ssd = sm_plan_ssd_mfma(c.s, pairs, aligned4 != 0, &q).family != SM_COST_KERNEL_NONE;
+                            const int ns = (D + 255) / 256;
+                            if (ns > 2) { if (sad || ssd) return 1; continue; }       // (sm_cost_strip_launch refuses it)
+                            reached[half][0][ns] |= sad;
+                            reached[half][1][ns] |= ssd;
+                        }
+    for (int half = 1; half <= 10; half++)
+        for (int ssd = 0; ssd < 2; ssd++)
+            for (int ns = 1; ns <= 2; ns++)
+                if (reached[half][ssd][ns]) printf("k_cost_strip<%d, %s, %d>\n", half, ssd ? "true" : "false", ns);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     const char *mode = argc > 1 ? argv[1] : "";
@@ -246,6 +280,7 @@ int main(int argc, char **argv)
     if (!strcmp(mode, "sweep")) return sweep();
     if (!strcmp(mode, "stats")) return stats();
     if (!strcmp(mode, "time")) return time_cost();
+    if (!strcmp(mode, "strips")) return strips();
     if (!strcmp(mode, "case") && argc == 4) {
         const std::vector<PlanCase> cases = atoi(argv[2]) ? plan_cost_cases() : plan_match_cases();
         const size_t i = (size_t)atoi(argv[3]);
@@ -253,6 +288,6 @@ int main(int argc, char **argv)
         print_case(cases[i]);
         return 0;
     }
-    fprintf(stderr, "usage: plan_model_check dump | sweep | stats | time | case K N\n");
+    fprintf(stderr, "usage: plan_model_check dump | sweep | stats | time | strips | case K N\n");
     return 2;
 }

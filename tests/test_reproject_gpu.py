@@ -211,8 +211,9 @@ def test_point_cloud_every_pattern_and_capacity(hip, dtype, size):
 
 
 def test_more_tiles_than_the_scan_has_lanes(hip):
-    """263168 pixels = 257 tiles: k_cloud_scan's loop runs twice and carries the first turn's sum; the dense kernel's
-    workgroups stride"""
+    """263168 pixels = 257 tiles: k_cloud_scan's loop runs twice and carries the first turn's sum.  (The dense kernel
+    takes its four-pixel path here: 65792 lanes in 257 workgroups, below the 1024 at which they begin to stride;
+    tests/test_second_turns_gpu.py has the sizes at which they do.)"""
     w, h = pp.SCAN_LOOP_SIZE
     plan = plan_for(hip, w, h, 2)
     try:

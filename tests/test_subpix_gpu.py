@@ -58,7 +58,7 @@ def check_against_definition(plan, left, right, web, cost, d, sw, mode, what):
 
 
 @pytest.mark.parametrize("d", [1, 2, 3, 64, 128, 256, 512])
-@pytest.mark.parametrize("n", [1, 3, 5, 9, 11, 15, 21, 25])
+@pytest.mark.parametrize("n", [1, 3, 5, 9, 11, 13, 15, 17, 19, 21, 23, 25])
 @pytest.mark.parametrize("cost", ["sad", "ssd"])
 @pytest.mark.parametrize("mode", ["toroidal", "ghost"])
 def test_sweep_against_the_definition(hip, mode, cost, n, d):
