@@ -575,6 +575,51 @@ int sm_sgm_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_r
 /* adds: allocates the SGM workspace now; idempotent */
 int sm_plan_reserve_sgm(sm_plan *plan);
 
+/* ---- match uniqueness: runner-up, ratio filter, confidence: PARITY UNPINNED -- *
+ * New work (no reference counterpart; the uniquenessRatio test of OpenCV's StereoBM / SGBM).  Every
+ * matcher returns how good its winner is, not by how much it won; the left-right check finds occlusions, not the
+ * ambiguous matches on repeated structure, where both searches agree on the same wrong period.  The runner-up is the
+ * best shift OUTSIDE the winner's +-1 neighbourhood (the neighbours of a true minimum are always nearly as good):
+ *   runner-up of a volume V(p, d), d = 0 .. D - 1, against a web map (1 + shift, 0 = invalid): with s = web(p),
+ *     E(p) = { d : |d - (s - 1)| >= 2 } for s in 1 .. D; for every other s (0 included; any int32 is legal) E(p) is
+ *     all of 0 .. D - 1: a pixel without a winner has no neighbourhood.
+ *     best2 = min over E(p) of V(p, d), web2 = 1 + the FIRST d of E(p) reaching it;
+ *     E(p) empty (D <= 2, or D = 3 and the winner in the middle): web2 = 0, best2 = -1 ("no rival").
+ *   sm_census_second: V = sm_census_wta's window cost A_d (same box, border rules, limits of 25 x 25 and 512 shifts);
+ *     the map is the caller's: sm_census_wta's own, a checked map, a re-search map.  With an all-zero map the call
+ *     returns sm_census_wta's web and best.
+ *   sm_sgm_wta2: V = SGM's S.  d_web / d_best / d_sub exactly as from sm_sgm_wta, d_web2 / d_best2 the runner-up of S
+ *     against that d_web; winner and runner-up in one call because S is never stored.  Left reference only.
+ *   sm_uniqueness_filter, ratio in 0 .. 100: out(p) = web(p) iff web(p) != 0 and (best2(p) < 0 or
+ *     best2(p) (100 - ratio) >= 100 best(p)), in 64-bit arithmetic; else 0.  OpenCV's rule, "no rival" kept.  ratio 0
+ *     keeps every pixel whose best2 >= best.  d_rejected: NULL or one int32 per pair, the pixels that were not 0 and
+ *     now are.  d_out may equal d_web; every other overlap is refused.  A sub map follows through sm_sub_mask.
+ *   sm_confidence -> uint8 [pairs][H][W], the cases in this order: 0 where web = 0; 255 where best2 < 0; 0 where
+ *     best2 <= best; else min(255, floor(255 (best2 - best) / best2)) in 64-bit arithmetic (best2 = 0 there means
+ *     best < 0: 255).  So 255 means "no rival" only where best > 0: a winner of cost best <= 0 with any rival of
+ *     positive cost gets 255 as well (the quotient is 1 or more).  Any int32 input is legal.
+ * Arguments are checked before any device call; a refusal names the function: a NULL plan or required pointer,
+ * census_width, the penalties and paths (sm_sgm_wta's messages), pairs, the window and shift limits, a ratio outside
+ * 0 .. 100, an output that overlaps an input image or the input map, outputs that overlap one another.  Workspace:
+ * nothing new.  sm_census_second uses the census workspace and sm_sgm_wta2 the SGM workspace, allocated and captured
+ * as for sm_census_wta and sm_sgm_wta (STREAM CAPTURE once sm_plan_reserve_census / sm_plan_reserve_sgm has been
+ * called; before, refused with SM_ERR_ARG, a message naming it, and the capture valid).  The filter and the
+ * confidence map need no workspace and can always be captured.  All calls run in `stream` order and use nothing the
+ * pipelined lanes use.                                                                                            */
+/* adds: the runner-up of the census search against d_web -> d_web2 (and, d_best2 non-NULL, its window costs) */
+int sm_census_second(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width, int pairs,
+                     const int32_t *d_web, int32_t *d_web2, int32_t *d_best2, void *stream);
+/* adds: sm_sgm_wta with the runner-up of S beside it; d_best, d_sub and d_best2 may be NULL */
+int sm_sgm_wta2(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width, int p1, int p2,
+                int paths, int pairs, int32_t *d_web, int32_t *d_best, int16_t *d_sub, int32_t *d_web2,
+                int32_t *d_best2, void *stream);
+/* adds: the ratio test -> d_out (in place allowed); d_rejected may be NULL */
+int sm_uniqueness_filter(sm_plan *plan, const int32_t *d_web, const int32_t *d_best, const int32_t *d_best2, int ratio,
+                         int pairs, int32_t *d_out, int32_t *d_rejected, void *stream);
+/* adds: the confidence map, one byte per pixel */
+int sm_confidence(sm_plan *plan, const int32_t *d_web, const int32_t *d_best, const int32_t *d_best2, int pairs,
+                  uint8_t *d_conf, void *stream);
+
 /* ---- disparity post-filters: PARITY UNPINNED ------------------------------ *
  * New work (no reference counterpart).  Two filters on the maps the calls above produce, between the
  * consistency check and step 3: cost -> check -> speckle / median -> hole filling.  Maps are [pairs][H][W] of type

@@ -175,6 +175,10 @@ _SIGNATURES = {
     "sm_sgm_wta_right": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sm_sgm_lr": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sm_plan_reserve_sgm": (_int, [_vp]),
+    "sm_census_second": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp]),
+    "sm_sgm_wta2": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sm_uniqueness_filter": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "sm_confidence": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp]),
     "sm_median_filter": (_int, [_vp, _vp, _int, _int, _int, _vp, _vp]),
     "sm_speckle_filter": (_int, [_vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sm_sub_mask": (_int, [_vp, _vp, _vp, _int, _vp]),

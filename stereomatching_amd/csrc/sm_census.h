@@ -1,6 +1,7 @@
 // sm_census.h -- shared between the translation units of the census cost mode: sm_census.hip (transform, arg-min,
-// refinement) and sm_census_near.hip (the guided re-search).  Host declarations and constants only: the kernels stay in
-// their units, and the re-search reaches the mode's argument checks and descriptors through the functions below.
+// refinement), sm_census_near.hip (the guided re-search) and sm_unique.hip (the runner-up's entry point).  Host
+// declarations and constants only: the kernels stay in their units, and the other two reach the mode's argument
+// checks, descriptors and launches through the functions below.
 #pragma once
 
 #include "sm_entry.h"
@@ -15,6 +16,10 @@ typedef unsigned long long u64;
 int sm_census_args(const sm_plan *plan, int census_width, int pairs, const char *me);
 // the arg-min over the plan's shifts from the workspace's descriptors
 int sm_census_wta_launch(const sm_plan *plan, int cw, bool mirror, int pairs, i32 *d_web, i32 *d_best, hipStream_t st);
+// the runner-up against the web map d_map (k_census_second, for sm_unique.hip): the same arg-min without the shifts
+// within one of the map's; web2 = 0 and best2 = -1 where none is left
+int sm_census_second_launch(const sm_plan *plan, int cw, int pairs, const i32 *d_map, i32 *d_web2, i32 *d_best2,
+                            hipStream_t st);
 
 // the mode as the entry driver sees it (sm_entry.h)
 struct CensusMode : sm_mode {

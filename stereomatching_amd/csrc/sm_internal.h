@@ -208,6 +208,11 @@ int sm_lr_check_launch(const sm_plan *plan, bool mirrored, const i32 *web, const
 int sm_lr_unmirror(const sm_plan *plan, int pairs, i32 *d_web_right, i32 *d_best_right, hipStream_t st);
 // sm_census.hip, for SGM: both images of `pairs` pairs into the census workspace (4-byte descriptors for c <= 5, 8 for 7)
 int sm_census_descriptors(sm_plan *plan, int cw, const uint8_t *left, const uint8_t *right, int pairs, hipStream_t st);
+// sm_sgm.hip, for sm_sgm_wta2 (sm_unique.hip): the checks every SGM entry makes besides its pointers, and the left pass
+// whose last direction (k_sgm_path_second) writes the runner-up maps beside web / best / sub (best, sub, best2: NULL ok)
+int sm_sgm_args(const sm_plan *plan, int census_width, int p1, int p2, int paths, int pairs, const char *me);
+int sm_sgm_second_pass(const sm_plan *plan, int cw, int p1, int p2, int paths, int pairs, i32 *web, i32 *best,
+                       int16_t *sub, i32 *web2, i32 *best2, hipStream_t st);
 // sm_filter.hip, for sm_sgm_lr: k_sgm_sub_mask, sub = 0 where web = 0, over n elements
 int sm_sub_mask_launch(const i32 *web, int16_t *sub, long long n, hipStream_t st);
 

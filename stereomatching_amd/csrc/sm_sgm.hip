@@ -24,6 +24,9 @@
 //                  step i + SGP_PF is loaded while step i is computed: the chain of a line is thousands of steps long,
 //                  and without that it waits on memory at every one.  d -+ 1 are ds_bpermute shifts of one lane's end
 //                  values; m_q is an in-lane min, four DPP min steps within each row of 16 lanes and four readlanes.
+//   k_sgm_path_second  LAST with a second reduction (the same text, sm_sgm_path_body.h): the keys of the shifts further
+//                  than 1 from the winner's go through sgm_wave_min once more, and the runner-up maps of DESIGN.md 22
+//                  come out beside web / best / sub.  S is still never stored.
 // (k_sgm_sub_mask, sub = 0 where the checked map is 0, is a post-filter: sm_filter.hip, sm_sub_mask_launch)
 
 
@@ -198,120 +201,14 @@ __device__ __forceinline__ i32 sgm_pick(const i32 (&v)[K], int lane, int k)
     return __builtin_amdgcn_readlane(t, lane);
 }
 
-// grid ceil(lines / 4), block 256: one line per wave
-template <int K, int MODE>
-__global__ __launch_bounds__(256) void k_sgm_path(const u16 *__restrict__ A, i32 *__restrict__ S, i32 *web, i32 *best,
-                                                  int16_t *sub, const SgmPathGeom g)
-{
-    const int lane = threadIdx.x & 63;
-    const int line = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (line >= g.lines) return;
-    const int W = g.w, H = g.h;
-    // the line's first pixel: its predecessor lies outside the image
-    int x0, y0;
-    if (g.dy == 0) {
-        y0 = line; x0 = g.dx > 0 ? 0 : W - 1;
-    } else if (g.dx == 0) {
-        x0 = line; y0 = g.dy > 0 ? 0 : H - 1;
-    } else if (line < W) {
-        x0 = line; y0 = g.dy > 0 ? 0 : H - 1;
-    } else {
-        const int j = line - W + 1;
-        x0 = g.dx > 0 ? 0 : W - 1; y0 = g.dy > 0 ? j : H - 1 - j;
-    }
-    const int lx = g.dx > 0 ? W - x0 : g.dx < 0 ? x0 + 1 : 0x7fffffff;
-    const int ly = g.dy > 0 ? H - y0 : g.dy < 0 ? y0 + 1 : 0x7fffffff;
-    const int len = min(lx, ly);
-    const long long pstep = (long long)g.dy * W + g.dx;          // pixels per step
-    const long long p0 = (long long)y0 * W + x0;
-    const int dl = lane * K;                                     // this lane's first shift
-    const u16 *a0 = A + (size_t)p0 * g.Dp + dl;
-    i32 *s0 = S + (size_t)p0 * g.Dp + dl;
-    const long long vstep = pstep * g.Dp;
-
-    i32 ar[SGP_PF][K], sr[SGP_PF][K];
-    auto load = [&](int i, i32 (&av)[K], i32 (&sv)[K]) {
-        SgmVec<K>::load_a(a0 + i * vstep, av);
-        if (MODE != SGM_FIRST) SgmVec<K>::load_s(s0 + i * vstep, sv);
-    };
-#pragma unroll
-    for (int j = 0; j < SGP_PF; j++)
-        if (j < len) load(j, ar[j], sr[j]);
-
-    i32 L[K];
-    i32 m = 0;
-    const i32 P1 = g.p1, P2 = g.p2;
-    for (int base = 0; base < len; base += SGP_PF) {
-#pragma unroll
-        for (int j = 0; j < SGP_PF; j++) {
-            const int i = base + j;
-            if (i >= len) break;
-            i32 av[K], sv[K];
-#pragma unroll
-            for (int k = 0; k < K; k++) { av[k] = ar[j][k]; sv[k] = sr[j][k]; }
-            if (i + SGP_PF < len) load(i + SGP_PF, ar[j], sr[j]);
-            if (i == 0) {
-#pragma unroll
-                for (int k = 0; k < K; k++) L[k] = dl + k < g.D ? av[k] : SGM_INF;
-            } else {
-                i32 lo = __shfl_up(L[K - 1], 1), hi = __shfl_down(L[0], 1);   // L(q, d - 1) of entry 0, L(q, d + 1) of K - 1
-                if (lane == 0) lo = SGM_INF;
-                if (lane == 63) hi = SGM_INF;
-                const i32 jump = m + P2;
-                i32 nl[K];
-#pragma unroll
-                for (int k = 0; k < K; k++) {
-                    const i32 dm = k == 0 ? lo : L[k - 1], dp = k == K - 1 ? hi : L[k + 1];
-                    const i32 t = min(min(L[k], min(dm, dp) + P1), jump);
-                    nl[k] = dl + k < g.D ? av[k] + t - m : SGM_INF;
-                }
-#pragma unroll
-                for (int k = 0; k < K; k++) L[k] = nl[k];
-            }
-            i32 lm = L[0];
-#pragma unroll
-            for (int k = 1; k < K; k++) lm = min(lm, L[k]);
-            m = sgm_wave_min(lm);
-
-            if (MODE == SGM_FIRST) {
-                SgmVec<K>::store_s(s0 + i * vstep, L);
-            } else if (MODE == SGM_MID) {
-                i32 t[K];
-#pragma unroll
-                for (int k = 0; k < K; k++) t[k] = sv[k] + L[k];
-                SgmVec<K>::store_s(s0 + i * vstep, t);
-            } else {
-                // S <= 8 * 62767 < 2^19: keys S << 8 | d, the first d wins a tie; entries d >= D lose to every real one
-                // (S = 8 * 62767 and a padded range: tests/test_census_extremes_gpu.py test_sgm_at_its_u16_and_key_bounds)
-                i32 tot[K], key = 0x7fffffff;
-#pragma unroll
-                for (int k = 0; k < K; k++) {
-                    tot[k] = sv[k] + L[k];
-                    if (dl + k < g.D) key = min(key, (tot[k] << 8) | (dl + k));
-                }
-                key = sgm_wave_min(key);
-                const int s = (key & 0xff) + 1;
-                const i32 b = key >> 8;
-                int16_t q16 = (int16_t)(16 * s);
-                if (sub && s > 1 && s < g.D) {
-                    const i32 sm2 = sgm_pick<K>(tot, (s - 2) / K, (s - 2) % K);
-                    const i32 sp = sgm_pick<K>(tot, s / K, s % K);
-                    const i32 a = sm2 - b, c = sp - b, den = a + c;
-                    int q = 0;
-                    if (den > 0) q = min(8, max(-8, smn_floordiv(16 * (a - c) + den, 2 * den)));
-                    q16 = (int16_t)(16 * s + q);
-                }
-                if (lane == 0) {
-                    const int x = x0 + i * g.dx, y = y0 + i * g.dy;
-                    const size_t o = (size_t)g.map + (size_t)y * W + (g.mirror ? W - 1 - x : x);
-                    web[o] = s;
-                    if (best) best[o] = b;
-                    if (sub) sub[o] = q16;
-                }
-            }
-        }
-    }
-}
+// k_sgm_path<K, MODE> and k_sgm_path_second<K>: one text, sm_sgm_path_body.h, expanded twice (as in sm_census.hip: the
+// existing kernels' tokens are what they were, and so are their instructions and register counts)
+#define SGM_SECOND 0
+#include "sm_sgm_path_body.h"
+#undef SGM_SECOND
+#define SGM_SECOND 1
+#include "sm_sgm_path_body.h"
+#undef SGM_SECOND
 
 // ---------------------------------------------------------------------------
 // host side
@@ -385,8 +282,9 @@ static const void *sgm_path_ptr(int mode)
 }
 
 // the directions in stream order (integer sums: the order changes nothing); the last one emits the maps
+// (web2: the last direction is k_sgm_path_second, which writes the runner-up maps as well)
 static int sgm_paths_launch(const sm_plan *plan, int p1, int p2, int paths, bool mirror, int pair, i32 *web, i32 *best,
-                            int16_t *sub, hipStream_t st)
+                            int16_t *sub, i32 *web2, i32 *best2, hipStream_t st)
 {
     static const int dirs[8][2] = {{1, 0}, {0, 1}, {1, 1}, {-1, 1}, {1, -1}, {-1, -1}, {0, -1}, {-1, 0}};
     static const int four[4] = {0, 1, 6, 7};
@@ -406,21 +304,41 @@ static int sgm_paths_launch(const sm_plan *plan, int p1, int p2, int paths, bool
         const void *fn = K == 1 ? sgm_path_ptr<1>(mode) : K == 2 ? sgm_path_ptr<2>(mode) : sgm_path_ptr<4>(mode);
         // (paths >= 4: the last direction is never the first, so S always holds the other directions' sum)
         void *args[] = {(void *)&A, (void *)&S, (void *)&web, (void *)&best, (void *)&sub, (void *)&g};
-        const hipError_t e = hipLaunchKernel(fn, dim3((g.lines + 3) / 4), dim3(256), args, 0, st);
-        if (e != hipSuccess) return sm_fail(SM_ERR_HIP, "launch of k_sgm_path failed: %s", hipGetErrorString(e));
+        void *args_second[] = {(void *)&A, (void *)&S, (void *)&web, (void *)&best, (void *)&sub, (void *)&web2,
+                               (void *)&best2, (void *)&g};
+        const bool second = web2 && mode == SGM_LAST;
+        if (second)
+            fn = K == 1 ? (const void *)k_sgm_path_second<1> : K == 2 ? (const void *)k_sgm_path_second<2>
+                                                                      : (const void *)k_sgm_path_second<4>;
+        const hipError_t e = hipLaunchKernel(fn, dim3((g.lines + 3) / 4), dim3(256), second ? args_second : args, 0, st);
+        if (e != hipSuccess)
+            return sm_fail(SM_ERR_HIP, "launch of %s failed: %s", second ? "k_sgm_path_second" : "k_sgm_path",
+                           hipGetErrorString(e));
     }
     return SM_OK;
 }
 
 // the left (or right-reference) SGM maps of `pairs` pairs, one pair at a time through the volumes
 static int sgm_pass(const sm_plan *plan, int cw, int p1, int p2, int paths, bool mirror, int pairs, i32 *web, i32 *best,
-                    int16_t *sub, hipStream_t st)
+                    int16_t *sub, hipStream_t st, i32 *web2 = nullptr, i32 *best2 = nullptr)
 {
     for (int q = 0; q < pairs; q++) {
         SM_TRY(sgm_cost_launch(plan, cw, mirror, q, st));
-        SM_TRY(sgm_paths_launch(plan, p1, p2, paths, mirror, q, web, best, sub, st));
+        SM_TRY(sgm_paths_launch(plan, p1, p2, paths, mirror, q, web, best, sub, web2, best2, st));
     }
     return SM_OK;
+}
+
+// for sm_unique.hip (sm_sgm_wta2): the checks of every SGM entry, and the left pass with the runner-up maps
+int sm_sgm_args(const sm_plan *plan, int census_width, int p1, int p2, int paths, int pairs, const char *me)
+{
+    return sgm_args(plan, census_width, p1, p2, paths, pairs, me);
+}
+
+int sm_sgm_second_pass(const sm_plan *plan, int cw, int p1, int p2, int paths, int pairs, i32 *web, i32 *best,
+                       int16_t *sub, i32 *web2, i32 *best2, hipStream_t st)
+{
+    return sgm_pass(plan, cw, p1, p2, paths, false, pairs, web, best, sub, st, web2, best2);
 }
 
 // the mode as the entry driver sees it (sm_entry.h)

@@ -540,6 +540,59 @@ class StereoPlan:
             lib.sm_sgm_lr, lambda pairs: (int(census), int(p1), int(p2), int(paths), pairs), left, right, max_diff,
             want_right, want_best, web, web_right, best, want_sub=want_sub, sub=sub))
 
+    # ---- match uniqueness: runner-up, ratio filter, confidence ---------------------
+    def census_second(self, left, right, web, census=7, want_best=True, web2=None, best2=None):
+        """The runner-up of the census search (sm_census_second) -> (web2, best2): census_wta's arg-min over the shifts
+        further than 1 from the shift of the int32 map `web` (1 + shift; 0 and anything outside 1..D: over all shifts);
+        web2 = 0 and best2 = -1 where no shift is left.  `web` may be census_wta's own map, a checked map, a re-search
+        map."""
+        left, right, pairs = self._pair(left, right)
+        web = self._prior(web, pairs, "web")
+        web2 = self._out(web2, pairs, "web2")
+        best2 = self._out(best2, pairs, "best2") if want_best else None
+        check(lib.sm_census_second(self._h, _ptr(left), _ptr(right), int(census), pairs, _ptr(web), _ptr(web2),
+                                   _ptr(best2), self._stream()))
+        return web2, best2
+
+    def sgm_wta2(self, left, right, census=7, p1=10, p2=120, paths=8, want_best=True, want_sub=False, want_best2=True,
+                 web=None, best=None, sub=None, web2=None, best2=None):
+        """sgm_wta with the runner-up of the aggregate beside it (sm_sgm_wta2) -> (web, best, sub, web2, best2): the
+        first three exactly as sgm_wta gives them, web2 / best2 the arg-min of S over the shifts further than 1 from
+        the winner's (web2 = 0, best2 = -1 where there is none).  Outputs not wanted are None."""
+        left, right, pairs = self._pair(left, right)
+        web = self._out(web, pairs, "web")
+        best = self._out(best, pairs, "best") if want_best else None
+        sub = self._out(sub, pairs, "sub", torch.int16) if want_sub else None
+        web2 = self._out(web2, pairs, "web2")
+        best2 = self._out(best2, pairs, "best2") if want_best2 else None
+        check(lib.sm_sgm_wta2(self._h, _ptr(left), _ptr(right), int(census), int(p1), int(p2), int(paths), pairs,
+                              _ptr(web), _ptr(best), _ptr(sub), _ptr(web2), _ptr(best2), self._stream()))
+        return web, best, sub, web2, best2
+
+    def _unique_maps(self, web, best, best2):
+        web = self._images(web, torch.int32, "web")
+        pairs = web.shape[0]
+        return web, self._prior(best, pairs, "best"), self._prior(best2, pairs, "best2"), pairs
+
+    def uniqueness_filter(self, web, best, best2, ratio, out=None, want_rejected=False):
+        """The uniqueness test (sm_uniqueness_filter) -> the filtered map, or (map, rejected pixels per pair) with
+        want_rejected: a valid pixel stays iff it has no rival (best2 < 0) or best2 * (100 - ratio) >= best * 100,
+        ratio in 0..100 (OpenCV's uniquenessRatio).  out=web filters in place; sub_mask lets a sub map follow."""
+        web, best, best2, pairs = self._unique_maps(web, best, best2)
+        out = self._out(out, pairs, "out")
+        rejected = torch.empty(pairs, dtype=torch.int32, device=self._dev) if want_rejected else None
+        check(lib.sm_uniqueness_filter(self._h, _ptr(web), _ptr(best), _ptr(best2), int(ratio), pairs, _ptr(out),
+                                       _ptr(rejected), self._stream()))
+        return (out, rejected) if want_rejected else out
+
+    def confidence(self, web, best, best2, out=None):
+        """Per-pixel confidence (sm_confidence) -> uint8 map: 0 where web = 0, 255 where there is no rival, 0 where
+        best2 <= best, else min(255, 255 * (best2 - best) // best2)."""
+        web, best, best2, pairs = self._unique_maps(web, best, best2)
+        out = self._out(out, pairs, "out", torch.uint8)
+        check(lib.sm_confidence(self._h, _ptr(web), _ptr(best), _ptr(best2), pairs, _ptr(out), self._stream()))
+        return out
+
     # ---- disparity post-filters (between the check and step 3) ------------------
     def reserve_filter(self):
         """The speckle filter's workspace (a label and a component size per pixel of max_pairs maps), allocated now:

@@ -1,0 +1,187 @@
+"""Match uniqueness on the CPU: the numpy definition (tests/unique_reference.py) against a pixel-by-pixel restatement,
+its identities, and what the cases of tests/unique_patterns.py can tell -- asserted here, so that a pass of
+test_unique_gpu.py on them means something."""
+import numpy as np
+import pytest
+
+from stereomatching_amd.synth import make_pair
+from tests import census_reference as cr
+from tests import unique_patterns as up
+from tests import unique_reference as ur
+
+MODES = ["toroidal", "ghost"]
+
+
+# ---------------------------------------------------------------------------
+# the vectorised definition against the loops
+# ---------------------------------------------------------------------------
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("census", [3, 5, 7])
+@pytest.mark.parametrize("n", [1, 3])
+def test_runner_up_equals_the_pixel_loop(mode, census, n):
+    w, h = 11, 7
+    rng = np.random.default_rng(census * 10 + n)
+    left, right = (rng.integers(0, 256, (h, w)).astype(np.uint8) for _ in range(2))
+    for D in (1, 2, 3, 5):
+        vol = ur.census_volume(left, right, D, n, census, mode)
+        best, web = cr.wta(left, right, D, n, census, mode)
+        assert np.array_equal(vol.min(axis=-1), best) and np.array_equal(vol.argmin(axis=-1) + 1, web)
+        maps = [web, np.zeros_like(web), up.sweep(w, h, D), rng.integers(-2, D + 3, (h, w)).astype(np.int32),
+                rng.choice(np.array([up.I32_MIN, up.I32_MAX, 0, 1, D], np.int64), (h, w)).astype(np.int32)]
+        for m in maps:
+            got = ur.census_second(left, right, m, D, n, census, mode)
+            want = ur.runner_up_bruteforce(vol, m)
+            assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), (D, m[0, :4])
+            assert got[0].dtype == np.int32 and got[1].dtype == np.int32
+
+
+def test_filter_and_confidence_equal_the_pixel_loop():
+    web, best, best2 = up.extremes()
+    for ratio in up.RATIOS + [1, 50, 99]:
+        got = ur.uniqueness_filter(web, best, best2, ratio)
+        want = ur.uniqueness_filter_bruteforce(web, best, best2, ratio)
+        assert np.array_equal(got[0], want[0]) and got[1] == want[1], ratio
+    assert np.array_equal(ur.confidence(web, best, best2), ur.confidence_bruteforce(web, best, best2))
+    rng = np.random.default_rng(1)
+    web, best, best2 = (rng.integers(-3, 40, (9, 13)).astype(np.int32) for _ in range(3))
+    assert np.array_equal(ur.confidence(web, best, best2), ur.confidence_bruteforce(web, best, best2))
+    assert np.array_equal(ur.uniqueness_filter(web, best, best2, 15)[0],
+                          ur.uniqueness_filter_bruteforce(web, best, best2, 15)[0])
+    # every value of the confidence's last case, by hand: best2 = 1000
+    b = np.arange(0, 1001, dtype=np.int32)
+    c = ur.confidence(np.ones_like(b), b, np.full_like(b, 1000))
+    assert c[0] == 255 and c[1] == 254 and c[4] == 253 and c[500] == 127 and c[999] == 0 and c[1000] == 0
+
+
+# ---------------------------------------------------------------------------
+# identities
+# ---------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", list(up.CENSUS_CASES))
+def test_census_identities(name):
+    c, e = up.CENSUS_CASES[name], up.census_case(name)
+    # a zero map gives census_wta
+    assert np.array_equal(e["second"]["zeros"][0], e["best"]) and np.array_equal(e["second"]["zeros"][1], e["web"])
+    for q in range(up.PAIRS):
+        best, web = cr.wta(e["left"][q], e["right"][q], c["d"], c["sw"], c["census"], c["mode"])
+        assert np.array_equal(best, e["best"][q]) and np.array_equal(web, e["web"][q])
+    # against the volume's own winner the runner-up is never better, and never in the winner's neighbourhood
+    best2, web2 = e["second"]["own"]
+    has = web2 != 0
+    assert (best2[has] >= e["best"][has]).all() and (best2[~has] == -1).all()
+    assert (np.abs(web2[has] - e["web"][has]) >= 2).all()
+    # against any map: web2 is 0 or a shift of the plan, further than 1 from the map's
+    for kind in up.MAPS:
+        b2, w2 = e["second"][kind]
+        m = e["maps"][kind].astype(np.int64)
+        assert ((w2 >= 0) & (w2 <= c["d"])).all() and ((w2 == 0) == (b2 == -1)).all()
+        assert (np.abs(w2 - m)[(w2 != 0) & (m >= 1) & (m <= c["d"])] >= 2).all()
+
+
+@pytest.mark.parametrize("case", up.FILTER_CASES, ids=up.filter_id)
+def test_filter_identities(case):
+    web, best, best2, *_ = up.filter_inputs(case)
+    valid = web != 0
+    if case[2] != "checked":
+        # (a checked map's best2 is the runner-up against the map with its 0s, where the winner itself may return)
+        assert (best2[valid & (best2 >= 0)] >= best[valid & (best2 >= 0)]).all()
+    out0, rej0 = ur.uniqueness_filter(web, best, best2, 0)
+    assert np.array_equal(out0, web) and rej0 == 0                     # ratio 0 keeps all
+    kept = valid
+    for ratio in range(0, 101, 5):
+        out, rej = ur.uniqueness_filter(web, best, best2, ratio)
+        k = out != 0
+        assert np.array_equal(out[k], web[k]) and (k <= kept).all() and rej == int(valid.sum() - k.sum()), ratio
+        kept = k                                                       # the kept set shrinks monotonically
+    assert (ur.confidence(web, best, best2)[~valid] == 0).all()
+
+
+def test_confidence_is_255_exactly_where_there_is_no_rival():
+    """on non-negative costs with best > 0 (every census and SGM map of a textured pair): among the valid pixels the
+    confidence is 255 iff best2 < 0"""
+    seen = 0
+    for case in up.FILTER_CASES:
+        web, best, best2, *_ = up.filter_inputs(case)
+        valid = (web != 0) & (best > 0)
+        conf = ur.confidence(web, best, best2)
+        assert np.array_equal(conf[valid] == 255, best2[valid] < 0), case
+        seen += int((best2[valid] < 0).sum())
+    assert seen > 500
+
+
+# ---------------------------------------------------------------------------
+# what the GPU cases can tell
+# ---------------------------------------------------------------------------
+
+# Toroidal with more shifts than columns: A_(d + W) = A_d, so the winner's cost returns W shifts away, outside its
+# neighbourhood: best2 = best at (nearly) every pixel, and every ratio above 0 rejects them.
+PERIODIC = {"64x16 D130"}
+
+
+@pytest.mark.parametrize("case", up.FILTER_CASES, ids=up.filter_id)
+def test_the_filter_cases_reject_some_and_keep_some(case):
+    mode, name, kind = case
+    web, best, best2, w, h, d = up.filter_inputs(case)
+    valid = int((web != 0).sum())
+    rates = {r: ur.uniqueness_filter(web, best, best2, r)[1] / valid for r in up.RATIOS}
+    if d <= 3:
+        assert (best2[web != 0] < 0).any()                             # the pixels without a rival
+        if d <= 2:
+            assert (best2 == -1).all() and all(v == 0 for v in rates.values())
+        return
+    assert (best2 >= 0).all()
+    if mode == "census" and name in PERIODIC:
+        assert (best2[web != 0] == best[web != 0]).mean() > 0.95 and rates[0] == 0 and rates[5] > 0.95
+        return
+    for r in (5, 15, 30):                                              # own maps and checked maps alike
+        assert 0.05 <= rates[r] <= 0.95, (r, rates)
+
+
+def test_the_case_sets_hold_pixels_without_a_rival():
+    for cases in (up.CENSUS_CASES, up.SGM_CASES):
+        few = [n for n, c in cases.items() if c["d"] <= 3]
+        assert {cases[n]["d"] for n in few} >= {2, 3}
+    e = up.census_case("20x9 D3")
+    b2 = e["second"]["own"][0]
+    assert (b2 == -1).any() and (b2 >= 0).any()                        # the winner in the middle, and at an end
+    assert np.array_equal(b2 == -1, e["web"] == 2)
+    s = up.sgm_case("20x9 D3")
+    assert (s["best2"] == -1).any() and (s["best2"] >= 0).any()
+    assert (up.sgm_case("20x9 D2")["web2"] == 0).all()
+
+
+def test_the_sweep_reaches_every_value_and_the_end_of_a_launch():
+    for name, c in up.CENSUS_CASES.items():
+        m = up.census_case(name)["maps"]["sweep"]
+        if m.size >= 2 * (c["d"] + 3):
+            assert set(np.unique(m)) == set(range(-1, c["d"] + 2)), name
+    # D = 130: the second launch holds shifts 128 and 129 and six padded ones beside them.  A map shift of 128 or 129
+    # excludes padded shift 130 as well (excluded AND out of range), at every column of a lane's four; 126 .. 129
+    # straddle the two launches
+    m = up.census_case("64x16 D130")["maps"]["sweep"]
+    x = np.broadcast_to(np.arange(m.shape[-1]), m.shape)
+    for shift in (126, 127, 128, 129):
+        assert {int(v) for v in x[m - 1 == shift] % 4} == {0, 1, 2, 3}, shift
+    m = up.census_case("64x8 D260")["maps"]["sweep"]
+    assert all((m - 1 == s).any() for s in (127, 128, 255, 256, 258, 259))
+
+
+@pytest.mark.parametrize("name", list(up.SGM_K))
+def test_sgm_winners_lie_on_both_edges_of_a_lane(name):
+    K, e = up.SGM_K[name], up.sgm_case(name)
+    d, d2 = e["web"].astype(np.int64) - 1, e["web2"].astype(np.int64) - 1
+    assert (e["web2"] != 0).all() and (np.abs(d2 - d) >= 2).all() and (e["best2"] >= e["best"]).all()
+    if K > 1:
+        assert (d % K == 0).sum() > 100 and (d % K == K - 1).sum() > 100
+    assert (d // K != d2 // K).sum() > 100                             # the runner-up in another lane than the winner
+    assert (d // K == d2 // K).any() or K < 4                          # ... and, four shifts a lane, in the same one
+    if name.endswith("K4"):
+        assert up.SGM_CASES[name]["d"] % 64 != 0                       # a padded range: lanes past D hold no shift
+
+
+def test_sgm_case_is_make_pair_seed_7():
+    c = up.SGM_CASES["70x20 D24 K1"]
+    left, right = make_pair(c["w"], c["h"], c["d"], seed=7)
+    e = up.sgm_case("70x20 D24 K1")
+    assert np.array_equal(e["left"][0], left) and np.array_equal(e["right"][0], right)

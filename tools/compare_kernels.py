@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Compare the gfx950 kernels and the exported C symbols of two builds of libstereo_hip.so.
 
-    python tools/compare_kernels.py OLD.so NEW.so
+    python tools/compare_kernels.py [--allow-added] OLD.so NEW.so
 
+--allow-added: for a change that adds kernels and entry points beside the existing ones: only OLD's symbols are compared
+(what NEW has besides them is not a difference, and the counts of NEW in the summary line are of those symbols).
 For a change that must not touch any kernel (a refactor, a new stage beside the existing ones).  Kernels are compared
 per SYMBOL, not per file, so a kernel may move to another translation unit (another code object): every gfx950 code
 object of each library is extracted from its .hip_fatbin section and disassembled, the listing is split at function
@@ -115,13 +117,19 @@ def survey(lib: Path, tmp: Path):
 
 
 def main() -> int:
-    if len(sys.argv) != 3:
+    added_ok = "--allow-added" in sys.argv
+    args = [a for a in sys.argv[1:] if a != "--allow-added"]
+    if len(args) != 2:
         print(__doc__)
         return 2
-    old, new = Path(sys.argv[1]), Path(sys.argv[2])
+    old, new = Path(args[0]), Path(args[1])
     with tempfile.TemporaryDirectory() as t:
         n_old, f_old, r_old, e_old = survey(old, Path(t))
         n_new, f_new, r_new, e_new = survey(new, Path(t))
+    if added_ok:                                        # a new stage: only OLD's symbols are compared
+        f_new = {k: v for k, v in f_new.items() if k in f_old}
+        r_new = {k: v for k, v in r_new.items() if k in r_old}
+        e_new &= e_old
     bad = 0
     for name in sorted(set(f_old) | set(f_new)):
         if name not in f_new:

@@ -29,7 +29,11 @@ tracer's own lines: the kernels are recorded all the same, and a failed test doe
 FILE or as tests/test_x_gpu.py=FILE (without the prefix the test file is tests/<stem of FILE>.py),
 and REPLACES the entries of the test files it is given; entries of other test files stay.  A test
 file killed at its limit only because tracing slows it gets a longer limit or is split with -k; it
-is not retried in a loop.  `missing` prints the inventory's kernels that no test file launches,
+is not retried in a loop.  A stage added later keeps the
+traces of its own GPU test files in a record of its own beside the first one, tests/golden/
+kernel_dispatches_mi355x.<stage>.json.gz (`merge --record THAT_FILE tests/test_<stage>_gpu.py=FILE`): load() adds
+every such supplement to the record it returns, so the coverage test sees them, and the first record's bytes change
+only when the test files recorded in it are traced again.  `missing` prints the inventory's kernels that no test file launches,
 by family (profiles/coverage/never_launched.txt is its output at the commit named there).
 """
 from __future__ import annotations
@@ -64,11 +68,27 @@ def names_of(path: Path) -> set[str]:
     return {normalise(line) for line in path.read_text().splitlines() if line.strip()}
 
 
-def load(path: Path = RECORD) -> dict:
+def supplements(path: Path = RECORD) -> list[Path]:
+    """the records beside `path` that add to it: kernel_dispatches_mi355x.<stage>.json.gz for ...mi355x.json.gz"""
+    stem = path.name[:-len(".json.gz")]
+    return sorted(p for p in path.parent.glob(stem + ".*.json.gz") if p != path)
+
+
+def _load_one(path: Path) -> dict:
     if not path.exists():
         return {"head": "", "kernels": {}}
     with gzip.open(path, "rt") as f:
         return json.load(f)
+
+
+def load(path: Path = RECORD, with_supplements: bool = True) -> dict:
+    """the record at `path`, by default with the test files of its supplements added to each kernel's list"""
+    rec = _load_one(path)
+    if with_supplements:
+        for extra in supplements(path):
+            for k, tests in _load_one(extra)["kernels"].items():
+                rec["kernels"][k] = sorted(set(rec["kernels"].get(k, [])) | set(tests))
+    return rec
 
 
 def save(rec: dict, path: Path = RECORD) -> None:
@@ -122,7 +142,8 @@ def main(argv) -> int:
         return 0
     known = set(inventory(Path(opts["--lib"]) if "--lib" in opts else None))
     record = Path(opts.get("--record", RECORD))
-    rec = load(record)
+    # merge rewrites one file: what its supplements hold stays in them
+    rec = load(record, with_supplements=cmd != "merge")
     if cmd == "merge":
         traced = {}
         for a in args:
