@@ -45,6 +45,10 @@
 #define SM_BS_CAT(a, b) SM_BS_CAT2(a, b)
 
 #define SM_BS_WAVES 2   // min waves per SIMD: keeps VGPR + AGPR <= 256 (one AGPR more halves the occupancy)
+// staging loads a thread has in flight at once, left + right image: C3's tile (40 rows of 10 + 16 words, 128 threads:
+// 3.1 and 5 words per thread) is one chunk of each
+#define SM_STAGE_CH_L 4
+#define SM_STAGE_CH_R 5
 
 // Diagnostic build only (-DSM_STAMPS, tools/wave_timeline.py): every wave records
 // when it started, finished staging, finished its warm-up rows and ended (constant
@@ -278,6 +282,63 @@ __device__ __forceinline__ void add_lockstep(u32 (&S)[DS][SB], int dd0, const u3
 
 template <int V> struct IntTag { static constexpr int value = V; };
 
+// ---------------------------------------------------------------------------
+// Staging: `nrow` rows of `rw` words, row r at src + r * stride, to dst[r * rw + k], by T threads.  Element
+// e = r * rw + k belongs to thread e % T, so consecutive threads load consecutive words of a row and a thread's
+// word of dst is e itself.  A thread's loads do not depend on each other: issue() sends CH of them back to back,
+// which costs ONE round trip to memory, and write() stores them afterwards, each waiting only for its own value
+// (the compiler counts vmcnt down).  Written as load - write - load - write, the compiler waited for every value
+// before the next load left: five dependent round trips for the 9 words a thread stages at C3.
+// Nothing is divided per element: (k, word of src) of e + T follow from those of e, and the first e = thread
+// index < T is split with a float reciprocal -- (int)((e + 0.5f) * (1.0f / rw)) is e / rw while rw <= 4096 and
+// e <= 128 (the product is off by at most 1.5e-5, and at least 0.5 / rw away from the next integer).
+// LAST: the rows' last chunk, the only one in which a thread can be without an element.  Such a thread stages
+// element 0 once more -- the same value to the same word as thread 0 -- so it forms no address of its own, and
+// neither the loads nor the stores stand under a branch (a branch per element would put the waits back).
+// ---------------------------------------------------------------------------
+template <int T, int CH>
+struct RowStager {
+    const u32 *src;
+    u32 *dst;
+    int rw, total, step_k, step_from, wrap_from;
+    int e, k, from;         // this thread's next element: its index, its word of the row, its word of src
+    u32 v[CH];
+    __device__ __forceinline__ RowStager(const u32 *src_, int stride, u32 *dst_, int nrow, int rw_)
+        : src(src_), dst(dst_), rw(rw_), total(nrow * rw_)
+    {
+        const float inv = __builtin_amdgcn_rcpf((float)rw);
+        const int t_row = (int)(((float)T + 0.5f) * inv), row = (int)(((float)threadIdx.x + 0.5f) * inv);
+        step_k = T - t_row * rw;
+        step_from = t_row * stride + step_k;
+        wrap_from = stride - rw;
+        e = (int)threadIdx.x;
+        k = e - row * rw;
+        from = row * stride + k;
+    }
+    // a full chunk remains in front of the last one
+    __device__ __forceinline__ bool more() const { return e - (int)threadIdx.x + T * CH < total; }
+    template <typename Tag>
+    __device__ __forceinline__ void issue(Tag)
+    {
+#pragma unroll
+        for (int j = 0; j < CH; j++) {
+            v[j] = src[Tag::value && e >= total ? 0 : from];
+            e += T; k += step_k; from += step_from;
+            if (k >= rw) { k -= rw; from += wrap_from; }
+        }
+    }
+    // the chunk issued last
+    template <typename Tag>
+    __device__ __forceinline__ void write(Tag) const
+    {
+#pragma unroll
+        for (int j = 0; j < CH; j++) {
+            const int ej = e - (CH - j) * T;
+            dst[Tag::value && ej >= total ? 0 : ej] = v[j];
+        }
+    }
+};
+
 template <int CTRL>
 __device__ __forceinline__ u32 dpp(u32 v)
 {
@@ -382,24 +443,21 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
     const int ty0 = tile_y * (DUO ? 2 * g.tile_h : g.tile_h);
     const int plw = g.plw, prw = g.prw, nsr = g.nsr;
     const u32 *extL = ext + (size_t)pair * 2 * g.ext_image_words;
-    const u32 *extR = extL + g.ext_image_words;
     u32 *pL = lds;                  // [nsr][plw]
     u32 *pR = pL + nsr * plw;       // [nsr][prw]
 
-    // ---- stage the tile's rows (+ window halo): coalesced dword row loads
-    {
-        const int wx0 = tx0 >> 5;
-        const int per_row = plw + prw;
-        for (int it = threadIdx.x; it < nsr * per_row; it += DUO ? 128 : 64) {
-            const int row = it / per_row, k = it - row * per_row;
-            const bool is_r = k >= plw;
-            const int kk = is_r ? k - plw : k;
-            const u32 v = (is_r ? extR : extL)[(size_t)(ty0 + row) * g.ext_words + wx0 + kk];
-            if (is_r) pR[row * prw + kk] = v; else pL[row * plw + kk] = v;
-        }
-    }
-    __syncthreads();
-    SM_STAMP(1);
+    // ---- stage the tile's rows (+ window halo): coalesced dword row loads, SM_STAGE_CH_L + SM_STAGE_CH_R of them
+    // in flight per thread (RowStager); C3's tile is one chunk of each image
+    constexpr int T = DUO ? 128 : 64;
+    const u32 *rowsL = extL + (size_t)ty0 * g.ext_words + (tx0 >> 5);
+    RowStager<T, SM_STAGE_CH_L> stL(rowsL, g.ext_words, pL, nsr, plw);
+    RowStager<T, SM_STAGE_CH_R> stR(rowsL + g.ext_image_words, g.ext_words, pR, nsr, prw);
+    // (shapes with more staged words than one chunk: large windows, one-wave workgroups, tall tiles)
+    while (stL.more()) { stL.issue(IntTag<0>{}); stL.write(IntTag<0>{}); }
+    stL.issue(IntTag<1>{});
+    while (stR.more()) { stR.issue(IntTag<0>{}); stR.write(IntTag<0>{}); }
+    stR.issue(IntTag<1>{});
+    // ... and while the last loads are under way, what does not depend on them: the lane's role, its masks, its sums
 
     // ---- lane role
     const int s = tid & (g.nl - 1);           // which 16 shifts
@@ -436,7 +494,17 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
 #pragma unroll
     for (int dd = 0; dd < DS; dd++)
 #pragma unroll
-        for (int k = 0; k < SB; k++) S[dd][k] = 0;
+        for (int k = 0; k < SB; k++) {
+            S[dd][k] = 0;
+            // (zeroed HERE, under the staging loads: left to itself the compiler zeroes the planes behind the barrier)
+            asm volatile("" : "+v"(S[dd][k]));
+        }
+
+    SM_PIN();
+    stL.write(IntTag<1>{});
+    stR.write(IntTag<1>{});
+    __syncthreads();
+    SM_STAMP(1);
 
     // the views one window row contributes: N pre-shifted words of the left row and
     // the three words the right row's sliding views are cut from
