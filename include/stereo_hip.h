@@ -575,6 +575,49 @@ int sm_sgm_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_r
 /* adds: allocates the SGM workspace now; idempotent */
 int sm_plan_reserve_sgm(sm_plan *plan);
 
+/* ---- banded SGM: semi-global aggregation within +-r of a prior map: PARITY UNPINNED -- *
+ * New work (no reference counterpart; the tSGM idea of coarse-to-fine SGM pipelines).  The guided
+ * re-search above with SGM's smoothness term: the last step of the half-resolution path becomes coarse SGM, upsample,
+ * fine SGM in a band.  Arguments as sm_sgm_wta's (census_width, p1, p2, paths) and sm_census_wta_near's (d_prior,
+ * radius r in 1..4; any int32 is a legal prior).  Definition:
+ *   K(p)      = sm_census_wta_near's: { d : 0 <= d <= D - 1, |d - (prior(p) - 1)| <= r }, empty for prior(p) = 0;
+ *   A(p, d)   = sm_census_wta's window cost, d in K(p) (all n x n taps with p's own d);
+ *   L_r(p, d) = A(p, d) if q = p - r lies outside the image (paths never wrap) or K(q) is empty (a pixel without a
+ *               band breaks the path, which restarts after it), else
+ *               A(p, d) + min(L_r(q, d), L_r(q, d-1) + p1, L_r(q, d+1) + p1, m_q + p2) - m_q, m_q = min over K(q) of
+ *               L_r(q, k), terms whose shift is not in K(q) dropped;  A <= L_r <= A + p2;
+ *   S(p, d)   = sum over sm_sgm_wta's directions of L_r(p, d); best = min over K(p) of S, web = 1 + the LEAST d of
+ *               K(p) reaching it; K(p) empty: web = best = sub = 0;
+ *   sub       = with d = web - 1: d - 1 and d + 1 both in K(p): sm_sgm_wta's rule on S(d-1), S(d), S(d+1); otherwise
+ *               (the winner at a band end, at 0 or at D - 1) 16 web;
+ *   right reference: mirror(sgm_near(mirror(R), mirror(L), mirror(prior_right))); the check is sm_lr_check's, and
+ *               sm_sgm_near_lr's d_sub is 0 where it rejected.
+ * Where K(p) is all of 0 .. D - 1 at every pixel the maps are sm_sgm_wta's; with p1 = p2 = 0 web is
+ * sm_census_wta_near's and best = paths * its best.  Windows up to 25 x 25 and up to 512 shifts (the census limits:
+ * nothing here grows with D).  Refused before any device call, naming the function: a NULL plan or required pointer,
+ * census_width, paths, penalties, radius, pairs, the window and shift limits, and an output that overlaps an image, a
+ * prior or another output.  Workspace: the census workspace and the banded volumes of ONE pair, 96 * W * H bytes
+ * whatever the radius (16 slots a pixel of u16 data term and int32 aggregate; 0.8 GB at 3840 x 2160); pairs go
+ * through them in turn.  The full SGM volumes are neither needed nor touched.  Allocated by sm_plan_reserve_sgm_near
+ * or by the first call that needs it, counted in sm_plan_workspace_bytes, freed by sm_plan_destroy.  STREAM CAPTURE:
+ * once sm_plan_reserve_sgm_near has been called; before, the call is refused with SM_ERR_ARG, a message naming it,
+ * and the capture valid.                                                                                           */
+/* adds: banded SGM arg-min -> d_web; d_best (min over K of S) and d_sub (int16, 1/16 shift) may be NULL */
+int sm_sgm_wta_near(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+                    int p1, int p2, int paths, int pairs, const int32_t *d_prior, int radius, int32_t *d_web,
+                    int32_t *d_best, int16_t *d_sub, void *stream);
+/* adds: the right-reference map around d_prior_right (a right-reference map), natural order */
+int sm_sgm_wta_near_right(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+                          int p1, int p2, int paths, int pairs, const int32_t *d_prior_right, int radius,
+                          int32_t *d_web_right, int32_t *d_best_right, void *stream);
+/* adds: descriptors once, both passes, check; d_web = checked map; d_best / d_web_right / d_rejected / d_sub may be NULL */
+int sm_sgm_near_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+                   int p1, int p2, int paths, int pairs, const int32_t *d_prior, const int32_t *d_prior_right,
+                   int radius, int max_diff, int32_t *d_web, int32_t *d_best, int32_t *d_web_right,
+                   int32_t *d_rejected, int16_t *d_sub, void *stream);
+/* adds: allocates the banded SGM workspace (and the census workspace) now; idempotent */
+int sm_plan_reserve_sgm_near(sm_plan *plan);
+
 /* ---- match uniqueness: runner-up, ratio filter, confidence: PARITY UNPINNED -- *
  * New work (no reference counterpart; the uniquenessRatio test of OpenCV's StereoBM / SGBM).  Every
  * matcher returns how good its winner is, not by how much it won; the left-right check finds occlusions, not the

@@ -175,6 +175,11 @@ _SIGNATURES = {
     "sm_sgm_wta_right": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sm_sgm_lr": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sm_plan_reserve_sgm": (_int, [_vp]),
+    "sm_sgm_wta_near": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _int, _vp, _vp, _vp, _vp]),
+    "sm_sgm_wta_near_right": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _int, _vp, _vp, _vp]),
+    "sm_sgm_near_lr": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp,
+                              _vp, _vp]),
+    "sm_plan_reserve_sgm_near": (_int, [_vp]),
     "sm_census_second": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp]),
     "sm_sgm_wta2": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sm_uniqueness_filter": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp]),

@@ -314,6 +314,7 @@ static const struct {
     /* SM_WS_FILTER  */ {offsetof(sm_plan, d_filter), ws_filter_bytes, false, "labels and sizes of the speckle filter"},
     /* SM_WS_INTERP  */ {offsetof(sm_plan, d_interp), sm_itp_bytes, false, "directional maps and carries of the interpolation"},
     /* SM_WS_CLOUD   */ {offsetof(sm_plan, d_cloud), sm_cloud_bytes, false, "tile counts of the point cloud"},
+    /* SM_WS_SGM_NEAR */ {offsetof(sm_plan, d_sgm_near), sm_sgm_near_volume_bytes, false, "banded SGM volumes"},
 };
 
 static void *&ws_ptr(const sm_plan *plan, int r) { return *(void **)((char *)plan + ws_rows[r].member); }

@@ -76,6 +76,7 @@ struct sm_plan {
     i32 *d_interp;       // sm_interp.hip: per pair six directional maps [6][H][W], line carries [6][segments][W + H - 1], row
                          // carries [2][H][chunks], 4 bytes an element (layout at the top of sm_interp.hip)
     i32 *d_cloud;        // sm_reproject.hip, sm_point_cloud: kept pixels per tile of 1024 pixels, then their offsets: [max_pairs][tiles]
+    void *d_sgm_near;    // sm_sgm_near.hip: one pair's banded volumes: A_b [H][W][16] u16, then S_b [H][W][16] i32 (slot innermost)
     int cost_lds_raised; // sm_cost_wta: the LDS limit of this plan's four-wave SAD kernel is raised (on `device`)
     char describe[512];
 };
@@ -137,7 +138,7 @@ void sm_step3_resolve_kernels(void);              // sm_step3.hip
 // adds a member, a row and a set, and nothing else.  A row of 0 bytes is never allocated and never missing.
 // ---------------------------------------------------------------------------
 enum { SM_WS_NARROW, SM_WS_EXT_LR, SM_WS_WEB_LR, SM_WS_GRAY_LR, SM_WS_CENSUS, SM_WS_SGM, SM_WS_FILTER, SM_WS_INTERP,
-       SM_WS_CLOUD, SM_WS_ROWS };
+       SM_WS_CLOUD, SM_WS_SGM_NEAR, SM_WS_ROWS };
 struct sm_ws_set {
     unsigned rows;             // bit r = row r
     const char *what;          // "the workspace of <what> is not allocated"
@@ -151,6 +152,7 @@ static const sm_ws_set SM_WS_SET_CENSUS = {1u << SM_WS_CENSUS | 1u << SM_WS_WEB_
 static const sm_ws_set SM_WS_SET_SGM = {1u << SM_WS_SGM, "SGM", "sm_plan_reserve_sgm", &SM_WS_SET_CENSUS};
 static const sm_ws_set SM_WS_SET_FILTER = {1u << SM_WS_FILTER, "the speckle filter", "sm_plan_reserve_filter", nullptr};
 static const sm_ws_set SM_WS_SET_INTERP = {1u << SM_WS_INTERP, "the interpolation", "sm_plan_reserve_interp", nullptr};
+static const sm_ws_set SM_WS_SET_SGM_NEAR = {1u << SM_WS_SGM_NEAR, "banded SGM", "sm_plan_reserve_sgm_near", &SM_WS_SET_CENSUS};
 static const sm_ws_set SM_WS_SET_CLOUD = {1u << SM_WS_CLOUD, "the point cloud", "sm_plan_reserve_cloud", nullptr};
 // all or nothing: on a failure every buffer this call allocated is freed and the plan is as before (but `first` stays)
 int sm_ws_reserve(sm_plan *plan, const sm_ws_set &set, const char *me);
@@ -163,6 +165,7 @@ size_t sm_lr_gray_batch_bytes(const sm_plan *plan);   // one batch of mirrored g
 size_t sm_itp_bytes(const sm_plan *plan);         // sm_interp.hip (its tile constants decide)
 size_t sm_sgm_volume_bytes(const sm_plan *plan);  // sm_sgm.hip (its padded shift count decides)
 size_t sm_cloud_bytes(const sm_plan *plan);       // sm_reproject.hip (its tile size decides)
+size_t sm_sgm_near_volume_bytes(const sm_plan *plan);   // sm_sgm_near.hip (its slot count decides)
 
 // ---------------------------------------------------------------------------
 // Argument rules that more than one entry point applies (sm_api.hip; the two on the decision tables: sm_edges.hip).
@@ -211,6 +214,8 @@ int sm_census_descriptors(sm_plan *plan, int cw, const uint8_t *left, const uint
 // sm_sgm.hip, for sm_sgm_wta2 (sm_unique.hip): the checks every SGM entry makes besides its pointers, and the left pass
 // whose last direction (k_sgm_path_second) writes the runner-up maps beside web / best / sub (best, sub, best2: NULL ok)
 int sm_sgm_args(const sm_plan *plan, int census_width, int p1, int p2, int paths, int pairs, const char *me);
+// ... those of them that need no plan (census width, paths, penalties), for banded SGM, whose shift limit is the census mode's
+int sm_sgm_scalar_args(int census_width, int p1, int p2, int paths, const char *me);
 int sm_sgm_second_pass(const sm_plan *plan, int cw, int p1, int p2, int paths, int pairs, i32 *web, i32 *best,
                        int16_t *sub, i32 *web2, i32 *best2, hipStream_t st);
 // sm_filter.hip, for sm_sgm_lr: k_sgm_sub_mask, sub = 0 where web = 0, over n elements

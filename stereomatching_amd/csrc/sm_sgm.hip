@@ -236,12 +236,19 @@ extern "C" int sm_plan_reserve_sgm(sm_plan *plan)
 }
 
 // what every SGM entry checks besides its pointers (before any device call; the checks that need no plan first)
-static int sgm_args(const sm_plan *plan, int census_width, int p1, int p2, int paths, int pairs, const char *me)
+// (the checks that need no plan: also banded SGM's, sm_sgm_near.hip)
+int sm_sgm_scalar_args(int census_width, int p1, int p2, int paths, const char *me)
 {
     SM_TRY(sm_check_census_width(census_width, me));
     if (paths != 4 && paths != 8) return sm_fail(SM_ERR_ARG, "%s: paths %d is not 4 or 8", me, paths);
     if (p1 < 0 || p2 < p1 || p2 > 32767)
         return sm_fail(SM_ERR_ARG, "%s: penalties p1 %d, p2 %d break 0 <= p1 <= p2 <= 32767", me, p1, p2);
+    return SM_OK;
+}
+
+static int sgm_args(const sm_plan *plan, int census_width, int p1, int p2, int paths, int pairs, const char *me)
+{
+    SM_TRY(sm_sgm_scalar_args(census_width, p1, p2, paths, me));
     SM_TRY(sm_check_pairs(plan, pairs, me));
     return sm_check_reach(plan, SGM_MAX_SHIFTS, me);
 }

@@ -540,6 +540,40 @@ class StereoPlan:
             lib.sm_sgm_lr, lambda pairs: (int(census), int(p1), int(p2), int(paths), pairs), left, right, max_diff,
             want_right, want_best, web, web_right, best, want_sub=want_sub, sub=sub))
 
+    # ---- banded SGM: aggregation within +-radius of a prior map -----------------
+    def reserve_sgm_near(self):
+        """The banded SGM workspace (the census workspace, and one pair's banded volumes, 96 bytes a pixel), allocated
+        now: keeps the allocation out of timed paths and out of stream captures."""
+        check(lib.sm_plan_reserve_sgm_near(self._h))
+
+    def sgm_wta_near(self, left, right, prior, census=7, p1=10, p2=120, paths=8, radius=1, want_best=True,
+                     want_sub=False, web=None, best=None, sub=None):
+        """SGM within `radius` (1..4) of the int32 web map `prior` (sm_sgm_wta_near, parity unpinned) -> (web, best,
+        sub): census_wta_near's candidates aggregated along `paths` lines with sgm_wta's penalties; a pixel whose
+        prior leaves no shift breaks the paths through it and gets web = best = sub = 0."""
+        return self._match_one(lib.sm_sgm_wta_near,
+                               lambda pairs, p: (int(census), int(p1), int(p2), int(paths), pairs, p, int(radius)), left,
+                               right, "", want_best, web, best, priors=((prior, "prior"),), want_sub=want_sub, sub=sub)
+
+    def sgm_wta_near_right(self, left, right, prior_right, census=7, p1=10, p2=120, paths=8, radius=1, want_best=True,
+                           web_right=None, best_right=None):
+        """The right-reference banded SGM (sm_sgm_wta_near_right) -> (web_right, best_right), around a right-reference
+        prior map."""
+        return self._match_one(lib.sm_sgm_wta_near_right,
+                               lambda pairs, p: (int(census), int(p1), int(p2), int(paths), pairs, p, int(radius)), left,
+                               right, "_right", want_best, web_right, best_right, priors=((prior_right, "prior_right"),))
+
+    def sgm_near_lr(self, left, right, prior, prior_right, census=7, p1=10, p2=120, paths=8, radius=1, max_diff=0,
+                    want_right=False, want_best=False, want_sub=False, web=None, web_right=None, best=None,
+                    sub=None) -> SGMLRResult:
+        """Both banded passes and the check in one call (sm_sgm_near_lr) -> SGMLRResult(web, rejected, web_right, best,
+        sub), shaped like sgm_lr's."""
+        return SGMLRResult(*self._match_lr(
+            lib.sm_sgm_near_lr,
+            lambda pairs, p, q: (int(census), int(p1), int(p2), int(paths), pairs, p, q, int(radius)), left, right,
+            max_diff, want_right, want_best, web, web_right, best,
+            priors=((prior, "prior"), (prior_right, "prior_right")), want_sub=want_sub, sub=sub))
+
     # ---- match uniqueness: runner-up, ratio filter, confidence ---------------------
     def census_second(self, left, right, web, census=7, want_best=True, web2=None, best2=None):
         """The runner-up of the census search (sm_census_second) -> (web2, best2): census_wta's arg-min over the shifts
