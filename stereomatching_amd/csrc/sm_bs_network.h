@@ -294,3 +294,176 @@ SM_NET_UNROLL
 SM_NET_UNROLL
         for (int it = 0; it < IT; it++) S[dd0 + it][k] = wr[it][P.out[k] - NIN];
 }
+
+// ---------------------------------------------------------------------------
+// The counter of a two-wave workgroup's shared warm-up rows (sm_match_bs_kernel.h, WT): NI one-bit inputs -- the
+// mismatch bits of HALF window rows of one shift -- to their count on TB = bits_for(NI) planes, in ONE carry-save
+// counter.  The sums are zero before the warm-up, so the planes of the count ARE the planes of S: nothing is added
+// to anything.  Wired like the row network: every weight is a CHAIN (a cell takes the sum of the cell before it
+// and two fresh wires), the cells are issued highest weight first, so one partial sum per weight and a few
+// carries are alive per item and four items fit the registers side by side.  All wires are positive.  The top
+// plane makes no carries: the count is known to be < 2^TB.
+// ---------------------------------------------------------------------------
+struct CountCell { short a, b, c, s, cy, w; };       // inputs (c < 0: half adder), sum, carry (< 0: not made), weight
+
+// wire numbers: [0, NI) the inputs, from NI on the outputs of the cells in the order they are made
+template <int NI, int TB>
+struct CountPlan {
+    static constexpr int MAXC = NI + TB;            // a full adder removes a wire; half adders: one per weight
+    CountCell cell[MAXC] = {};
+    int ncell = 0;
+    int nwires = NI;
+    int nops = 0;
+    short out[TB] = {};         // the wire that is plane k of the count (< 0: the plane is zero)
+};
+
+template <int NI, int TB>
+constexpr CountPlan<NI, TB> count_make_plan()
+{
+    static_assert(NI >= 3 && (1 << TB) > NI, "planes of the count");
+    CountPlan<NI, TB> p;
+    short q[2 * NI + 2 * TB] = {}, nx[NI + TB] = {};
+    int head = 0, tail = 0, nn = 0;
+    for (int w = 0; w < TB; w++) {
+        const bool top = w == TB - 1;
+        head = 0; tail = 0;
+        if (w == 0)
+            for (int i = 0; i < NI; i++) q[tail++] = (short)i;
+        for (int i = 0; i < nn; i++) q[tail++] = nx[i];
+        nn = 0;
+        while (tail - head >= 2) {
+            const int k = tail - head >= 3 ? 3 : 2;
+            CountCell c = {q[head], q[head + 1], (short)(k == 3 ? q[head + 2] : -1), (short)p.nwires++, -1, (short)w};
+            head += k;
+            p.nops++;
+            if (!top) {
+                c.cy = (short)p.nwires++;
+                nx[nn++] = c.cy;
+                p.nops++;
+            }
+            q[--head] = c.s;
+            p.cell[p.ncell++] = c;
+        }
+        p.out[w] = tail > head ? q[head] : (short)-1;
+    }
+    // order of issue: of the cells whose inputs are there, the one of the highest weight first (as net_make_plan)
+    bool made[NI + 2 * CountPlan<NI, TB>::MAXC] = {};
+    for (int i = 0; i < NI; i++) made[i] = true;
+    CountCell order[CountPlan<NI, TB>::MAXC] = {};
+    bool done[CountPlan<NI, TB>::MAXC] = {};
+    for (int n = 0; n < p.ncell; n++) {
+        int pick = -1;
+        for (int i = 0; i < p.ncell; i++) {
+            const CountCell &c = p.cell[i];
+            if (done[i] || !made[c.a] || !made[c.b] || (c.c >= 0 && !made[c.c])) continue;
+            if (pick < 0 || c.w > p.cell[pick].w) pick = i;
+        }
+        done[pick] = true;
+        order[n] = p.cell[pick];
+        made[order[n].s] = true;
+        if (order[n].cy >= 0) made[order[n].cy] = true;
+    }
+    for (int n = 0; n < p.ncell; n++) p.cell[n] = order[n];
+    return p;
+}
+
+template <int NI, int TB>
+struct CountPlanOf { static constexpr CountPlan<NI, TB> value = count_make_plan<NI, TB>(); };
+
+// the shortest distance, in operations of one item's instruction stream of IT items side by side, between a
+// cell's operation and the operation that made one of its inputs (inputs of the counter: made right in front
+// of the cell, all items' before the first sum -- at least IT operations before their use)
+template <int NI, int TB>
+constexpr int count_min_distance(int it)
+{
+    const CountPlan<NI, TB> p = CountPlanOf<NI, TB>::value;
+    int pos[NI + 2 * CountPlan<NI, TB>::MAXC] = {};
+    for (int i = 0; i < NI; i++) pos[i] = -(1 << 20);
+    int at = 0, best = 1 << 20;
+    for (int n = 0; n < p.ncell; n++) {
+        const CountCell &c = p.cell[n];
+        const short in[3] = {c.a, c.b, c.c};
+        for (int j = 0; j < 3; j++)
+            if (in[j] >= 0 && at - pos[in[j]] < best) best = at - pos[in[j]];
+        pos[c.s] = at;
+        at += it;
+        if (c.cy >= 0) { pos[c.cy] = at; at += it; }
+    }
+    return best;
+}
+
+// Operations per shift of the shared warm-up rows of an N x N window, the mismatch bits included: in one counter
+// (N / 2 * N bits and the cells of the plan) and row by row (per row N bits, a tree N -> HB planes and the ripple
+// add of its count into the SB sum planes: 2 for plane 0, a carry and a plane each above, no carry out of the top)
+constexpr int warm_ops_tree(int n, int cells_ops) { return n / 2 * n + cells_ops; }
+template <int N>
+constexpr int warm_ops_tree() { return warm_ops_tree(N, count_make_plan<N / 2 * N, bits_for(N / 2 * N)>().nops); }
+constexpr int warm_ops_rows(int n) { return n / 2 * (n + net_ops_count_tree(n) + 2 * bits_for(n * n) - 1); }
+
+template <int NI, int IT, int NW, int ID, typename XF>
+SM_NET_FN u32 count_wire(XF &xin, const u32 (&wr)[IT][NW], int it)
+{
+    if constexpr (ID < NI) return xin(it, ID);
+    else return wr[it][ID - NI];
+}
+
+template <int NI, int TB, int IT, int C, int NW, typename XF>
+SM_NET_FN void count_cells(XF &xin, u32 (&wr)[IT][NW])
+{
+    constexpr CountPlan<NI, TB> P = CountPlanOf<NI, TB>::value;
+    if constexpr (C < P.ncell) {
+        constexpr CountCell cl = P.cell[C];
+        constexpr bool full = cl.c >= 0;
+        u32 a[IT], b[IT], c[IT];
+SM_NET_UNROLL
+        for (int it = 0; it < IT; it++) {
+            a[it] = count_wire<NI, IT, NW, cl.a>(xin, wr, it);
+            b[it] = count_wire<NI, IT, NW, cl.b>(xin, wr, it);
+            if constexpr (full) c[it] = count_wire<NI, IT, NW, cl.c>(xin, wr, it);
+            else c[it] = 0u;
+        }
+SM_NET_UNROLL
+        for (int it = 0; it < IT; it++) {
+            if constexpr (full) wr[it][cl.s - NI] = bop<BOP_XOR3>(a[it], b[it], c[it]);
+            else wr[it][cl.s - NI] = a[it] ^ b[it];
+            SM_PIN();
+        }
+        if constexpr (cl.cy >= 0) {
+SM_NET_UNROLL
+            for (int it = 0; it < IT; it++) {
+                if constexpr (full) wr[it][cl.cy - NI] = bop<BOP_MAJ>(a[it], b[it], c[it]);
+                else wr[it][cl.cy - NI] = a[it] & b[it];
+                SM_PIN();
+            }
+        }
+        SM_SYNC();
+        count_cells<NI, TB, IT, C + 1, NW>(xin, wr);
+    }
+}
+
+template <int NI, int TB, int IT, int K, int NW>
+SM_NET_FN void count_planes(u32 (&h)[IT][TB], const u32 (&wr)[IT][NW])
+{
+    if constexpr (K < TB) {
+        constexpr CountPlan<NI, TB> P = CountPlanOf<NI, TB>::value;
+SM_NET_UNROLL
+        for (int it = 0; it < IT; it++) {
+            if constexpr (P.out[K] >= NI) h[it][K] = wr[it][P.out[K] - NI];
+            else h[it][K] = 0u;
+        }
+        count_planes<NI, TB, IT, K + 1, NW>(h, wr);
+    }
+}
+
+// h[it] = the count of xin(it, i), i < NI, for it < IT side by side; inputs are made when first used, in the
+// order of their numbers
+template <int NI, int TB, int IT, typename XF>
+SM_NET_FN void count_chain_lockstep(XF xin, u32 (&h)[IT][TB])
+{
+    constexpr CountPlan<NI, TB> P = CountPlanOf<NI, TB>::value;
+    constexpr int NW = P.nwires - NI;
+    static_assert(count_min_distance<NI, TB>(IT) >= IT, "a cell reads a result made fewer than IT operations before");
+    u32 wr[IT][NW];
+    count_cells<NI, TB, IT, 0, NW>(xin, wr);
+    count_planes<NI, TB, IT, 0, NW>(h, wr);
+}

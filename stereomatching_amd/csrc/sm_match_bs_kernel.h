@@ -282,6 +282,21 @@ __device__ __forceinline__ void add_lockstep(u32 (&S)[DS][SB], int dd0, const u3
 
 template <int V> struct IntTag { static constexpr int value = V; };
 
+// Which builds count a two-wave workgroup's shared warm-up rows in one carry-save counter per shift (WT, see the
+// kernel's warm-up): the two-wave builds whose wave shares at least two rows, less those that would lose occupancy or
+// gain scratch by it -- the views of all N / 2 rows are alive at once, next to the sums.  The exceptions are what ONE
+// compiler's resource report said (profiles/r11/resource_usage.txt): nothing fails at build time if another
+// toolchain spills elsewhere, so the table is made again, and the exceptions derived again from it, whenever the
+// compiler changes.  A build that does not take the counter is the code it was before.
+// That table: up to 13 x 13 every build keeps its two waves per SIMD without scratch (13 x 13 at 4 shifts per lane goes
+// from 176 to 193 .. 207 registers of the 256 it may have).  From 15 x 15 on the views of 7 and more rows do not fit:
+// 32 .. 1264 bytes of scratch per lane at 8 and at 4 shifts per lane alike (15 x 15 toroidal at 4 shifts alone would
+// fit, with 250 registers; its ghost build would not, and the rule stays one line).
+constexpr bool warm_tree_taken(int n, bool duo)
+{
+    return duo && n / 2 >= 2 && n <= 13;
+}
+
 // ---------------------------------------------------------------------------
 // Staging: `nrow` rows of `rw` words, row r at src + r * stride, to dst[r * rw + k], by T threads.  Element
 // e = r * rw + k belongs to thread e % T, so consecutive threads load consecutive words of a row and a thread's
@@ -490,15 +505,21 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
         dvalid = dlim >= DS ? (1u << DS) - 1u : (dlim <= 0 ? 0u : ((1u << dlim) - 1u));
     }
 
+    // WT: a two-wave workgroup's wave counts its HALF shared warm-up rows in ONE carry-save counter per shift (see
+    // the warm-up below): the counter's TB planes ARE the sums, so no plane of S is zeroed here.
+    constexpr int TB = bits_for(HALF * N);      // planes of the count of HALF rows
+    constexpr bool WT = warm_tree_taken(N, DUO);
     u32 S[DS][SB];
+    if constexpr (!WT) {
 #pragma unroll
-    for (int dd = 0; dd < DS; dd++)
+        for (int dd = 0; dd < DS; dd++)
 #pragma unroll
-        for (int k = 0; k < SB; k++) {
-            S[dd][k] = 0;
-            // (zeroed HERE, under the staging loads: left to itself the compiler zeroes the planes behind the barrier)
-            asm volatile("" : "+v"(S[dd][k]));
-        }
+            for (int k = 0; k < SB; k++) {
+                S[dd][k] = 0;
+                // (zeroed HERE, under the staging loads: left to itself the compiler zeroes the planes behind the barrier)
+                asm volatile("" : "+v"(S[dd][k]));
+            }
+    }
 
     SM_PIN();
     stL.write(IntTag<1>{});
@@ -649,9 +670,57 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
     // 16 x SB register copies per row for it).
     SM_SLICE_PRIO();                // the warm-up rows are shorter than one time slice
     if (DUO) {
-        // this wave's HALF of the N - 1 rows both first windows contain ...
+        // WT: this wave's HALF shared rows in one counter per shift.  Row by row (the loop below) every row pays an LDS
+        // round trip of its own, a tree N -> HB planes and a ripple add of its count into all SB planes of the sums:
+        // 3 operations per mismatch bit (9 x 9: 4 x (9 + 14 + 13) = 144 per shift).  Here the reads of all HALF rows are
+        // issued back to back, and the HALF * N mismatch bits of a shift go through one carry-save counter
+        // (count_chain_lockstep, sm_bs_network.h) whose TB planes ARE S[d] -- the sums are zero before: 2 operations
+        // per bit (36 + 68 = 104).  GW shifts side by side, like every other part of the kernel.
+        if constexpr (WT) {
+            static_assert(TB <= SB, "the count of HALF rows fits the sum planes");
+            static_assert(warm_ops_tree<N>() < warm_ops_rows(N), "the counter is the shorter form");
+            static_assert(N != 9 || (warm_ops_tree<N>() == 104 && warm_ops_rows(N) == 144), "operations per shift at 9 x 9");
+            const u32 a0L = (u32)(uintptr_t)pL + 4u * (u32)(c0 * plw + wL), a0R = (u32)(uintptr_t)pR + 4u * (u32)(c0 * prw + wR);
+            const u32 stL_ = (u32)(sgn * 4 * plw), stR_ = (u32)(sgn * 4 * prw);
+            RawRow raw[HALF];
+#pragma unroll
+            for (int r = 0; r < HALF; r++) lds_issue(raw[r], a0L + stL_ * (u32)r, a0R + stR_ * (u32)r);
+            SM_PIN();
+            RowViews v[HALF];
+            u32 rv[HALF][N + GW - 1];           // per row: right views dd0 ... dd0 + GW + N - 2 of the group
+#pragma unroll
+            for (int r = 0; r < HALF; r++) {
+                views_of(raw[r], v[r]);
+#pragma unroll
+                for (int m = 0; m < N - 1; m++) rv[r][m + GW] = rview(v[r], m);
+            }
+#pragma unroll
+            for (int dd0 = 0; dd0 < DS; dd0 += GW) {
+#pragma unroll
+                for (int r = 0; r < HALF; r++) {
+#pragma unroll
+                    for (int m = 0; m < N - 1; m++) rv[r][m] = rv[r][m + GW];
+#pragma unroll
+                    for (int m = 0; m < GW; m++) { rv[r][N - 1 + m] = rview(v[r], dd0 + N - 1 + m); SM_PIN(); }
+                }
+                SM_SYNC();
+                u32 h[GW][TB];
+                // input i: column i % N of row i / N
+                count_chain_lockstep<HALF * N, TB, GW>([&](int it, int i) -> u32 {
+                    const int r = i / N, col = i % N;
+                    const u32 x = GHOST ? bop<BOP_XOR_AND>(v[r].lv[col], rv[r][it + col], cvv[col]) : (v[r].lv[col] ^ rv[r][it + col]);
+                    SM_PIN();
+                    return x;
+                }, h);
+#pragma unroll
+                for (int it = 0; it < GW; it++)
+#pragma unroll
+                    for (int k = 0; k < SB; k++) S[dd0 + it][k] = k < TB ? h[it][k] : 0u;
+            }
+        }
+        // this wave's HALF of the N - 1 rows both first windows contain (WT: counted above) ...
 #pragma unroll 1
-        for (int e = 0; e <= HALF; e++) {
+        for (int e = WT ? HALF : 0; e <= HALF; e++) {
         if (e == HALF) {
         // ... the other wave's half, through an LDS block [2 halves of the shifts][DS / 2 *
         // SB / 2 plane pairs][64 lanes]: wave w assembles the totals of half w.  Each wave
@@ -661,8 +730,13 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
         // at a time, both ways, with a barrier each: 8 barriers, each of which waits for
         // whichever of the two waves its SIMD currently serves at the lower priority --
         // measured ~2.3 us per workgroup, more than one of the 1.7 us warm-up rows saved.)
-        constexpr int DH = DS / 2, XP = DH * SB / 2;
-        static_assert(DS % 2 == 0 && (DH * SB) % 2 == 0, "exchange halves");
+        // WT: the partial sums of HALF rows have PB = TB planes (the planes above are zero), so steps (1) and (2) move
+        // TB planes per shift; the totals are SB planes as before and keep their words.  The partial sums lie at the
+        // END of a slot (from plane pair XP - XQ on): the totals of the shifts already added, written from the slot's
+        // start, then never reach a partial sum that is still to be read -- (k + 1) SB <= XP - XQ + (k + 1) TB for
+        // every pair of shifts k < DH / 2.
+        constexpr int DH = DS / 2, XP = DH * SB / 2, PB = WT ? TB : SB, XQ = DH * PB / 2;
+        static_assert(DS % 2 == 0 && (DH * SB) % 2 == 0 && (DH * PB) % 2 == 0, "exchange halves");
         typedef u32 v2u __attribute__((ext_vector_type(2)));
         // (the two slots end / begin at word g.xm_off: behind them -- and over them, once the warm-up
         // is done -- lie the buffers of the lane merge, wave w's over the slot that wave w reads LAST)
@@ -671,24 +745,24 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
             constexpr int OWN = decltype(own_tag)::value, OTH = 1 - OWN;
             v2u *slot_own = xq + OWN * XP * 64, *slot_oth = xq + OTH * XP * 64;
 #pragma unroll
-            for (int j = 0; j < XP; j++) {
+            for (int j = 0; j < XQ; j++) {
                 const int p = 2 * j, q = 2 * j + 1;
-                const v2u v = {S[OTH * DH + p / SB][p % SB], S[OTH * DH + q / SB][q % SB]};
-                slot_oth[j * 64] = v;
+                const v2u v = {S[OTH * DH + p / PB][p % PB], S[OTH * DH + q / PB][q % PB]};
+                slot_oth[(XP - XQ + j) * 64] = v;
             }
             __syncthreads();
 #pragma unroll
-            for (int dd = 0; dd < DH; dd += 2) {        // two shifts = SB plane pairs at a time
-                u32 o[2][SB];
+            for (int dd = 0; dd < DH; dd += 2) {        // two shifts = PB plane pairs (totals: SB) at a time
+                u32 o[2][PB];
 #pragma unroll
-                for (int j = 0; j < SB; j++) {
+                for (int j = 0; j < PB; j++) {
                     const int p = 2 * j, q = 2 * j + 1;
-                    const v2u v = slot_own[(dd * SB / 2 + j) * 64];
-                    o[p / SB][p % SB] = v.x;
-                    o[q / SB][q % SB] = v.y;
+                    const v2u v = slot_own[(XP - XQ + dd * PB / 2 + j) * 64];
+                    o[p / PB][p % PB] = v.x;
+                    o[q / PB][q % PB] = v.y;
                 }
-                add_planes<SB, SB>(S[OWN * DH + dd], o[0]);
-                add_planes<SB, SB>(S[OWN * DH + dd + 1], o[1]);
+                add_planes<SB, PB>(S[OWN * DH + dd], o[0]);
+                add_planes<SB, PB>(S[OWN * DH + dd + 1], o[1]);
 #pragma unroll
                 for (int j = 0; j < SB; j++) {
                     const int p = 2 * j, q = 2 * j + 1;

@@ -48,6 +48,9 @@ def waves_and_rows(geom: dict, height: int, pairs: int):
 def _setup_text(geom: dict) -> str:
     n = geom["window"]
     if geom["kernel"] == 4 and geom.get("waves_per_workgroup", 1) == 2:
+        if 5 <= n <= 13:        # warm_tree_taken of csrc/sm_match_bs_kernel.h
+            return (f"set-up + one counter over {n // 2} shared warm-up rows + 1 warm-up row + swap of the {n - 1} "
+                    f"shared rows' sums with the workgroup's other wave")
         return (f"set-up + {n // 2 + 1} warm-up rows + swap of the {n - 1} shared rows' sums with the "
                 f"workgroup's other wave")
     return f"set-up + {n} warm-up rows"
