@@ -442,7 +442,9 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
     // per lane: four units per slice (other lengths, phases and duty cycles all within +-1.5 %,
     // profiles/r02/ab_priority_pattern.txt).  The launches of 8 and 4 shifts per lane are short
     // and swap every unit (C2's match launch 17.1 -> 15.6 us, profiles/r04/ab_prio_unit.txt).
-    // s_setprio is issued once per row (issuing it only on a change measured no faster, profiles/r03).
+    // s_setprio is issued once per row (issuing it only on a change measured no faster, profiles/r03; neither did
+    // issuing it on every fourth row of the builds of 16 shifts per lane, whose slice is some 8 rows long: C3 step
+    // 82.0 .. 82.5 -> 82.0 .. 82.3 us, profiles/r12/ab_rowloop.txt).
     constexpr unsigned PATTERN = DS == 16 ? 0xF0F0F0F0u : 0xAAAAAAAAu;
     const unsigned long long clk0 = clk;
 #define SM_SLICE_PRIO()                                                               \
@@ -814,6 +816,21 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
         lds_issue(qn, aNewL, aNewR);
         lds_issue(qo, aNewL - sL * N, aNewR - sR * N);
     }
+    // ---- the row loop.  Its output path has two forms, of which a workgroup takes one (`fixed`, wave-uniform, decided
+    // here once): the generic one, which asks the launch's shape as it goes, and the fixed-shape one (FX) for the shape
+    // the flagship launch has in all tiles but those at the image's right and lower border -- lanes merged through LDS,
+    // NLF lanes per word, all D = NLF * DS shifts, int32 maps stored 16 bytes at a time, tile wholly inside the image.
+    // Only the two-wave builds of 16 shifts per lane with the full shift range carry the fixed form; every other build,
+    // and every workgroup that fails one of the tests, runs the generic one.
+    // (ONE loop with the choice inside, one scalar branch per row.  Two copies of the loop, chosen between in front of
+    // them, were built first: the sums then enter two loops, the allocator kept a second set of them, and every build
+    // that carries both forms spilled -- 9 x 9: 179 registers, 540 bytes of scratch per lane.)
+    constexpr int NLF = 128 / DS, L2F = DS == 16 ? 3 : DS == 8 ? 4 : 5;    // lanes per word, log2
+    constexpr int LPIF = NLF / 4, PERF = 32 / LPIF;                         // lanes per merge item, pixels per lane
+    constexpr bool FXB = DUO && DS == 16 && FULLD;
+    bool fixed = false;
+    if constexpr (FXB)
+        fixed = g.xmerge && g.nl == NLF && g.web_bytes == 4 && g.vec_ok && tx0 + 32 * (64 / NLF) <= g.w && ty0 + 2 * g.tile_h <= g.h;
 #pragma unroll 1
     for (int t = 0;;) {
         SM_SLICE_PRIO();
@@ -1031,6 +1048,56 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
             }
         };
 
+        // The same for the fixed shape (FX): lane `sub` of an item's LPIF lanes turns PERF pixels of the word at (xw, yy)
+        // into integers, chunk c at pixel 4 * (sub + c * LPIF).  The word lies inside the image, the maps are int32 and
+        // 16-byte aligned, the shift index has AB + L2F planes and D - 1 has all of them set: nothing is asked per
+        // chunk or plane but whether the counts are wanted.
+        auto emit_fixed = [&](u32 (&B)[SB], u32 (&arg)[ABMAX], int xw, int yy, int sub) {
+            constexpr int NA = AB + L2F;
+            static_assert(NA <= 8 && (1 << NA) == NLF * DS, "index planes of the fixed shape");
+            u32 allone = B[0];
+#pragma unroll
+            for (int k = 1; k < SB; k++) allone &= B[k];
+            // "no shift matched" -> web = D: every plane of D - 1 is set
+#pragma unroll
+            for (int k = 0; k < NA; k++) arg[k] |= allone;
+            const size_t o0 = ((size_t)pair * g.h + yy) * g.w + xw;
+            // (a loop, not PERF / 4 copies: in one straight stretch the scheduler works on all chunks at once, with some
+            // fifty registers more than the sums beside them leave -- every build spilled)
+#pragma unroll 1
+            for (int c = 0, p0 = 4 * sub; c < PERF / 4; c++, p0 += 4 * LPIF) {
+                u32 alo = 0;
+#pragma unroll
+                for (int k = 0; k < NA; k++) alo += (__umul24((arg[k] >> p0) & 15u, 0x204081u) & 0x01010101u) << k;
+                const v4i wq = {(i32)(alo & 255u) + 1, (i32)((alo >> 8) & 255u) + 1, (i32)((alo >> 16) & 255u) + 1, (i32)(alo >> 24) + 1};
+                store_map4(web + o0 + p0, wq);
+                if (best) {                          // uniform: the counts are wanted at all
+                    u32 bb = 0, bhi = 0;
+#pragma unroll
+                    for (int k = 0; k < SB; k++) {
+                        const u32 sp = __umul24((B[k] >> p0) & 15u, 0x204081u) & 0x01010101u;
+                        if (k < 8) bb += sp << k; else bhi += sp << (k - 8);
+                    }
+                    const u32 none = __umul24((allone >> p0) & 15u, 0x204081u) & 0x01010101u;
+                    i32 bv[4];
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        int taps = N * N;
+                        if (GHOST) {
+                            const int x = xw + p0 + q;
+                            const int cols = min(g.w - 1, x + HALF) - max(0, x - HALF) + 1;
+                            const int rws = min(g.h - 1, yy + HALF) - max(0, yy - HALF) + 1;
+                            taps = cols * rws;
+                        }
+                        const bool no = (none >> (8 * q)) & 1u;
+                        bv[q] = no ? 0 : taps - (i32)(((bb >> (8 * q)) & 255u) | (((bhi >> (8 * q)) & 255u) << 8));
+                    }
+                    const v4i bq = {bv[0], bv[1], bv[2], bv[3]};
+                    store_map4(best + o0 + p0, bq);
+                }
+            }
+        };
+
         // lanes `me` and me ^ (1 << K) hold candidates of the same pixels: lower count wins, on a tie
         // the lane with the higher shifts (bit K of `me` set); the winner's bit K becomes plane NA
 #define SM_MERGE(K, me, NA)                                                            \
@@ -1048,7 +1115,8 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
             _Pragma("unroll") for (int k = 0; k < NA; k++) arg[k] = bop<BOP_SEL>(take, pa[k], arg[k]); \
             arg[NA] = take ^ mine_high;   /* partner's bit K = ~mine */              \
         }
-        if (g.xmerge) {
+        auto merge_rows = [&](auto fx_tag) {
+            constexpr bool FX = decltype(fx_tag)::value != 0;
             // ---- THE NL LANES OF A WORD ARE MERGED THROUGH LDS, FOUR ROWS AT A TIME.  Merging them per
             // row with DPP costs log2(nl) full compare-and-select levels per lane and row (~105 VALU
             // instructions of 1640 at C3, 36 of them half-rate DPP moves; measured by leaving them out:
@@ -1082,8 +1150,13 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 // reader role: item (rr, wr), sub-lane `sub` of its LPI lanes
-                const int lpi = g.nl >> 2, l2lpi = g.log2nl - 2;
-                const int rr = tid >> 4, wr = (tid & 15) >> l2lpi, sub = tid & (lpi - 1);
+                const int lpi = FX ? LPIF : g.nl >> 2, l2lpi = FX ? L2F - 2 : g.log2nl - 2;
+                // (FX: the role is made again from the lane index in every batch.  With constant shifts the compiler
+                // would keep it, and every chunk's bit offset and address part derived from it, in registers across
+                // the row loop, which has none to spare: the slide spilled)
+                int tb = tid;
+                if constexpr (FX) asm volatile("" : "+v"(tb));
+                const int rr = tb >> 4, wr = (tb & 15) >> l2lpi, sub = tb & (lpi - 1);
                 u32 Bm[SB], am[ABMAX];
 #pragma unroll
                 for (int k = 0; k < ABMAX; k++) am[k] = 0;
@@ -1141,13 +1214,18 @@ __global__ __launch_bounds__(DUO ? 128 : 64, SM_BS_WAVES) void k_match_bs(const 
                 // rows was built and measured -- no better at C3 / C5 (90.6 vs 89.5 us), the extra LDS round trip
                 // costs what the contiguous stores gain; the store flavour matters far more: with `nt` instead of
                 // `sc1` scattered pieces cost a factor 2.3 at 8 x 1080p.  profiles/r04/ab_store_flavour.txt)
-                if (rr <= r && yy < g.h && yy >= 0) {
+                if constexpr (FX) {
+                    if (rr <= r) emit_fixed(Bm, am, tx0 + 32 * wr, yy, sub);       // (the last batch of a tile may be short)
+                } else if (rr <= r && yy < g.h && yy >= 0) {
                     const int per = 32 >> l2lpi;
                     emit_pixels(Bm, am, tx0 + 32 * wr, yy, 4 * sub, per, 4 * lpi);
                 }
                 __builtin_amdgcn_wave_barrier();
             }
-        } else {
+        };
+        if (FXB && fixed) merge_rows(IntTag<FXB ? 1 : 0>{});
+        else if (g.xmerge) merge_rows(IntTag<0>{});
+        else {
             // ---- merge the nl lanes of this word per row (DPP; ds_bpermute beyond 16 lanes)
             if (g.nl > 1) SM_MERGE(0, s, AB)
             if (g.nl > 2) SM_MERGE(1, s, AB + 1)
