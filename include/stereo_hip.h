@@ -575,6 +575,30 @@ int sm_sgm_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_r
 /* adds: allocates the SGM workspace now; idempotent */
 int sm_plan_reserve_sgm(sm_plan *plan);
 
+/* ---- SGM: the left-right check from one aggregated volume: PARITY UNPINNED -- *
+ * New work (no reference counterpart; how OpenCV's SGBM and libSGM get their right-reference disparity).
+ * sm_sgm_lr aggregates twice, once per reference image.  Here the right map is read off the LEFT pass's aggregate S
+ * along its diagonals, so one aggregation serves both maps.  Arguments and S as sm_sgm_wta's.  Definition:
+ *   left maps   d_web / d_best / d_sub exactly as from sm_sgm_wta;
+ *   right map   right pixel (u, y) takes candidate d from left pixel x = u - d:
+ *               toroidal: every d = 0 .. D - 1, x = (u - d) mod W (D > W: the same x serves several d);
+ *               ghost:    only d <= u (S has no column left of 0); d = 0 is always a candidate;
+ *               best_right(u, y) = min over the candidates of S(y, x, d), web_right = 1 + the LEAST d reaching it;
+ *   check       sm_lr_check's rule between web and this web_right; d_sub is 0 where it rejected.
+ * This is ANOTHER right map than sm_sgm_wta_right's, not a faster route to it: the paths and the box window belong to
+ * the left image only.  With p1 = p2 = 0 in toroidal mode web_right is sm_census_wta_right's.  Refusals: sm_sgm_wta's
+ * and sm_sgm_lr's, in their order, with these names in them.  Workspace: the SGM workspace as it is (nothing new;
+ * sm_plan_reserve_sgm), pairs going through the one volume in turn.  STREAM CAPTURE: as sm_sgm_wta.                */
+/* adds: the unchecked left maps and the single-volume right maps, natural order; d_best, d_sub, d_best_right may be NULL */
+int sm_sgm_wta_both(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+                    int p1, int p2, int paths, int pairs, int32_t *d_web, int32_t *d_best, int16_t *d_sub,
+                    int32_t *d_web_right, int32_t *d_best_right, void *stream);
+/* adds: sm_sgm_lr with the single-volume right map: one aggregation, then the check; parameters and NULL rules as
+ * sm_sgm_lr's; d_web_right, where given, receives the single-volume map */
+int sm_sgm_lr_single(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+                     int p1, int p2, int paths, int pairs, int max_diff, int32_t *d_web, int32_t *d_best,
+                     int32_t *d_web_right, int32_t *d_rejected, int16_t *d_sub, void *stream);
+
 /* ---- banded SGM: semi-global aggregation within +-r of a prior map: PARITY UNPINNED -- *
  * New work (no reference counterpart; the tSGM idea of coarse-to-fine SGM pipelines).  The guided
  * re-search above with SGM's smoothness term: the last step of the half-resolution path becomes coarse SGM, upsample,

@@ -175,6 +175,8 @@ _SIGNATURES = {
     "sm_sgm_wta_right": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sm_sgm_lr": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sm_plan_reserve_sgm": (_int, [_vp]),
+    "sm_sgm_wta_both": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sm_sgm_lr_single": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sm_sgm_wta_near": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _int, _vp, _vp, _vp, _vp]),
     "sm_sgm_wta_near_right": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _int, _vp, _vp, _vp]),
     "sm_sgm_near_lr": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp,

@@ -218,6 +218,11 @@ int sm_sgm_args(const sm_plan *plan, int census_width, int p1, int p2, int paths
 int sm_sgm_scalar_args(int census_width, int p1, int p2, int paths, const char *me);
 int sm_sgm_second_pass(const sm_plan *plan, int cw, int p1, int p2, int paths, int pairs, i32 *web, i32 *best,
                        int16_t *sub, i32 *web2, i32 *best2, hipStream_t st);
+// sm_sgm.hip, for the single-volume check (sm_sgm_both.hip): the data term and all directions of ONE pair with the last
+// direction launched as k_sgm_path<K, SGM_MID>: afterwards *S, [H][W][*Dp] int32 in the plan's SGM workspace, holds the
+// full aggregate (entries d >= num_shifts are not costs: wrapped sums of the path kernel's padding value)
+int sm_sgm_volume_pass(const sm_plan *plan, int cw, int p1, int p2, int paths, int pair, const i32 **S, int *Dp,
+                       hipStream_t st);
 // sm_filter.hip, for sm_sgm_lr: k_sgm_sub_mask, sub = 0 where web = 0, over n elements
 int sm_sub_mask_launch(const i32 *web, int16_t *sub, long long n, hipStream_t st);
 

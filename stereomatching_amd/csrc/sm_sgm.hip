@@ -290,8 +290,9 @@ static const void *sgm_path_ptr(int mode)
 
 // the directions in stream order (integer sums: the order changes nothing); the last one emits the maps
 // (web2: the last direction is k_sgm_path_second, which writes the runner-up maps as well)
+// (keep: the last direction is SGM_MID as well, so the full S is left in the volume and no map is written)
 static int sgm_paths_launch(const sm_plan *plan, int p1, int p2, int paths, bool mirror, int pair, i32 *web, i32 *best,
-                            int16_t *sub, i32 *web2, i32 *best2, hipStream_t st)
+                            int16_t *sub, i32 *web2, i32 *best2, hipStream_t st, bool keep = false)
 {
     static const int dirs[8][2] = {{1, 0}, {0, 1}, {1, 1}, {-1, 1}, {1, -1}, {-1, -1}, {0, -1}, {-1, 0}};
     static const int four[4] = {0, 1, 6, 7};
@@ -307,7 +308,7 @@ static int sgm_paths_launch(const sm_plan *plan, int p1, int p2, int paths, bool
         const int *dir = dirs[paths == 4 ? four[r] : r];
         g.dx = dir[0]; g.dy = dir[1];
         g.lines = g.dy == 0 ? g.h : g.dx == 0 ? g.w : g.w + g.h - 1;
-        const int mode = r == 0 ? SGM_FIRST : r == paths - 1 ? SGM_LAST : SGM_MID;
+        const int mode = r == 0 ? SGM_FIRST : r == paths - 1 && !keep ? SGM_LAST : SGM_MID;
         const void *fn = K == 1 ? sgm_path_ptr<1>(mode) : K == 2 ? sgm_path_ptr<2>(mode) : sgm_path_ptr<4>(mode);
         // (paths >= 4: the last direction is never the first, so S always holds the other directions' sum)
         void *args[] = {(void *)&A, (void *)&S, (void *)&web, (void *)&best, (void *)&sub, (void *)&g};
@@ -346,6 +347,17 @@ int sm_sgm_second_pass(const sm_plan *plan, int cw, int p1, int p2, int paths, i
                        int16_t *sub, i32 *web2, i32 *best2, hipStream_t st)
 {
     return sgm_pass(plan, cw, p1, p2, paths, false, pairs, web, best, sub, st, web2, best2);
+}
+
+// for sm_sgm_both.hip: the data term and every direction of pair `pair`, the last one as k_sgm_path<K, SGM_MID>, so that
+// the aggregate volume holds the full S afterwards: *S its [H][W][*Dp] int32 entries (entries d >= D are not costs)
+int sm_sgm_volume_pass(const sm_plan *plan, int cw, int p1, int p2, int paths, int pair, const i32 **S, int *Dp,
+                       hipStream_t st)
+{
+    *Dp = sgm_padded_shifts(plan);
+    *S = (const i32 *)((const char *)plan->d_sgm + (size_t)2 * plan->width * plan->height * *Dp);
+    SM_TRY(sgm_cost_launch(plan, cw, false, pair, st));
+    return sgm_paths_launch(plan, p1, p2, paths, false, pair, nullptr, nullptr, nullptr, nullptr, nullptr, st, true);
 }
 
 // the mode as the entry driver sees it (sm_entry.h)

@@ -540,6 +540,30 @@ class StereoPlan:
             lib.sm_sgm_lr, lambda pairs: (int(census), int(p1), int(p2), int(paths), pairs), left, right, max_diff,
             want_right, want_best, web, web_right, best, want_sub=want_sub, sub=sub))
 
+    def sgm_wta_both(self, left, right, census=7, p1=10, p2=120, paths=8, want_best=True, want_sub=False,
+                     want_best_right=True, web=None, best=None, sub=None, web_right=None, best_right=None):
+        """sgm_wta's maps and a right-reference map read off the same aggregate (sm_sgm_wta_both) -> (web, best, sub,
+        web_right, best_right): web_right(u, y) = 1 + the least d minimising S(y, u - d, d) over the left pixels that
+        the border mode gives right pixel u (toroidal: all, modulo the width; ghost: d <= u).  One aggregation instead
+        of sgm_wta + sgm_wta_right's two; the right map is not sgm_wta_right's.  Outputs not wanted are None."""
+        left, right, pairs = self._pair(left, right)
+        web = self._out(web, pairs, "web")
+        best = self._out(best, pairs, "best") if want_best else None
+        sub = self._out(sub, pairs, "sub", torch.int16) if want_sub else None
+        web_right = self._out(web_right, pairs, "web_right")
+        best_right = self._out(best_right, pairs, "best_right") if want_best_right else None
+        check(lib.sm_sgm_wta_both(self._h, _ptr(left), _ptr(right), int(census), int(p1), int(p2), int(paths), pairs,
+                                  _ptr(web), _ptr(best), _ptr(sub), _ptr(web_right), _ptr(best_right), self._stream()))
+        return web, best, sub, web_right, best_right
+
+    def sgm_lr_single(self, left, right, census=7, p1=10, p2=120, paths=8, max_diff=0, want_right=False,
+                      want_best=False, want_sub=False, web=None, web_right=None, best=None, sub=None) -> SGMLRResult:
+        """sgm_lr with sgm_wta_both's right map (sm_sgm_lr_single) -> SGMLRResult, shaped like sgm_lr's: one
+        aggregation and the check, about half of sgm_lr's time."""
+        return SGMLRResult(*self._match_lr(
+            lib.sm_sgm_lr_single, lambda pairs: (int(census), int(p1), int(p2), int(paths), pairs), left, right, max_diff,
+            want_right, want_best, web, web_right, best, want_sub=want_sub, sub=sub))
+
     # ---- banded SGM: aggregation within +-radius of a prior map -----------------
     def reserve_sgm_near(self):
         """The banded SGM workspace (the census workspace, and one pair's banded volumes, 96 bytes a pixel), allocated
