@@ -121,6 +121,29 @@ def test_sgm_reaches_its_u16_and_key_bounds(p1, p2):
     assert sr.aggregate(a, p1, p2, 4).max() == 4 * L_MAX
 
 
+def test_sgm_shows_the_full_cost_only_where_it_is_the_only_shift():
+    """anti's shift k costs 30000 everywhere, but a cheaper shift wins and the path minimum never passes through k: with
+    the data term saturated at 0x7000 = 28672 (profiles/mutants: census_c, a mutant of k_sgm_cost_v's stores) the maps
+    of anti(98, 28, 5) are what they were, so that case cannot tell.  At D = 1 the full cost is the winner itself:
+    best = paths * 30000 at every pixel, which the saturated data term misses (test_census_extremes_gpu.py
+    test_sgm_full_cost_at_the_only_shift)"""
+    left, right = cx.anti(W, H, 5)
+    a = sr.data_term(left, right, 64, 25, 7, "toroidal")
+    assert a.max() == A_MAX and (a > 0x7000).any()
+    for p1, p2 in ((32767, 32767), (0, 0)):
+        want, sat = sr.winner(sr.aggregate(a, p1, p2, 8)), sr.winner(sr.aggregate(np.minimum(a, 0x7000), p1, p2, 8))
+        assert all(np.array_equal(x, y) for x, y in zip(want, sat)), (p1, p2)
+    left, right = cx.anti(W, H, 0)
+    for mode in ("toroidal", "ghost"):
+        a = sr.data_term(left, right, 1, 25, 7, mode)
+        # (ghost: a window on the border holds fewer pixels; the interior still lies above 0x7000)
+        assert (a == A_MAX).all() if mode == "toroidal" else 0x7000 < a.max() < A_MAX
+        for paths in (4, 8):
+            best, web, sub = sr.winner(sr.aggregate(a, 32767, 32767, paths))
+            assert best.max() == paths * a.max() and (web == 1).all() and (sub == 16).all()
+            assert not np.array_equal(sr.winner(sr.aggregate(np.minimum(a, 0x7000), 32767, 32767, paths))[0], best)
+
+
 def test_sgm_of_rows_anti_is_constant_over_d():
     """every A, so every L_r and S, is the same at all shifts of a pixel, whatever the penalties: web 1, sub 16,
     best = paths * 26250 (toroidal)"""

@@ -189,6 +189,24 @@ def test_sgm_at_its_u16_and_key_bounds(hip, mode, d, p1, p2):
 
 
 @pytest.mark.parametrize("mode", MODES)
+def test_sgm_full_cost_at_the_only_shift(hip, mode):
+    """anti(98, 28, 0), D = 1: the one shift costs 30000 at every pixel (toroidal), so best = paths * 30000 and the data
+    term's u16 store shows in a map.  With more shifts a cheaper one wins and the full cost reaches no map: a data term
+    saturated at 0x7000 passed every other case here (profiles/mutants/README.md, census_c)"""
+    w, h = 98, 28
+    left, right = cx.anti(w, h, 0)
+    plan = hip.StereoPlan(w, h, 1, 25, mode)
+    try:
+        for paths in (8, 4):
+            check_all(plan, left[None], right[None], 1, 25, 7, 32767, 32767, paths, mode, 1, 0, (mode, paths))
+        if mode == "toroidal":
+            web, best, _ = plan.sgm_wta(dev(left[None]), dev(right[None]), 7, 32767, 32767, 4, want_sub=True)
+            assert (host(web) == 1).all() and (host(best) == 4 * 30000).all()
+    finally:
+        plan.close()
+
+
+@pytest.mark.parametrize("mode", MODES)
 def test_sgm_bounds_with_four_paths_and_in_a_batch(hip, mode):
     """4 paths on the padded range; a batch of two pairs with distinct k, so that the volumes are reused between
     pairs at full range"""

@@ -1,0 +1,141 @@
+"""The mutation audit's data stays usable (tools/mutants.py, profiles/mutants/README.md): every mutant of
+tests/mutants/manifest.json is complete, its patch still fits the sources and touches the one file it names, its groups
+are GPU test files, and the recorded run (profiles/mutants/results.json) has a verdict for exactly the mutants that may
+run, with every survivor accounted for in the record.  Nothing is built here."""
+import json
+import re
+from pathlib import Path
+
+import pytest
+
+from tools import mutants as mt
+
+ROOT = Path(__file__).resolve().parent.parent
+RESULTS = ROOT / "profiles" / "mutants" / "results.json"
+README = ROOT / "profiles" / "mutants" / "README.md"
+MANIFEST = mt.manifest()
+IDS = [m["id"] for m in MANIFEST]
+VERDICTS = ("killed", "survived")
+# the nine mutants of the two earlier records, and the least the newest kernels get
+RECORDED = {"census_a", "census_b", "census_b2", "census_c", "poison_a", "poison_b", "poison_c", "poison_d", "poison_e"}
+NEWEST = {"B1", "B2", "B3", "B4", "N1", "N2", "N3", "N4", "C1", "C2", "U1", "U2", "U3", "U4", "W1", "W2"}
+
+
+@pytest.fixture(scope="module")
+def results():
+    return json.loads(RESULTS.read_text())
+
+
+@pytest.fixture(scope="module")
+def survivors_recorded():
+    """{(id, group): (kind, test id or None)} of the README's lines `- ID (group): equivalent, because ...` and
+    `- ID (group): closed by tests/file.py::test_name`"""
+    out = {}
+    for m in re.finditer(r"^- `?(\w+)`? \((\w+)\): (equivalent, because \S.*|closed by (tests/\S+?\.py)::(\w+).*)$",
+                         README.read_text(), re.M):
+        out[(m.group(1), m.group(2))] = ("closed", (m.group(4), m.group(5))) if m.group(4) else ("equivalent", None)
+    return out
+
+
+def test_the_manifest_names_each_mutant_once_and_the_ones_asked_for():
+    assert len(IDS) == len(set(IDS))
+    assert RECORDED | NEWEST <= set(IDS)
+    patches = {p.stem for p in mt.MUTDIR.glob("*.patch")}
+    assert patches == set(IDS), "a patch without an entry, or an entry without a patch"
+
+
+@pytest.mark.parametrize("m", MANIFEST, ids=IDS)
+def test_every_entry_is_complete(m):
+    for f in mt.FIELDS:
+        assert f in m, f
+    assert isinstance(m["run"], bool)
+    assert re.match(r"(k|sm)_\w+", m["kernel"])
+    for f in ("what", "reach"):
+        assert isinstance(m[f], str) and len(m[f]) > 10, f
+    assert "\n" not in m["what"], "one sentence"
+    assert (mt.B.CSRC / m["file"]).is_file()
+    assert m["groups"] and set(m["predicted"]) == set(m["groups"])
+    for name, p in m["predicted"].items():
+        assert p["verdict"] in VERDICTS, name
+        assert p["test"] if p["verdict"] == "killed" else p.get("why"), name
+    # the two earlier records keep their "new" and "old" groups; a newer mutant has one group, its unit's own modules
+    assert set(m["groups"]) == ({"new", "old"} if m["id"] in RECORDED else {"own"})
+
+
+def test_a_value_that_can_reach_an_address_is_never_run():
+    by_id = {m["id"]: m for m in MANIFEST}
+    assert by_id["poison_c"]["run"] is False and by_id["poison_c"]["reach"].startswith("YES")
+    for m in MANIFEST:
+        assert m["run"] or re.match(r"YES|STOPPED", m["reach"]), m["id"]
+
+
+@pytest.mark.parametrize("m", MANIFEST, ids=IDS)
+def test_every_patch_fits_the_sources_and_touches_the_file_it_names(m):
+    """(a refactoring that moves a mutated line fails here, not in the audit)"""
+    text = (mt.MUTDIR / f"{m['id']}.patch").read_text()
+    assert mt.patch_files(text) == [mt.CSRC_REL + m["file"]]
+    assert re.findall(r"^--- (\S+)", text, re.M) == ["a/" + mt.CSRC_REL + m["file"]]
+    source = (mt.B.CSRC / m["file"]).read_text()
+    mutated = mt.check_patch(m)
+    changed = sum(1 for ln in text.splitlines() if re.match(r"[+-](?![+-]{2} )", ln))
+    assert mutated != source and 1 <= changed <= 12, "a mutant is a handful of lines"
+    assert mt.units_of(m["file"]), "no translation unit would be rebuilt"
+
+
+def test_the_patch_check_refuses_a_patch_that_does_not_fit():
+    m = dict(MANIFEST[0])
+    text = (mt.MUTDIR / f"{m['id']}.patch").read_text()
+    source = (mt.B.CSRC / m["file"]).read_text()
+    with pytest.raises(ValueError):
+        mt.apply_patch(text, "// a line more\n" + source, "moved")
+    with pytest.raises(ValueError):
+        mt.apply_patch(text, source.replace("0x8000", "0x8001"), "edited")
+    assert mt.apply_patch(text, source, "fits") != source
+
+
+@pytest.mark.parametrize("m", MANIFEST, ids=IDS)
+def test_every_group_is_gpu_test_files(m):
+    for files in m["groups"].values():
+        assert files
+        for f in files:
+            path = ROOT / f
+            assert re.fullmatch(r"tests/test_\w+_gpu\.py", f) and path.is_file(), f
+            assert re.search(r"^pytestmark = pytest\.mark\.gpu|^@pytest\.mark\.gpu", path.read_text(), re.M), f
+
+
+def test_the_recorded_run_has_a_verdict_for_exactly_the_mutants_that_may_run(results):
+    assert "stopped" not in results, "the recorded run was ended by a child"
+    assert "tools/mutants.py" in results["command"]
+    want = {m["id"] for m in MANIFEST if m["run"]}
+    assert set(results["mutants"]) == want
+    for m in MANIFEST:
+        if not m["run"]:
+            continue
+        got = results["mutants"][m["id"]]
+        assert set(got) == set(m["groups"]), m["id"]
+        for name, files in m["groups"].items():
+            key = mt.group_key(files)
+            base = results["unmodified"][key]
+            assert base["verdict"] == "passed" and base["limit"] >= max(mt.MIN_LIMIT, 2 * base["seconds"])
+            v = got[name]
+            assert v["verdict"] in VERDICTS and v["files"] == key, (m["id"], name)
+            assert v["limit"] >= mt.MIN_LIMIT and v["seconds"] <= v["limit"]
+            assert (v["verdict"] == "killed") == bool(v.get("first_failure")), (m["id"], name)
+
+
+def test_every_survivor_is_equivalent_or_closed_in_the_record(results, survivors_recorded):
+    by_id = {m["id"]: m for m in MANIFEST}
+    for mid, groups in results["mutants"].items():
+        alive = [g for g, v in groups.items() if v["verdict"] == "survived"]
+        for g in alive:
+            assert (mid, g) in survivors_recorded, f"{mid} survived {g}: the record names it neither equivalent nor closed"
+            kind, test = survivors_recorded[(mid, g)]
+            if kind == "closed":
+                path = ROOT / test[0]
+                assert path.is_file() and re.search(rf"^def {test[1]}\(", path.read_text(), re.M), test
+                # what closes it killed it: another group of the same mutant holds that file and died
+                assert any(v["verdict"] == "killed" and test[0] in by_id[mid]["groups"][h]
+                           for h, v in groups.items()), (mid, g)
+        if alive and len(alive) == len(groups):
+            # killed by nothing: only an equivalent mutant may end so
+            assert all(survivors_recorded[(mid, g)][0] == "equivalent" for g in alive), mid

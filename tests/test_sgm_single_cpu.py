@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests import sgm_reference as sr
+from tests import sgm_single_patterns as sp
 from tests import sgm_single_reference as ss
 
 NEW = ("sm_sgm_wta_both", "sm_sgm_lr_single")
@@ -124,3 +125,46 @@ def test_left_maps_are_sgm_and_the_check_is_lr_check(mode):
         assert np.array_equal(e[md]["checked"], checked) and e[md]["rejected"] == rejected
         assert ((e[md]["sub_checked"] == 0) == (checked == 0)).all()
     assert e[0]["rejected"] >= e[1]["rejected"] > 0
+
+
+# ---------------------------------------------------------------------------
+# what the named cases of the GPU test can tell (tests/sgm_single_patterns.py)
+# ---------------------------------------------------------------------------
+
+def test_every_mistake_has_a_case_and_every_case_is_the_definition():
+    assert set(sp.MUTANT_CASE) == set(sp.MUTANTS) and set(sp.MUTANT_CASE.values()) <= set(sp.CASES)
+    for name in sp.CASES:
+        c, e = sp.inputs(name), sp.expected(name)
+        want = ss.both(c["left"], c["right"], c["d"], c["sw"], c["census"], c["p1"], c["p2"], c["paths"], c["mode"])
+        for k, v in zip(("best", "web", "sub", "best_right", "web_right"), want):
+            assert np.array_equal(e[k], v), (name, k)
+
+
+# the maps a mistake has to change on its case, and the ones it must leave alone
+TELLS = {"last_wins": {"web_right"}, "ghost_wraps": {"best_right", "web_right"}, "toroidal_clips": {"best_right", "web_right"},
+         "padding_joins": {"best", "web", "best_right", "web_right"}, "den_above_one": {"sub"}}
+
+
+@pytest.mark.parametrize("mutant", sp.MUTANTS)
+def test_the_named_case_tells_the_mistake_from_the_definition(mutant):
+    name = sp.MUTANT_CASE[mutant]
+    e, g = sp.expected(name), sp.mutant_maps(name, mutant)
+    changed = {k for k in e if not np.array_equal(e[k], g[k])}
+    assert changed == TELLS[mutant], (mutant, name, changed)
+
+
+def test_what_the_named_cases_are_made_of():
+    # the periodic pair ties three candidates of every right pixel; the padded case has one padded entry, in lane 63
+    s = sp.volume("periodic toroidal")
+    assert np.array_equal(s[:, :, 0], s[:, :, 8]) and np.array_equal(s[:, :, 0], s[:, :, 16])
+    assert sp.inputs("padded 63")["d"] == 63
+    for name in ("narrow toroidal", "narrow ghost"):
+        assert sp.inputs(name)["d"] > 3 * sp.inputs(name)["left"].shape[1]
+    # den = 1 comes as (S(d - 1), S(d + 1)) - best = (1, 0) only -- (0, 1) would make d - 1 the winner -- and gives q = 8
+    e, s = sp.expected("den one"), sp.volume("den one").astype(np.int64)
+    d = e["web"].astype(np.int64) - 1
+    inner = (e["web"] > 1) & (e["web"] < s.shape[-1])
+    lo = np.take_along_axis(s, np.clip(d - 1, 0, None)[..., None], -1)[..., 0] - e["best"]
+    hi = np.take_along_axis(s, np.clip(d + 1, None, s.shape[-1] - 1)[..., None], -1)[..., 0] - e["best"]
+    one = inner & (lo + hi == 1)
+    assert one.sum() >= 2 and (lo[one] == 1).all() and (e["sub"][one] == 16 * e["web"][one] + 8).all()

@@ -12,6 +12,7 @@ import torch
 from stereomatching_amd import capi
 from stereomatching_amd.capi import lib
 from tests import census_extreme_patterns as cx
+from tests import sgm_single_patterns as sp
 from tests import sgm_single_reference as ss
 from tests.guarded import guarded_input
 from tests.test_sgm_single_cpu import periodic_pair
@@ -211,6 +212,21 @@ def test_all_tie_and_periodic_tie_maps(hip, mode):
         _, web_right = check_both(plan, left[None], right[None], 20, 1, 7, 10, 120, 8, mode, (mode, "periodic"))
         if mode == "toroidal":
             assert (host(web_right) == 1).all()
+    finally:
+        plan.close()
+
+
+@pytest.mark.parametrize("name", sp.CASES)
+def test_named_cases_are_exact(hip, name):
+    """the cases of tests/sgm_single_patterns.py: each tells one mistake of the definition from the definition
+    (test_sgm_single_cpu.py shows which), so an exact pass rules that mistake out in the kernel"""
+    c = sp.inputs(name)
+    h, w = c["left"].shape
+    plan = hip.StereoPlan(w, h, c["d"], c["sw"], c["mode"])
+    try:
+        # (copies: the cases' arrays are read-only)
+        check_both(plan, np.array(c["left"][None]), np.array(c["right"][None]), c["d"], c["sw"], c["census"], c["p1"],
+                   c["p2"], c["paths"], c["mode"], (name,))
     finally:
         plan.close()
 

@@ -185,3 +185,54 @@ def test_sgm_case_is_make_pair_seed_7():
     left, right = make_pair(c["w"], c["h"], c["d"], seed=7)
     e = up.sgm_case("70x20 D24 K1")
     assert np.array_equal(e["left"][0], left) and np.array_equal(e["right"][0], right)
+
+
+# ---------------------------------------------------------------------------
+# the definition with one mistake differs from the definition on a case the GPU runs
+# ---------------------------------------------------------------------------
+
+def test_every_mistake_names_a_case_the_gpu_runs():
+    assert set(up.MUTANT_CASE) == set(up.MUTANTS)
+    for kind, (mode, name, which) in up.MUTANT_CASE.items():
+        if kind in up.ELEMENT_MUTANTS:
+            assert (mode, name, which) in up.FILTER_CASES, kind
+        elif mode == "census":
+            assert name in up.CENSUS_CASES and which in up.MAPS, kind
+        else:
+            assert name in up.SGM_CASES, kind
+
+
+@pytest.mark.parametrize("mutant", up.SECOND_MUTANTS)
+def test_the_named_case_tells_a_runner_up_mistake_from_the_definition(mutant):
+    mode, name, which = up.MUTANT_CASE[mutant]
+    if mode == "census":
+        e = up.census_case(name)
+        want_b, want_w = e["second"][which]
+        got = [up.mutant_runner_up(e["volume"][q], e["maps"][which][q], mutant) for q in range(up.PAIRS)]
+        got_b, got_w = np.stack([g[0] for g in got]), np.stack([g[1] for g in got])
+    else:
+        c, e = up.SGM_CASES[name], up.sgm_case(name)
+        from tests import sgm_reference as sg
+        s = sg.aggregate(sg.data_term(e["left"][0], e["right"][0], c["d"], c["sw"], c["census"], c["mode"]),
+                         c["p1"], c["p2"], c["paths"])
+        want_b, want_w = e["best2"][0], e["web2"][0]
+        assert np.array_equal(ur.runner_up(s, e["web"][0])[1], want_w)
+        got_b, got_w = up.mutant_runner_up(s, e["web"][0], mutant)
+    assert (got_w != want_w).sum() >= 3, (mutant, name)
+    if mutant != "last_wins":
+        assert (got_b != want_b).sum() >= 3, (mutant, name)            # (a tie moves the shift, not the cost)
+
+
+@pytest.mark.parametrize("mutant", up.ELEMENT_MUTANTS)
+def test_the_named_case_tells_an_element_wise_mistake_from_the_definition(mutant):
+    web, best, best2, *_ = up.filter_inputs(up.MUTANT_CASE[mutant])
+    differs = set()
+    for ratio in up.RATIOS:                                            # the ratios the GPU test runs
+        out, rejected = ur.uniqueness_filter(web, best, best2, ratio)
+        m_out, m_rejected, m_conf = up.mutant_elementwise(web, best, best2, ratio, mutant)
+        differs |= {"out"} if not np.array_equal(out, m_out) else set()
+        differs |= {"rejected"} if rejected != m_rejected else set()
+    differs |= {"confidence"} if not np.array_equal(ur.confidence(web, best, best2), m_conf) else set()
+    want = {"filter_strict": {"out", "rejected"}, "filter_rival_needed": {"out", "rejected"},
+            "count_takes_invalid": {"rejected"}, "confidence_256": {"confidence"}}[mutant]
+    assert differs == want, (mutant, differs)

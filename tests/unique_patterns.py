@@ -117,6 +117,51 @@ def filter_inputs(case):
     return e["web"], e["best"], e["best2"], c["w"], c["h"], c["d"]
 
 
+# ---------------------------------------------------------------------------
+# the definition with one mistake (test_unique_cpu.py: each differs from the definition on the case MUTANT_CASE names,
+# which test_unique_gpu.py runs exactly)
+# ---------------------------------------------------------------------------
+
+SECOND_MUTANTS = ("one_above_stays", "one_below_stays", "last_wins", "range_unchecked")
+ELEMENT_MUTANTS = ("filter_strict", "filter_rival_needed", "count_takes_invalid", "confidence_256")
+MUTANTS = SECOND_MUTANTS + ELEMENT_MUTANTS
+# a runner-up mistake: a census case and one of its MAPS, or ("sgm", case); an element-wise one: a case of FILTER_CASES
+MUTANT_CASE = {"one_above_stays": ("census", "33x17 D45", "own"), "one_below_stays": ("sgm", "70x20 D24 K1", None),
+               "last_wins": ("census", "64x16 D130", "zeros"), "range_unchecked": ("census", "65x20 D16", "sweep"),
+               "filter_strict": ("census", "64x16 D130", "own"), "filter_rival_needed": ("sgm", "20x9 D3", None),
+               "count_takes_invalid": ("census", "33x17 D45", "checked"), "confidence_256": ("sgm", "70x20 D100 K2", None)}
+
+
+def mutant_runner_up(vol, web, kind):
+    """-> (best2, web2) like unique_reference.runner_up, with the mistake `kind` of SECOND_MUTANTS"""
+    assert kind in SECOND_MUTANTS
+    vol = np.asarray(vol, np.int64)
+    D = vol.shape[-1]
+    s = np.asarray(web).astype(np.int64)
+    has = np.ones_like(s, bool) if kind == "range_unchecked" else (s >= 1) & (s <= D)
+    off = np.arange(D, dtype=np.int64) - (s[..., None] - 1)
+    lo, hi = (-1, 0) if kind == "one_above_stays" else (0, 1) if kind == "one_below_stays" else (-1, 1)
+    v = np.where(has[..., None] & (off >= lo) & (off <= hi), ur.NONE, vol)
+    k = D - 1 - np.argmin(v[..., ::-1], axis=-1) if kind == "last_wins" else np.argmin(v, axis=-1)
+    b = np.take_along_axis(v, k[..., None], -1)[..., 0]
+    none = b == ur.NONE
+    return np.where(none, -1, b).astype(np.int32), np.where(none, 0, k + 1).astype(np.int32)
+
+
+def mutant_elementwise(web, best, best2, ratio, kind):
+    """-> (out, rejected, confidence) like unique_reference's, with the mistake `kind` of ELEMENT_MUTANTS"""
+    assert kind in ELEMENT_MUTANTS
+    web = np.asarray(web, np.int32)
+    b, b2 = np.asarray(best).astype(np.int64), np.asarray(best2).astype(np.int64)
+    passes = b2 * (100 - ratio) > b * 100 if kind == "filter_strict" else b2 * (100 - ratio) >= b * 100
+    keep = (web != 0) & (passes if kind == "filter_rival_needed" else (b2 < 0) | passes)
+    rejected = int((~keep).sum()) if kind == "count_takes_invalid" else int(((web != 0) & ~keep).sum())
+    scale = 256 if kind == "confidence_256" else 255
+    c = np.minimum(255, np.where(b2 > 0, (scale * (b2 - b)) // np.maximum(b2, 1), 255))
+    c = np.where(web == 0, 0, np.where(b2 < 0, 255, np.where(b2 <= b, 0, c)))
+    return np.where(keep, web, 0).astype(np.int32), rejected, c.astype(np.uint8)
+
+
 def extremes(w=37, h=11, seed=3):
     """raw int32 triples (web, best, best2) [2][H][W]: every combination of the extreme values, then noise"""
     vals = np.array([I32_MIN, I32_MIN + 1, -30000, -1, 0, 1, 2, 29999, 30000, 1 << 23, (1 << 23) + 1, I32_MAX - 1, I32_MAX],
