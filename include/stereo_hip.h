@@ -753,6 +753,54 @@ int sm_weighted_median(sm_plan *plan, const void *d_in, int map_type, const uint
                        const uint16_t weights[256], int flags, int fill_min_weight, int pairs,
                        void *d_out, int32_t *d_filled, void *stream);
 
+/* ---- edge-aware smoother: PARITY UNPINNED --------------------------------- *
+ * New work (no reference counterpart): the global, edge-aware, confidence-weighted filter beside the
+ * local ones above.  The fast global smoother (Min et al., TIP 2014) used the way OpenCV's DisparityWLSFilter uses it:
+ * a weighted-least-squares problem whose smoothness weights come from the guide image is solved for confidence x
+ * disparity and for confidence, and the first result is divided by the second.  The result is a dense subpixel map,
+ * smooth inside surfaces, broken at the image's edges, deaf to low-confidence outliers, with holes filled from their
+ * own surface at any distance.  matcher (+ runner-up) -> sm_confidence -> check -> speckle -> smoother -> reproject.
+ * tests/wls_reference.py is the executable form of this definition; the library equals it bit for bit.
+ *   Maps are [pairs][H][W]; map_type and out_type are each SM_MAP_I32 (web) or SM_MAP_I16 (sub), in any combination.  A
+ *     pixel is valid iff its value v != 0; its value in 1/16 steps is the exact double u = 16 v (int32) or u = v
+ *     (int16); any value is legal.  d_guide: u8 [pairs][H][W].  d_conf: u8 [pairs][H][W], or NULL for a map of 255s.
+ *   weights: 256 uint16_t ON THE HOST, as for sm_weighted_median; any table is legal, zeros included.  It is passed to
+ *     the kernels by value: a captured graph holds the table of capture time.  lambda: finite, 0 <= lambda <= 2^20; it
+ *     multiplies the table's entries as they are (with guide_weights(sigma, peak) pass lambda / peak).  iterations T:
+ *     1 .. 8.
+ *   Start: c(p) = (double)conf(p) where in(p) != 0, else 0; N = c u, M = c (exact integers).
+ *   For t = 0 .. T-1, with lambda_t = ((1.5 lambda) 4^(T-1-t)) / (4^T - 1.0) computed on the host in double in that
+ *     order: every row is solved, then every column, for N and M alike.
+ *   One line f_0 .. f_(n-1): links l_i = lambda_t * (double)weights[|g_i - g_(i+1)|] for i = 0 .. n-2, l_(-1) = l_(n-1)
+ *     = 0; a_i = -l_(i-1), k_i = -l_i, b_i = (1.0 + l_(i-1)) + l_i.
+ *     Forward, i = 0 .. n-1: den_i = b_i - cp_(i-1) a_i; inv_i = 1.0 / den_i; cp_i = k_i inv_i; f'_i = (f_i - f'_(i-1)
+ *     a_i) inv_i (the terms with index -1 are absent at i = 0: den_0 = b_0, f'_0 = f_0 inv_0).
+ *     Backward: U_(n-1) = f'_(n-1); U_i = f'_i - cp_i U_(i+1).
+ *     Every operation is an IEEE double operation rounded on its own, in the order written.  den_i >= 1 always; no
+ *     intermediate of M is negative.  A line of one element is returned unchanged.
+ *   r(p) = N(p) / M(p) where M(p) > 0, else r = 0.0.  An int16 output receives rint(r) (ties to even) saturated to
+ *     int16; an int32 output rint(r / 16), saturated.  A result of 0 reads as invalid, as everywhere (maps of the
+ *     library's matchers have u >= 16 at valid pixels, and so have their averages).
+ *   flags = SM_WLS_NO_FILL: the output and d_raw are 0 where in(p) = 0.
+ *   d_raw: NULL or [pairs][H][W] doubles that receive r.  d_filled: NULL or one int32 per pair, the number of pixels
+ *     that were 0 and are no longer.
+ * Refused before any device call, naming the function: a NULL plan, map, guide, weights or output; an unknown map_type
+ * or out_type; a lambda that is not finite or outside the range; iterations outside 1 .. 8; unknown flag bits; pairs
+ * outside 1 .. max_pairs; any overlap among the buffers, except that d_out == d_in is allowed when the two types are
+ * equal (a pixel's input is read before its output is written).
+ * Workspace: three double planes per pair slot (N, M, cp), 24 * max_pairs * W * H bytes (199 MB for one 4K pair),
+ * allocated by sm_plan_reserve_wls or by the first call and counted in sm_plan_workspace_bytes from then on.  Inside
+ * a stream capture before the reservation the call is refused with SM_ERR_ARG (the capture stays valid); after it the
+ * call can be captured: no copy, no synchronisation.  The call runs in `stream` order and uses nothing the pipelined
+ * lanes use.                                                                                                       */
+#define SM_WLS_NO_FILL 1
+/* adds: the smoothed map of d_in -> d_out (of out_type) */
+int sm_wls_filter(sm_plan *plan, const void *d_in, int map_type, const uint8_t *d_conf, const uint8_t *d_guide,
+                  const uint16_t weights[256], double lambda, int iterations, int flags, int pairs,
+                  void *d_out, int out_type, double *d_raw, int32_t *d_filled, void *stream);
+/* adds: allocates the smoother's workspace now; idempotent */
+int sm_plan_reserve_wls(sm_plan *plan);
+
 /* ---- half-resolution path: PARITY UNPINNED -------------------------------- *
  * New work (no reference counterpart): SGM on a large pair costs a volume of W x H x shifts.  Matching
  * at half the size with half the shifts is an eighth of it; the coarse map is then brought back to the fine size

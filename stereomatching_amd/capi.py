@@ -21,6 +21,7 @@ SM_TOROIDAL, SM_GHOST = 0, 1
 SM_WEB_I32, SM_WEB_U16, SM_WEB_U8 = 0, 1, 2
 SM_MAP_I32, SM_MAP_I16 = 0, 1
 SM_WMED_FILL = 1
+SM_WLS_NO_FILL = 1
 SM_REDUCE_BOX, SM_REDUCE_BINOMIAL = 0, 1
 SM_UP_FILL = 1
 SM_CLASS_VALID, SM_CLASS_OCCLUDED, SM_CLASS_MISMATCHED = 0, 1, 2
@@ -191,6 +192,8 @@ _SIGNATURES = {
     "sm_sub_mask": (_int, [_vp, _vp, _vp, _int, _vp]),
     "sm_plan_reserve_filter": (_int, [_vp]),
     "sm_weighted_median": (_int, [_vp, _vp, _int, _vp, _int, _u16p, _int, _int, _int, _vp, _vp, _vp]),
+    "sm_wls_filter": (_int, [_vp, _vp, _int, _vp, _vp, _u16p, _dbl, _int, _int, _int, _vp, _int, _vp, _vp, _vp]),
+    "sm_plan_reserve_wls": (_int, [_vp]),
     "sm_reduce_half": (_int, [_vp, _vp, _int, _int, _vp, _vp]),
     "sm_upsample_double": (_int, [_vp, _vp, _int, _vp, _vp, _u16p, _int, _int, _vp, _vp]),
     "sm_occlusion_classify": (_int, [_vp, _vp, _vp, _int, _vp, _vp]),

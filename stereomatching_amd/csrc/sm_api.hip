@@ -297,6 +297,10 @@ static size_t ws_census_bytes(const sm_plan *plan)      // both images of max_pa
     return (size_t)2 * plan->max_pairs * plan->width * plan->height * sizeof(uint64_t);
 }
 static size_t ws_filter_bytes(const sm_plan *plan) { return 2 * sm_lr_map_bytes(plan); }
+static size_t ws_wls_bytes(const sm_plan *plan)         // N, M and cp: a double each per pixel of max_pairs maps
+{
+    return (size_t)3 * plan->max_pairs * plan->width * plan->height * sizeof(double);
+}
 
 static const struct {
     size_t member;                          // offsetof(sm_plan, the pointer)
@@ -315,6 +319,7 @@ static const struct {
     /* SM_WS_INTERP  */ {offsetof(sm_plan, d_interp), sm_itp_bytes, false, "directional maps and carries of the interpolation"},
     /* SM_WS_CLOUD   */ {offsetof(sm_plan, d_cloud), sm_cloud_bytes, false, "tile counts of the point cloud"},
     /* SM_WS_SGM_NEAR */ {offsetof(sm_plan, d_sgm_near), sm_sgm_near_volume_bytes, false, "banded SGM volumes"},
+    /* SM_WS_WLS     */ {offsetof(sm_plan, d_wls), ws_wls_bytes, false, "planes of the edge-aware smoother"},
 };
 
 static void *&ws_ptr(const sm_plan *plan, int r) { return *(void **)((char *)plan + ws_rows[r].member); }

@@ -712,6 +712,41 @@ class StereoPlan:
                                      self._stream()))
         return (out, filled) if want_filled else out
 
+    # ---- edge-aware smoother (after the speckle filter; its output is dense) --------
+    def reserve_wls(self):
+        """The smoother's workspace (three double planes per pixel of max_pairs maps), allocated now: keeps the
+        allocation out of timed paths and out of stream captures."""
+        check(lib.sm_plan_reserve_wls(self._h))
+
+    def wls_filter(self, map, guide, weights, lam, iterations=3, conf=None, fill=True, out=None, out_dtype=None,
+                   want_raw=False, want_filled=False):
+        """Confidence-weighted edge-aware smoother (sm_wls_filter) of an int32 web map or an int16 sub map -> the
+        smoothed map of out_dtype (default: the map's), then the raw quotient (float64, sixteenths of a pixel) with
+        want_raw, then the filled pixels per pair with want_filled.  guide: uint8 images of the map's shape; weights: 256
+        integers, the smoothness weight of two neighbours by their gray difference in the guide (guide_weights; lam
+        multiplies the entries as they are, so pass lam / peak with it); conf: uint8 confidence map (confidence()) or
+        None for 255 everywhere.  fill=False leaves invalid pixels 0.  out=map smooths in place (same dtype)."""
+        map = self._filter_map(map, "map")
+        pairs = map.shape[0]
+        guide = self._images(guide, torch.uint8, "guide")
+        if guide.shape[0] != pairs:
+            raise ValueError(f"guide: {guide.shape[0]} images for {pairs} pairs")
+        if conf is not None:
+            conf = self._images(conf, torch.uint8, "conf")
+            if conf.shape[0] != pairs:
+                raise ValueError(f"conf: {conf.shape[0]} maps for {pairs} pairs")
+        out_dtype = out_dtype or (out.dtype if out is not None else map.dtype)
+        if out_dtype not in MAP_TYPES:
+            raise ValueError(f"out_dtype: need int32 or int16, got {out_dtype}")
+        out = self._out(out, pairs, "out", out_dtype)
+        raw = torch.empty((pairs, self.height, self.width), dtype=torch.float64, device=self._dev) if want_raw else None
+        filled = torch.empty(pairs, dtype=torch.int32, device=self._dev) if want_filled else None
+        check(lib.sm_wls_filter(self._h, _ptr(map), MAP_TYPES[map.dtype], _ptr(conf), _ptr(guide), capi.w256(weights),
+                                float(lam), int(iterations), 0 if fill else capi.SM_WLS_NO_FILL, pairs, _ptr(out),
+                                MAP_TYPES[out_dtype], _ptr(raw), _ptr(filled), self._stream()))
+        res = (out,) + ((raw,) if want_raw else ()) + ((filled,) if want_filled else ())
+        return res if len(res) > 1 else out
+
     # ---- half-resolution path (reduce -> a matcher on a plan of half_shape() -> upsample) ---
     def half_shape(self):
         """(cw, ch) = ((W + 1) >> 1, (H + 1) >> 1): the size reduce_half writes and upsample_double reads; the coarse
