@@ -121,3 +121,41 @@ def z_crossing_calibration(w, h):
 def far_calibration(w, h):
     """finite everywhere, but a new projection that moves pixels by more than 1023: REL16 must be refused"""
     return rr.calibration(float(w), float(w), 0.5 * w, 0.5 * h, new_cx=0.5 * w - 1100.0)
+
+
+# ---------------------------------------------------------------------------
+# the REL16 refusal, one axis at a time (the mutation audit, profiles/mutants/README.md: R7)
+# ---------------------------------------------------------------------------
+EDGE_W, EDGE_H = 8, 3               # focal length 8: every quotient and product below is exact in binary
+
+
+def shift_calibration(w, h, sx, sy):
+    """an undistorted, unrotated camera whose new projection moves every pixel by exactly (sx, sy) source pixels
+    (multiples of 1/32 at a focal length that is a power of two): the displacement is (32 sx, 32 sy) everywhere"""
+    return rr.calibration(float(w), float(w), 0.5 * w, 0.5 * h, new_cx=0.5 * w - sx, new_cy=0.5 * h - sy)
+
+
+def refusal_edges(w=EDGE_W, h=EDGE_H):
+    """name -> (calibration, fits REL16): a displacement on either side of each end of int16, along ONE axis with the
+    other at 0, and one of 1100 pixels either way along y (far_calibration, which moves along x, turned by a quarter)"""
+    out = {}
+    for axis in "xy":
+        for d, fits in ((32767, True), (32768, False), (-32768, True), (-32769, False), (35200, False), (-35200, False)):
+            s = d / 32.0
+            out[f"d{axis} {d}"] = (shift_calibration(w, h, s if axis == "x" else 0.0, s if axis == "y" else 0.0), fits)
+    return out
+
+
+OVERFLOW_MISTAKES = ["overflow looks at dx only", "overflow looks at dy only"]
+
+
+def rel16_refused(mx, my, mistake=None):
+    """does rr.rel_map refuse these positions?  With `mistake` (one of OVERFLOW_MISTAKES): would a builder that makes
+    it refuse them"""
+    assert mistake is None or mistake in OVERFLOW_MISTAKES
+    mx, my = np.asarray(mx, np.int64), np.asarray(my, np.int64)
+    h, w = mx.shape
+    dx = mx - rr.ONE * np.arange(w, dtype=np.int64)[None, :]
+    dy = my - rr.ONE * np.arange(h, dtype=np.int64)[:, None]
+    seen = {None: (dx, dy), "overflow looks at dx only": (dx,), "overflow looks at dy only": (dy,)}[mistake]
+    return any(d.min() < -32768 or d.max() > 32767 for d in seen)

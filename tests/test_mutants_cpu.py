@@ -19,6 +19,15 @@ VERDICTS = ("killed", "survived")
 # the nine mutants of the two earlier records, and the least the newest kernels get
 RECORDED = {"census_a", "census_b", "census_b2", "census_c", "poison_a", "poison_b", "poison_c", "poison_d", "poison_e"}
 NEWEST = {"B1", "B2", "B3", "B4", "N1", "N2", "N3", "N4", "C1", "C2", "U1", "U2", "U3", "U4", "W1", "W2"}
+# the second audit: the stages around the matchers (smoother, interpolation, post-filters, pyramid, rectification,
+# subpixel refinement), each against its unit's own GPU module
+AROUND = ({f"G{i}" for i in range(1, 9)} | {f"I{i}" for i in range(1, 7)} | {f"F{i}" for i in range(1, 7)}
+          | {f"P{i}" for i in range(1, 8)} | {f"R{i}" for i in range(1, 8)} | {f"X{i}" for i in range(1, 6)})
+AROUND_OWN = {"G": "tests/test_wls_gpu.py", "I": "tests/test_interp_gpu.py", "F": "tests/test_filter_gpu.py",
+              "P": "tests/test_pyramid_gpu.py", "R": "tests/test_rectify_gpu.py", "X": "tests/test_subpix_gpu.py"}
+# the one newer mutant with a second group: the row scan's carry needs more than 64 chunks, which only the module of
+# the loops' second turns has
+SECOND_GROUP = {"I2": {"turns": ["tests/test_second_turns_gpu.py"]}}
 
 
 @pytest.fixture(scope="module")
@@ -39,7 +48,8 @@ def survivors_recorded():
 
 def test_the_manifest_names_each_mutant_once_and_the_ones_asked_for():
     assert len(IDS) == len(set(IDS))
-    assert RECORDED | NEWEST <= set(IDS)
+    assert RECORDED | NEWEST | AROUND <= set(IDS)
+    assert len(AROUND) == 39
     patches = {p.stem for p in mt.MUTDIR.glob("*.patch")}
     assert patches == set(IDS), "a patch without an entry, or an entry without a patch"
 
@@ -59,7 +69,13 @@ def test_every_entry_is_complete(m):
         assert p["verdict"] in VERDICTS, name
         assert p["test"] if p["verdict"] == "killed" else p.get("why"), name
     # the two earlier records keep their "new" and "old" groups; a newer mutant has one group, its unit's own modules
-    assert set(m["groups"]) == ({"new", "old"} if m["id"] in RECORDED else {"own"})
+    # (and I2 the one second group named above)
+    extra = SECOND_GROUP.get(m["id"], {})
+    assert set(m["groups"]) == ({"new", "old"} if m["id"] in RECORDED else {"own"} | set(extra))
+    for name, files in extra.items():
+        assert m["groups"][name] == files
+    if m["id"] in AROUND:
+        assert m["groups"]["own"] == [AROUND_OWN[m["id"][0]]], "a mutant of the second audit runs against its unit's module"
 
 
 def test_a_value_that_can_reach_an_address_is_never_run():

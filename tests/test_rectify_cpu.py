@@ -213,6 +213,33 @@ def test_rel16_is_refused_where_a_displacement_leaves_int16():
     assert rr.rel_map(np.array([[32767, -32768 + 32]]), np.zeros((1, 2), np.int64)).tolist() == [[[32767, 0], [-32768, 0]]]
 
 
+def test_the_refusal_edges_are_what_they_say_and_tell_a_flag_that_looks_at_one_axis():
+    """(the mutation audit's R7: the cases of test_map_build_where_z_crosses_zero_and_the_rel16_refusal overflow along x
+    or along both axes, so a builder whose flag looks at dx alone passed them)"""
+    w, h = rp.EDGE_W, rp.EDGE_H
+    edges = rp.refusal_edges()
+    assert len(edges) == 12
+    for name, (c, fits) in edges.items():
+        axis, d = name[1], int(name.split()[1])
+        mx, my = rr.build_positions(c, w, h)
+        dx, dy = mx - rr.ONE * np.arange(w)[None, :], my - rr.ONE * np.arange(h)[:, None]
+        moved, still = (dx, dy) if axis == "x" else (dy, dx)
+        assert (moved == d).all() and (still == 0).all(), name        # exactly d along one axis, 0 along the other
+        assert rp.rel16_refused(mx, my) == (not fits), name
+        if fits:
+            assert rr.build_map(c, w, h, "rel16").dtype == np.int16
+        else:
+            with pytest.raises(ValueError, match="abs32"):
+                rr.build_map(c, w, h, "rel16")
+        # the flag that looks at the other axis alone lets this map through; the one that looks at this axis does not
+        this, other = rp.OVERFLOW_MISTAKES[axis == "y"], rp.OVERFLOW_MISTAKES[axis == "x"]
+        assert rp.rel16_refused(mx, my, this) == (not fits) and not rp.rel16_refused(mx, my, other), name
+    # the cases the GPU module had before cannot tell "dx only": both are refused with it as without it
+    for c in (rp.far_calibration(320, 48), rp.z_crossing_calibration(320, 48)):
+        mx, my = rr.build_positions(c, 320, 48)
+        assert rp.rel16_refused(mx, my) and rp.rel16_refused(mx, my, "overflow looks at dx only")
+
+
 def test_smooth_calibration_fits_rel16_at_4k():
     """the claim behind the REL16 format: a 4K camera with k1 = -0.12 and a 0.02 rad rotation stays inside int16"""
     for side in (0, 1):

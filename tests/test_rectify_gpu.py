@@ -249,6 +249,31 @@ def test_map_build_where_z_crosses_zero_and_the_rel16_refusal(hip):
         plan.close()
 
 
+def test_rel16_refusal_looks_at_each_axis_on_its_own(hip):
+    """A displacement on either side of each end of int16 along ONE axis, the other at 0 (rp.refusal_edges;
+    test_rectify_cpu.py shows that a flag which looks at one axis alone gets these wrong).  The cases above overflow
+    along x or along both: a builder that never looked at dy passed them (profiles/mutants/README.md, R7)."""
+    w, h = rp.EDGE_W, rp.EDGE_H
+    plan = plan_for(hip, w, h)
+    try:
+        for name, (c, fits) in rp.refusal_edges().items():
+            want = rr.build_map(c, w, h, "abs32")
+            got = host(plan.rectify_map(c, "abs32"))
+            assert np.array_equal(got, want), (name, np.argwhere(got != want)[:4].tolist())
+            if fits:
+                want = rr.build_map(c, w, h, "rel16")
+                got = host(plan.rectify_map(c, "rel16"))
+                assert got.dtype == np.int16 and np.array_equal(got, want), (name, np.argwhere(got != want)[:4].tolist())
+            else:
+                with pytest.raises(ValueError):
+                    rr.build_map(c, w, h, "rel16")
+                with pytest.raises(capi.StereoHipError, match="SM_RMAP_ABS32") as err:
+                    plan.rectify_map(c, "rel16")
+                assert err.value.code == capi.SM_ERR_ARG, name
+    finally:
+        plan.close()
+
+
 def test_smooth_calibration_at_4k(hip):
     w, h = 3840, 2160
     plan = plan_for(hip, w, h)
