@@ -52,7 +52,7 @@ $(DEVSTAMP): FORCE
 	@mkdir -p $(dir $@)
 	@if [ "$$(cat $@ 2>/dev/null)" != "$(HIPFLAGS_BARE)" ]; then rm -f $(dir $@)*.o; echo "$(HIPFLAGS_BARE)" > $@; fi
 FORCE:
-stereomatching_amd/obj/product/%.o: $(CSRC)/%.hip $(CSRC)/sm_internal.h $(CSRC)/sm_entry.h $(CSRC)/sm_match_bs_kernel.h $(CSRC)/sm_bs_network.h $(CSRC)/sm_bs_ops.h $(CSRC)/sm_cost.h $(CSRC)/sm_census.h $(CSRC)/sm_census_wta_body.h $(CSRC)/sm_sgm_path_body.h $(CSRC)/sm_device.h $(CSRC)/sm_geom.h $(CSRC)/sm_plan_model.h include/stereo_hip.h $(DEVSTAMP)
+stereomatching_amd/obj/product/%.o: $(CSRC)/%.hip $(CSRC)/sm_internal.h $(CSRC)/sm_entry.h $(CSRC)/sm_match_bs_kernel.h $(CSRC)/sm_bs_network.h $(CSRC)/sm_bs_ops.h $(CSRC)/sm_cost.h $(CSRC)/sm_census.h $(CSRC)/sm_census_wta_body.h $(CSRC)/sm_sgm_path_body.h $(CSRC)/sm_near_tile_body.h $(CSRC)/sm_device.h $(CSRC)/sm_geom.h $(CSRC)/sm_plan_model.h include/stereo_hip.h $(DEVSTAMP)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(DEVLIB): $(DEVOBJ)
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC $^ -o $@

@@ -1,7 +1,8 @@
 // sm_census.h -- shared between the translation units of the census cost mode: sm_census.hip (transform, arg-min,
-// refinement), sm_census_near.hip (the guided re-search) and sm_unique.hip (the runner-up's entry point).  Host
-// declarations and constants only: the kernels stay in their units, and the other two reach the mode's argument
-// checks, descriptors and launches through the functions below.
+// refinement), sm_census_near.hip (the guided re-search) and sm_unique.hip (the runner-up's entry point), and with
+// sm_sgm_near.hip, whose data term is the guided re-search's.  Host declarations and constants only: the kernels stay
+// in their units (a text two units share: sm_near_tile_body.h), and the others reach the mode's argument checks,
+// descriptors and launches through the functions below.
 #pragma once
 
 #include "sm_entry.h"
@@ -10,6 +11,8 @@ typedef unsigned long long u64;
 
 #define SMN_TX 64          // transform, near: columns per workgroup
 #define SMN_TR 16          // transform, near: rows per workgroup (4 per lane)
+#define SMN_NQ 14          // near: positions per lane at most ((64 + 24) * (16 + 24) / 256, rounded up)
+#define SMN_NR 10          // near: rows of positions per wave at most ((16 + 24) / 4)
 
 // sm_census.hip.  (sm_census_descriptors, which SGM calls as well, is declared in sm_internal.h.)
 // what every census entry checks besides its pointers (before any device call)
@@ -32,4 +35,28 @@ struct CensusMode : sm_mode {
     {
         return sm_census_wta_launch(c.plan, cw, mirror, c.pairs, web, best, c.st);
     }
+};
+
+// sm_census_near.hip, for banded SGM (sm_sgm_near.hip) as well: what the two data terms over the shifts within `radius`
+// of a prior map share besides their kernel text (sm_near_tile_body.h).
+// The tile walk's view of a plan: the first fields of both kernels' parameter structs
+struct NearTileGeom {
+    int w, h, D;
+    int n, half;
+    int radius;
+    int sw, sh;             // positions of a tile: 64 + n - 1 columns, 16 + n - 1 rows
+    int tiles_x, tiles_y;
+    long long side;         // descriptors from side 0 (left) to side 1 (right) of the census workspace
+};
+// fills *g and the LDS bytes of a launch; refuses, as `what` ("census near", "sgm near"), a tile the kernels cannot hold
+int sm_near_tile_geom(const sm_plan *plan, int radius, const char *what, NearTileGeom *g, size_t *lds);
+// the prior maps of a call (one for each direction it runs) and its radius: a base of both modes
+struct NearPriors {
+    int radius;
+    const i32 *prior, *prior_right;
+    int inputs(const sm_call &c, bool left, bool right) const;
+    int radius_arg(const char *me) const;               // outside 1..4 (needs no plan)
+    // every output against the images and the priors: the int32 maps, the counts, and one more output of another size
+    int apart(const sm_call &c, const i32 *const *outs, int n_outs, const i32 *rejected, const void *extra = nullptr,
+              size_t extra_bytes = 0) const;
 };

@@ -225,6 +225,16 @@ int sm_sgm_second_pass(const sm_plan *plan, int cw, int p1, int p2, int paths, i
 // full aggregate (entries d >= num_shifts are not costs: wrapped sums of the path kernel's padding value)
 int sm_sgm_volume_pass(const sm_plan *plan, int cw, int p1, int p2, int paths, int pair, const i32 **S, int *Dp,
                        hipStream_t st);
+// SGM's directions in stream order, for sm_sgm.hip and sm_sgm_near.hip (integer sums: the order changes nothing):
+// direction r of `paths` (8: all of them; 4: the two axes, both ways) and the lines it has in a w x h image
+static inline void sm_sgm_direction(int paths, int r, int w, int h, int *dx, int *dy, int *lines)
+{
+    static const int dirs[8][2] = {{1, 0}, {0, 1}, {1, 1}, {-1, 1}, {1, -1}, {-1, -1}, {0, -1}, {-1, 0}};
+    static const int four[4] = {0, 1, 6, 7};
+    const int *dir = dirs[paths == 4 ? four[r] : r];
+    *dx = dir[0]; *dy = dir[1];
+    *lines = *dy == 0 ? h : *dx == 0 ? w : w + h - 1;
+}
 // sm_filter.hip, for sm_sgm_lr: k_sgm_sub_mask, sub = 0 where web = 0, over n elements
 int sm_sub_mask_launch(const i32 *web, int16_t *sub, long long n, hipStream_t st);
 

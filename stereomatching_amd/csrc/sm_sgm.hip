@@ -294,8 +294,6 @@ static const void *sgm_path_ptr(int mode)
 static int sgm_paths_launch(const sm_plan *plan, int p1, int p2, int paths, bool mirror, int pair, i32 *web, i32 *best,
                             int16_t *sub, i32 *web2, i32 *best2, hipStream_t st, bool keep = false)
 {
-    static const int dirs[8][2] = {{1, 0}, {0, 1}, {1, 1}, {-1, 1}, {1, -1}, {-1, -1}, {0, -1}, {-1, 0}};
-    static const int four[4] = {0, 1, 6, 7};
     SgmPathGeom g;
     g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts; g.Dp = sgm_padded_shifts(plan);
     g.p1 = p1; g.p2 = p2;
@@ -305,9 +303,7 @@ static int sgm_paths_launch(const sm_plan *plan, int p1, int p2, int paths, bool
     const u16 *A = (const u16 *)plan->d_sgm;
     i32 *S = (i32 *)((char *)plan->d_sgm + (size_t)2 * g.w * g.h * g.Dp);
     for (int r = 0; r < paths; r++) {
-        const int *dir = dirs[paths == 4 ? four[r] : r];
-        g.dx = dir[0]; g.dy = dir[1];
-        g.lines = g.dy == 0 ? g.h : g.dx == 0 ? g.w : g.w + g.h - 1;
+        sm_sgm_direction(paths, r, g.w, g.h, &g.dx, &g.dy, &g.lines);
         const int mode = r == 0 ? SGM_FIRST : r == paths - 1 && !keep ? SGM_LAST : SGM_MID;
         const void *fn = K == 1 ? sgm_path_ptr<1>(mode) : K == 2 ? sgm_path_ptr<2>(mode) : sgm_path_ptr<4>(mode);
         // (paths >= 4: the last direction is never the first, so S always holds the other directions' sum)

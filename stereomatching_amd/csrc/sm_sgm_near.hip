@@ -22,10 +22,10 @@
 // the prior and the maps in natural ones.
 //
 // Kernels:
-//   k_sgm_near_cost<NW, GHOST, MIRROR>  the data term.  k_census_near's scheme (sm_census_near.hip, written out here on
-//                  its own so that kernel's code stays what it is): a 64 x 16 tile's positions in registers, the OR of
-//                  the wanted shifts in LDS, a uniform walk of its set bits, row sums then column sums through LDS, the
-//                  next shift's loads in flight meanwhile.  The epilogue stores A to the pixel's slot of that shift.
+//   k_sgm_near_cost<NW, GHOST, MIRROR>  the data term: the tile walk that k_census_near makes, one text for both
+//                  (sm_near_tile_body.h): a 64 x 16 tile's positions in registers, the OR of the wanted shifts in LDS,
+//                  a uniform walk of its set bits, row sums then column sums through LDS, the next shift's loads in
+//                  flight meanwhile.  Here a pixel stores A to its slot of the shift.
 //   k_sgm_near_path<MODE>  one direction.  A DPP row of 16 lanes owns a line, lane = slot: four lines per wave, 16 per
 //                  workgroup (a horizontal direction is bound by the latency of its chain, not by lanes).
 //                  Step p: b_p - b_q slots lie between the two bands, so L(q, d) is one ds_bpermute within the row
@@ -39,19 +39,11 @@
 
 typedef unsigned short u16;
 
-#define SGN_NQ 14                 // cost: positions per lane at most ((64 + 24) * (16 + 24) / 256, rounded up)
-#define SGN_NR 10                 // cost: rows of positions per wave at most ((16 + 24) / 4)
 #define SGN_NS 16                 // slots per pixel: guard, 2r + 1 <= 9 shifts, guard, padding to a DPP row
 #define SGN_INF 0x3fffffff        // L of a slot outside K: never a minimum, + P2 cannot wrap
 #define SGN_PF 12                 // path kernel: steps loaded ahead
 
-struct SgmNearCostGeom {
-    int w, h, D;
-    int n, half;
-    int radius;
-    int sw, sh;                   // positions of a tile: 64 + n - 1 columns, 16 + n - 1 rows
-    int tiles_x, tiles_y;
-    long long side;               // descriptors from side 0 (left) to side 1 (right) of the census workspace
+struct SgmNearCostGeom : NearTileGeom {
     long long pair;               // pixels from the first pair's to this pair's (descriptors, prior)
 };
 
@@ -59,182 +51,26 @@ template <int NW, bool GHOST, bool MIRROR>
 __global__ __launch_bounds__(256) void k_sgm_near_cost(const u32 *__restrict__ desc, const i32 *__restrict__ prior,
                                                        u16 *__restrict__ A, const SgmNearCostGeom g)
 {
-    extern __shared__ __attribute__((aligned(16))) u32 sgn_lds[];
-    u32 *mask = sgn_lds;                                                   // [16]
-    u16 *cost = reinterpret_cast<u16 *>(sgn_lds + 16);                     // [sh][sw]
-    const int total = g.sw * g.sh;
-    u16 *hs = cost + ((total + 1) & ~1);                                   // [sh][64]
-    const int tid = threadIdx.x, lx = tid & 63, ly = tid >> 6;
-    int tx, ty;
-    sm_xcd_tile(g.tiles_x, g.tiles_y, tx, ty);
-    const int x0 = tx * SMN_TX, y0 = ty * SMN_TR;
-    const int W = g.w, H = g.h, D = g.D, n = g.n, half = g.half;
-    // MIRROR: the pass's left image is mirror(R), its right image mirror(L)
-    const u32 *dRef = desc + (size_t)NW * ((MIRROR ? (size_t)g.side : 0) + (size_t)g.pair);
-    const u32 *dOth = desc + (size_t)NW * ((MIRROR ? 0 : (size_t)g.side) + (size_t)g.pair);
-
-    // ---- this lane's positions: the reference descriptor, its row's offset in an image (-1: outside, ghost) and its
-    // column of the pass
-    u32 ref[SGN_NQ][NW];
-    int prow[SGN_NQ], pcol[SGN_NQ];
-#pragma unroll
-    for (int q = 0; q < SGN_NQ; q++) {
-        const int i = tid + 256 * q;
-#pragma unroll
-        for (int k = 0; k < NW; k++) ref[q][k] = 0;
-        prow[q] = -1;
-        pcol[q] = 0;
-        if (i < total) {
-            const int r = i / g.sw, c = i - r * g.sw;
-            int x = x0 - half + c, y = y0 - half + r;
-            bool on = true;
-            if (GHOST) on = x >= 0 && x < W && y >= 0 && y < H;
-            else { x = smn_mod(x, W); y = smn_mod(y, H); }
-            if (on) {
-                prow[q] = y * W;
-                pcol[q] = x;
-                const u32 *p = dRef + (size_t)NW * ((size_t)prow[q] + (MIRROR ? W - 1 - x : x));
-                if constexpr (NW == 2) {
-                    const uint2 t = *reinterpret_cast<const uint2 *>(p);
-                    ref[q][0] = t.x;
-                    ref[q][NW - 1] = t.y;
-                } else {
-                    ref[q][0] = p[0];
-                }
-            }
-        }
+#define SMN_TILE_PAIR ((size_t)g.pair)
+#define SMN_TILE_STATE int b0[4];                          // the shift of the pixel's slot 0
+#define SMN_TILE_NONE(j) b0[j] = 0;
+#define SMN_TILE_BAND(j, s) b0[j] = (s) - 2 - g.radius;
+// the pixel's slots in A_b (a pixel outside the image has no band and stores nothing: clamped)
+#define SMN_TILE_SETUP                                                          \
+    u16 *out[4];                                                                \
+    _Pragma("unroll") for (int j = 0; j < 4; j++) {                             \
+        const int y = min(y0 + 4 * ly + j, H - 1);                              \
+        out[j] = A + ((size_t)y * W + min(x, W - 1)) * SGN_NS;                  \
     }
-
-    // ---- this lane's four pixels: the band lo .. hi of each (hi < lo: none), the shift of its slot 0, the tile's mask
-    if (tid < 16) mask[tid] = 0;
-    __syncthreads();
-    const int x = x0 + lx;                                 // column of the pass
-    const int xn = MIRROR ? W - 1 - x : x;                 // natural column: the prior
-    int lo[4], hi[4], b0[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int y = y0 + 4 * ly + j;
-        lo[j] = 0;
-        hi[j] = -1;
-        b0[j] = 0;
-        if (x < W && y < H) {
-            const int s = prior[(size_t)g.pair + (size_t)y * W + xn];
-            // (s compared before any arithmetic on it: INT32_MIN and INT32_MAX are legal)
-            if (s != 0 && s >= 1 - g.radius && s <= D + g.radius) {
-                lo[j] = max(0, s - 1 - g.radius);
-                hi[j] = min(D - 1, s - 1 + g.radius);
-                b0[j] = s - 2 - g.radius;
-                const u64 bits = ((1ull << (hi[j] - lo[j] + 1)) - 1) << (lo[j] & 31);   // at most 9 bits
-                atomicOr(&mask[lo[j] >> 5], (u32)bits);
-                if ((u32)(bits >> 32)) atomicOr(&mask[(lo[j] >> 5) + 1], (u32)(bits >> 32));
-            }
-        }
-    }
-    __syncthreads();
-
-    // ---- the wanted shifts in ascending order; the other side's descriptors of the NEXT wanted shift are requested
-    // before the barriers of the current one
-    const int words = (D + 31) >> 5;
-    int wd = -1;
-    u32 m = 0;
-    auto next_wanted = [&]() -> int {                      // workgroup-uniform
-        while (m == 0) {
-            if (++wd >= words) return -1;
-            m = __builtin_amdgcn_readfirstlane(mask[wd]);
-        }
-        const int d = 32 * wd + __builtin_ctz(m);
-        m &= m - 1;
-        return d;
-    };
-    u32 oth[SGN_NQ][NW];
-    // every lane loads for every q below the tile's count: a position that has no descriptor to load (outside the
-    // image, past the ghost border, or past the last position) reads descriptor 0 of the pair and ignores it
-    auto request = [&](int d) {
-        const int dm = GHOST ? d : d % W;                  // toroidal: x + d mod W by one conditional subtraction
-#pragma unroll
-        for (int q = 0; q < SGN_NQ; q++) {
-            if (256 * q >= total) break;
-            int xo = pcol[q] + dm;
-            bool on = prow[q] >= 0;
-            if (GHOST) on = on && xo < W;
-            else if (xo >= W) xo -= W;
-            const size_t off = on ? (size_t)prow[q] + (size_t)(MIRROR ? W - 1 - xo : xo) : 0;
-            const u32 *p = dOth + (size_t)NW * off;
-            if constexpr (NW == 2) {
-                const uint2 v = *reinterpret_cast<const uint2 *>(p);
-                oth[q][0] = v.x;
-                oth[q][NW - 1] = v.y;
-            } else {
-                oth[q][0] = p[0];
-            }
-        }
-    };
-    u16 *out[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int y = min(y0 + 4 * ly + j, H - 1);
-        out[j] = A + ((size_t)y * W + min(x, W - 1)) * SGN_NS;
-    }
-    int d = next_wanted();
-    if (d >= 0) request(d);
-    while (d >= 0) {
-        // Hamming costs of the positions
-#pragma unroll
-        for (int q = 0; q < SGN_NQ; q++) {
-            if (256 * q >= total) break;
-            const int i = tid + 256 * q;
-            const bool past = GHOST && pcol[q] + d >= W;   // ghost: C = 0 past the right border
-            u32 c = 0;
-#pragma unroll
-            for (int k = 0; k < NW; k++) c += (u32)__builtin_popcount(ref[q][k] ^ (past ? 0u : oth[q][k]));
-            if (i < total) cost[i] = (u16)(prow[q] >= 0 ? c : 0u);
-        }
-        const int d_next = next_wanted();
-        if (d_next >= 0) request(d_next);
-        __syncthreads();
-        // horizontal n-sums of the tile's columns, every row of the positions: rows ly, ly + 4, ... of a lane
-        {
-            u32 s[SGN_NR];
-#pragma unroll
-            for (int k = 0; k < SGN_NR; k++) s[k] = 0;
-            const u16 *cr = cost + ly * g.sw + lx;
-#pragma unroll 3
-            for (int t = 0; t < n; t++) {
-#pragma unroll
-                for (int k = 0; k < SGN_NR; k++)
-                    if (ly + 4 * k < g.sh) s[k] += cr[4 * k * g.sw + t];
-            }
-#pragma unroll
-            for (int k = 0; k < SGN_NR; k++)
-                if (ly + 4 * k < g.sh) hs[(ly + 4 * k) * 64 + lx] = (u16)s[k];
-        }
-        __syncthreads();
-        // vertical n-sums: rows 4 ly .. 4 ly + 3 of the tile; the four share rows 3 .. n - 1 (n >= 4)
-        const u16 *hc = hs + (4 * ly) * 64 + lx;
-        u32 a[4];
-        if (n >= 4) {
-            u32 mid = 0;
-#pragma unroll 4
-            for (int t = 3; t < n; t++) mid += hc[t * 64];
-            const u32 h0 = hc[0], h1 = hc[64], h2 = hc[128];
-            const u32 t0 = hc[n * 64], t1 = hc[(n + 1) * 64], t2 = hc[(n + 2) * 64];
-            a[0] = h0 + h1 + h2 + mid;
-            a[1] = h1 + h2 + mid + t0;
-            a[2] = h2 + mid + t0 + t1;
-            a[3] = mid + t0 + t1 + t2;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                a[j] = 0;
-                for (int t = 0; t < n; t++) a[j] += hc[(j + t) * 64];
-            }
-        }
-        // (lo .. hi is empty for a pixel outside the image: no store; d - b0 is in 1 .. 2r + 1)
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            if (d >= lo[j] && d <= hi[j]) out[j][d - b0[j]] = (u16)a[j];
-        d = d_next;
-    }
+// (d - b0 is in 1 .. 2r + 1)
+#define SMN_TILE_TAKE(j, d, a) out[j][(d) - b0[j]] = (u16)(a);
+#include "sm_near_tile_body.h"
+#undef SMN_TILE_PAIR
+#undef SMN_TILE_STATE
+#undef SMN_TILE_NONE
+#undef SMN_TILE_BAND
+#undef SMN_TILE_SETUP
+#undef SMN_TILE_TAKE
 }
 
 struct SgmNearPathGeom {
@@ -406,19 +242,9 @@ static int sgn_cost_launch(const sm_plan *plan, int cw, bool mirror, int pair, c
                            hipStream_t st)
 {
     SgmNearCostGeom g;
-    g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts;
-    g.half = plan->square_width / 2; g.n = 2 * g.half + 1;
-    g.radius = radius;
-    g.sw = SMN_TX + g.n - 1;
-    g.sh = SMN_TR + g.n - 1;
-    g.tiles_x = (g.w + SMN_TX - 1) / SMN_TX;
-    g.tiles_y = (g.h + SMN_TR - 1) / SMN_TR;
-    g.side = (long long)plan->max_pairs * g.w * g.h;
+    size_t lds;
+    SM_TRY(sm_near_tile_geom(plan, radius, "sgm near", &g, &lds));
     g.pair = (long long)pair * g.w * g.h;
-    const int total = g.sw * g.sh;
-    const size_t lds = 4 * 16 + 2 * ((size_t)((total + 1) & ~1) + (size_t)g.sh * 64);
-    if (total > 256 * SGN_NQ || lds > 64 * 1024)
-        return sm_fail(SM_ERR_HIP, "sgm near: internal tiling error (%d positions, %zu bytes of LDS)", total, lds);
     const bool ghost = plan->border == SM_GHOST;
     const void *fn = cw == 7 ? SM_PASS_KERNEL(k_sgm_near_cost, 2, ghost, mirror)
                              : SM_PASS_KERNEL(k_sgm_near_cost, 1, ghost, mirror);
@@ -433,8 +259,6 @@ static int sgn_cost_launch(const sm_plan *plan, int cw, bool mirror, int pair, c
 static int sgn_paths_launch(const sm_plan *plan, int p1, int p2, int paths, bool mirror, int pair, const i32 *d_prior,
                             int radius, i32 *web, i32 *best, int16_t *sub, hipStream_t st)
 {
-    static const int dirs[8][2] = {{1, 0}, {0, 1}, {1, 1}, {-1, 1}, {1, -1}, {-1, -1}, {0, -1}, {-1, 0}};
-    static const int four[4] = {0, 1, 6, 7};
     SgmNearPathGeom g;
     g.w = plan->width; g.h = plan->height; g.D = plan->num_shifts;
     g.radius = radius;
@@ -444,9 +268,7 @@ static int sgn_paths_launch(const sm_plan *plan, int p1, int p2, int paths, bool
     const u16 *A = sgn_volume_a(plan);
     i32 *S = sgn_volume_s(plan);
     for (int r = 0; r < paths; r++) {
-        const int *dir = dirs[paths == 4 ? four[r] : r];
-        g.dx = dir[0]; g.dy = dir[1];
-        g.lines = g.dy == 0 ? g.h : g.dx == 0 ? g.w : g.w + g.h - 1;
+        sm_sgm_direction(paths, r, g.w, g.h, &g.dx, &g.dy, &g.lines);
         const void *fn = r == 0 ? (const void *)k_sgm_near_path<SGN_FIRST>
                        : r == paths - 1 ? (const void *)k_sgm_near_path<SGN_LAST> : (const void *)k_sgm_near_path<SGN_MID>;
         void *args[] = {(void *)&A, (void *)&S, (void *)&d_prior, (void *)&web, (void *)&best, (void *)&sub, (void *)&g};
@@ -458,43 +280,27 @@ static int sgn_paths_launch(const sm_plan *plan, int p1, int p2, int paths, bool
 
 // the mode as the entry driver sees it (sm_entry.h): the guided re-search's inputs and overlap rules
 // with SGM's scalars
-struct SgmNearMode : sm_mode {
+struct SgmNearMode : sm_mode, NearPriors {
+    using NearPriors::inputs;
     static constexpr const sm_ws_set &ws = SM_WS_SET_SGM_NEAR;
-    int cw, p1, p2, paths, radius;
-    const i32 *prior, *prior_right;
+    int cw, p1, p2, paths;
     const int16_t *sub;                 // the call's d_sub (NULL: none): an output like the maps the driver hands to apart
     SgmNearMode(int census_width, int p1_, int p2_, int paths_, int radius_, const i32 *p, const i32 *p_right,
                 const int16_t *d_sub)
-        : cw(census_width), p1(p1_), p2(p2_), paths(paths_), radius(radius_), prior(p), prior_right(p_right), sub(d_sub) {}
-    int inputs(const sm_call &c, bool left, bool right) const
-    {
-        if (left && right)
-            return prior && prior_right ? SM_OK : sm_fail(SM_ERR_ARG, "%s: prior map pointer is NULL", c.me);
-        return (right ? prior_right : prior) ? SM_OK
-               : sm_fail(SM_ERR_ARG, "%s: %s is NULL", c.me, right ? "d_prior_right" : "d_prior");
-    }
+        : NearPriors{radius_, p, p_right}, cw(census_width), p1(p1_), p2(p2_), paths(paths_), sub(d_sub) {}
     // SGM's plan-free checks (sm_sgm_scalar_args: the one copy of their messages) and the radius, then the census
     // mode's, whose reach of 512 shifts stands in place of SGM's 256 (nothing here grows with D)
     int args(const sm_call &c) const
     {
         SM_TRY(sm_sgm_scalar_args(cw, p1, p2, paths, c.me));
-        if (radius < 1 || radius > 4) return sm_fail(SM_ERR_ARG, "%s: radius %d outside 1..4", c.me, radius);
+        SM_TRY(radius_arg(c.me));
         return sm_census_args(c.plan, cw, c.pairs, c.me);
     }
+    // the int16 subpixel map as well, which the driver compares with the other maps only
     int apart(const sm_call &c, const i32 *const *outs, int n_outs, const i32 *rejected) const
     {
-        const size_t px = (size_t)c.pairs * c.plan->width * c.plan->height, map = px * sizeof(i32);
-        // the int32 maps, the counts, and the int16 subpixel map, which the driver compares with the other maps only
-        for (int k = 0; k <= n_outs + 1; k++) {
-            const void *o = k < n_outs ? (const void *)outs[k] : k == n_outs ? (const void *)rejected : (const void *)sub;
-            const size_t ob = k < n_outs ? map : k == n_outs ? (size_t)c.pairs * sizeof(i32) : map / 2;
-            if (!o) continue;
-            if (overlap(o, c.left, ob, px) || overlap(o, c.right, ob, px))
-                return sm_fail(SM_ERR_ARG, "%s: an output overlaps an input image", c.me);
-            if ((prior && overlap(o, prior, ob, map)) || (prior_right && overlap(o, prior_right, ob, map)))
-                return sm_fail(SM_ERR_ARG, "%s: an output overlaps a prior map", c.me);
-        }
-        return SM_OK;
+        return NearPriors::apart(c, outs, n_outs, rejected, sub,
+                                 (size_t)c.pairs * c.plan->width * c.plan->height * sizeof(int16_t));
     }
     int prepare(const sm_call &c) const { return sm_census_descriptors(c.plan, cw, c.left, c.right, c.pairs, c.st); }
     // one pair at a time through the volumes

@@ -25,9 +25,9 @@ AROUND = ({f"G{i}" for i in range(1, 9)} | {f"I{i}" for i in range(1, 7)} | {f"F
           | {f"P{i}" for i in range(1, 8)} | {f"R{i}" for i in range(1, 8)} | {f"X{i}" for i in range(1, 6)})
 AROUND_OWN = {"G": "tests/test_wls_gpu.py", "I": "tests/test_interp_gpu.py", "F": "tests/test_filter_gpu.py",
               "P": "tests/test_pyramid_gpu.py", "R": "tests/test_rectify_gpu.py", "X": "tests/test_subpix_gpu.py"}
-# the one newer mutant with a second group: the row scan's carry needs more than 64 chunks, which only the module of
-# the loops' second turns has
-SECOND_GROUP = {"I2": {"turns": ["tests/test_second_turns_gpu.py"]}}
+# the two newer mutants with a second group: the row scan's carry needs more than 64 chunks, which only the module of
+# the loops' second turns has; and C1 mutates the one text of two kernels (sm_near_tile_body.h), each with its module
+SECOND_GROUP = {"I2": {"turns": ["tests/test_second_turns_gpu.py"]}, "C1": {"near": ["tests/test_near_gpu.py"]}}
 
 
 @pytest.fixture(scope="module")
