@@ -32,6 +32,10 @@ TIE_PATTERNS = ("all_match_0", "all_match_1", "no_centre_match")
 GRAY_PATTERNS = ("black_white", "white_black", "both_0", "both_255", "both_77", "checker_2", "checker_64",
                  "zero_cost_column")
 SKEW = {"skewed_95_05": (0.95, 0.05), "skewed_05_95": (0.05, 0.95), "skewed_98_02": (0.98, 0.02)}
+# not one of GRAY_PATTERNS: it is for one shift count only (D = 1), tests/test_extremes_gpu.py
+# test_sad_full_cost_beside_a_free_shift_below_zero (the mutation audit's S1 and S3, profiles/mutants/README.md)
+FREE_SHIFT_BELOW_ZERO = "stripes_off_by_one"
+FREE_SHIFT_SHAPE = (32, 2)                  # width (even, above every window), rows beyond the window
 
 
 def bits_for(v):
@@ -115,6 +119,13 @@ def gray_pattern(name, w, h, c=77):
         cols = np.where((np.arange(w) % period) < period // 2, 0, 255).astype(np.uint8)
         img = np.repeat(cols[None, :], h, axis=0)
         return img, img.copy()
+    if name == FREE_SHIFT_BELOW_ZERO:
+        # columns 0, 255, 0, 255, .. on the right, the same one column further on the left: L(x) = R(x - 1), so the
+        # shift -1, which does not exist, would cost 0, and the shift 0 costs 255 at every tap (w even: also across
+        # the wrap).  With D = 1 nothing else competes.
+        assert w % 2 == 0
+        img = np.repeat(np.where(np.arange(w) % 2, 255, 0).astype(np.uint8)[None, :], h, axis=0)
+        return np.roll(img, 1, axis=1), img
     if name == "zero_cost_column":          # the layout of test_quad_sad_largest_possible_sums
         right = white.copy()
         right[:, min(60, w - 1)] = 0
@@ -234,3 +245,44 @@ def cost_hot_path_bruteforce(left, right, num_shifts, square_width, mode="toroid
         best[upd] = s[upd]
         web[upd] = d + 1
     return best.astype(np.int32), web
+
+
+# ---------------------------------------------------------------------------
+# the mutation audit's S1 and S3: the constant that keeps shifts which do not exist from winning
+# ---------------------------------------------------------------------------
+
+# k_sad_pc's packed sums of the positions below shift 0 (a lane's first quad starts up to 3 positions early) start at a
+# constant BIG, so that they lose to every real sum without a test in the row loop.  The mistakes: one short of what a
+# tie needs (windows up to 9 x 9), and the constant of the larger windows' builds, which is no bound at 13 x 13.
+MISTAKES = {"poison one short": lambda n: n * n * 255, "poison below a full cost": lambda n: 65535 - n * n * 255}
+
+
+def sums_below_zero(left, right, n, mode):
+    """the SAD window sums of the shifts -1, -2, -3 as the kernel forms them: R(x + d) with the border applied
+    (ghost: 0 left of the image), every tap inside the image counted -> [3][H][W]"""
+    left = np.asarray(left, np.int64)
+    right = np.asarray(right, np.int64)
+    out = []
+    for d in (1, 2, 3):
+        if mode == "toroidal":
+            r = np.roll(right, d, axis=1)
+        else:
+            r = np.zeros_like(right)
+            r[:, d:] = right[:, :right.shape[1] - d]
+        out.append(_window_sums(np.abs(left - r), n, mode))
+    return np.stack(out)
+
+
+def wins_below_zero(left, right, best, square_width, mode, mistake):
+    """the pixels where a position below shift 0 would take the arg-min (at equal sums its key is the smaller) if its sum
+    started at MISTAKES[mistake](n) instead of above every real sum; `best` is the definition's best map -> bool [H][W].
+    Pixel x has the positions -1 .. -((x - half) mod 4): its quads start at the dword that holds its window's first
+    column.  (Ghost: the columns x < half are the strip kernel's, which has none.)"""
+    n = window(square_width)
+    half = n // 2
+    x = np.arange(np.asarray(left).shape[1])
+    has = np.stack([k <= ((x - half) & 3) for k in (1, 2, 3)])
+    if mode != "toroidal":
+        has &= x >= half
+    bad = MISTAKES[mistake](n) + sums_below_zero(left, right, n, mode)
+    return ((bad <= np.asarray(best, np.int64)[None]) & has[:, None, :]).any(axis=0)

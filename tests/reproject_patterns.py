@@ -81,5 +81,77 @@ def matrices(w, h):
     }
 
 
+# ---------------------------------------------------------------------------
+# the mutation audit's cases (profiles/mutants/README.md, third audit: J1, J2, J3, J5)
+# ---------------------------------------------------------------------------
+
+EDGE_W, EDGE_H = 8, 3                 # W % 4 == 0: four pixels a lane; EDGE_W - 1 columns of the same maps: one
+EDGE_GATE = (2.0, 40.0)               # (Z_GATES' bounds)
+FUSED_A = 1.0 + 2.0 ** -52            # 3 a = 3 + 1.5 ulp: a tie, rounded up to 3 + 2^-50 when the product is rounded
+FUSED_B = -(2.0 - 2.0 ** -24 + 3 * 2.0 ** -52)
+
+
+def edge_matrices():
+    """name -> 16 doubles.  Wh = 1 in all three, Y = y and Z = d (the disparity itself), so that Z sits exactly on a
+    gate's bounds where the map says so:
+      z_is_d       X = x;
+      x_overflows  X = 1e300 x: no float32 from column 1 on, while Y and Z stay finite;
+      fused_tie    X = (a x + b y): at (x, y) = (3, 1) the double sum is 1 + 2^-24 + 2^-52, above the middle of the
+                   float32 pair 1 and 1 + 2^-23, when a x is rounded on its own; formed with one rounding
+                   (fused multiply-add) it is the middle itself, 1 + 2^-24, which goes to 1 (ties to even)."""
+    base = np.zeros(16)
+    base[0] = base[5] = base[10] = base[15] = 1.0
+    over = base.copy()
+    over[0] = 1e300
+    fused = base.copy()
+    fused[0], fused[1] = FUSED_A, FUSED_B
+    return {"z_is_d": base, "x_overflows": over, "fused_tie": fused}
+
+
+def edge_map(pairs, w, h, dtype):
+    """every pixel valid, the even disparities 0, 2, 4, .. in raster order (every other pair: in reverse): d = 2 and
+    d = 40, EDGE_GATE's bounds, occur in every pair of 21 pixels or more"""
+    assert h * w >= 21
+    d = (2 * np.arange(h * w)) % 64
+    d = np.stack([d[::-1] if p % 2 else d for p in range(pairs)]).reshape(pairs, h, w)
+    return (d + 1).astype(np.int32) if dtype == np.int32 else (16 * (d + 1)).astype(np.int16)
+
+
+MISTAKES = ("z_min excluded", "z_max excluded", "X not tested", "row 0 fused")
+
+
+def _fused_row0(q, x, y, d):
+    """((fma(q0, x, q1 y) then fma(q2, d, .)) + q3 with each fused multiply-add rounded once (exact rationals,
+    converted to the nearest double)"""
+    from fractions import Fraction as Fr
+    out = np.empty(x.shape)
+    for i in np.ndindex(x.shape):
+        inner = float(Fr(float(q[0])) * Fr(float(x[i])) + Fr(float(q[1] * y[i])))
+        out[i] = float(Fr(float(q[2])) * Fr(float(d[i])) + Fr(inner)) + q[3]
+    return out
+
+
+def project_with(m, q, z_range, mistake):
+    """ref.project with one mistake of MISTAKES made -> (Xf, Yf, Zf, kept)"""
+    assert mistake in MISTAKES
+    q = ref.check_q(q)
+    lo, hi = ref.check_z(z_range)
+    m = np.asarray(m)
+    h, w = m.shape[-2:]
+    d = ref.disparity(m)
+    x = np.broadcast_to(np.arange(w, dtype=np.float64)[None, :], d.shape)
+    y = np.broadcast_to(np.arange(h, dtype=np.float64)[:, None], d.shape)
+    with np.errstate(all="ignore"):
+        r = [((q[4 * i] * x + q[4 * i + 1] * y) + q[4 * i + 2] * d) + q[4 * i + 3] for i in range(4)]
+        if mistake == "row 0 fused":
+            r[0] = _fused_row0(q, x, y, d)
+        xf, yf, zf = ((r[i] / r[3]).astype(np.float32) for i in range(3))
+        above = lo < zf if mistake == "z_min excluded" else lo <= zf
+        below = zf < hi if mistake == "z_max excluded" else zf <= hi
+        finite = np.isfinite(yf) & np.isfinite(zf) & (True if mistake == "X not tested" else np.isfinite(xf))
+        kept = (m != 0) & finite & above & below
+    return xf, yf, zf, kept
+
+
 def gray(pairs, w, h, seed):
     return np.random.default_rng(seed + 77).integers(0, 256, (pairs, h, w), dtype=np.uint8)

@@ -155,6 +155,27 @@ def lr_scene(w, h, seed, num_shifts=64, square_width=9, mode="toroidal", max_dif
     return checked
 
 
+def no_positive(w, h, seed):
+    """a caller-made map whose every value is below 0 (-1000 .. -11, both present): its maximum is negative, which a
+    running maximum that starts at 0 instead of INT_MIN never reports (the mutation audit's Z4); with 10 lines the
+    contour interval is 98, and 100 if the maximum were 0"""
+    web = np.random.default_rng(seed).integers(-1000, -10, (h, w)).astype(np.int32)
+    web[0, 0], web[-1, -1] = -1000, -11
+    return web
+
+
+# n = 185 (n % 4 = 1: k_minmax_zero's scalar tail, and the scalar loop for the second pair of a stack) and n = 256
+# (16-byte loads throughout)
+NO_POSITIVE_SHAPES = ((37, 5), (64, 4))
+MISTAKES = ("maximum starts at 0",)
+
+
+def min_max_with(web, mistake):
+    """(min, max) of a map with the mistake made"""
+    assert mistake in MISTAKES
+    return int(web.min()), max(int(web.max()), 0)
+
+
 def with_pattern(fn, w, h, seed):
     return np.ascontiguousarray(fn(w, h, seed), np.int32)
 

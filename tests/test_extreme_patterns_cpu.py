@@ -74,6 +74,37 @@ def test_cost_patterns_reach_the_largest_sums():
 
 
 @pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("mistake,windows", [("poison one short", (3, 5, 7, 9)), ("poison below a full cost", (13,))])
+def test_a_free_shift_below_zero_tells_a_poison_constant_that_is_too_small(mistake, windows, mode):
+    """(the mutation audit's S1 and S3: k_sad_pc with BIG one short of a tie, and with the small windows' scheme at
+    13 x 13, passed every SAD test.)  The position below shift 0 takes the arg-min only where EVERY real shift costs at
+    least BIG more than it does: with the stripes moved by one column and D = 1 the only real shift costs n^2 255 and
+    the shift -1 nothing.  No gray pattern of test_sad_kernels_at_the_extremes, at any of its shift counts, has such a pixel."""
+    for sw in windows:
+        w, h = xp.FREE_SHIFT_SHAPE[0], sw + xp.FREE_SHIFT_SHAPE[1]
+        left, right = xp.gray_pattern(xp.FREE_SHIFT_BELOW_ZERO, w, h)
+        best, web = oracle.cost_hot_path(left, right, 1, sw, mode, "sad")
+        wins = xp.wins_below_zero(left, right, best, sw, mode, mistake)
+        if mode == "toroidal":
+            three_of_four = ((np.arange(w) - sw // 2) & 3) != 0         # the column residues that have a position -1
+            assert (best == sw * sw * 255).all() and (wins == three_of_four[None, :]).all(), sw
+        else:
+            # (only where no tap is missing: a window cut by the border costs less than BIG, as in the kernel, which
+            # stages zeros there in both images)
+            half = sw // 2
+            three_of_four = ((np.arange(w) - half) & 3) != 0
+            assert (wins[half:h - half, sw:w - sw] == three_of_four[None, sw:w - sw]).all() and h - 2 * half == 3, sw
+        assert (web == 1).all()
+        bb, bw = xp.cost_hot_path_bruteforce(left, right, 1, sw, mode, "sad")
+        assert np.array_equal(bb, best) and np.array_equal(bw, web)
+        for d in (1, 33, 500):
+            for name in xp.GRAY_PATTERNS:
+                left, right = xp.gray_pattern(name, 150, sw + 10)
+                best, _ = oracle.cost_hot_path(left, right, d, sw, mode, "sad")
+                assert not xp.wins_below_zero(left, right, best, sw, mode, mistake).any(), (sw, d, name)
+
+
+@pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("sw,d", [(1, 9), (3, 33), (4, 7), (5, 20), (9, 17)])
 def test_oracle_hot_path_equals_the_bruteforce_on_every_pattern(mode, sw, d):
     n = xp.window(sw)

@@ -239,3 +239,29 @@ def test_sad_kernels_at_the_extremes(hip, sw, mode):
         names, ob = check_cost(hip, sw, d, mode, "sad", sets)
         if mode == "toroidal":
             assert (ob[names.index("black_white")] == sw * sw * 255).all()
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("sw", [3, 5, 7, 9, 11, 13, 15])
+def test_sad_full_cost_beside_a_free_shift_below_zero(hip, sw, mode):
+    """k_sad_pc's lanes start their first quad up to three positions below shift 0, and only the constant those sums
+    start at (BIG) keeps them from winning: it must exceed every real sum, by one at least, because the earlier
+    position wins a tie.  That decides a pixel only where every real shift costs BIG more than a position below 0
+    does -- nowhere in the other patterns (the mutation audit's S1 and S3 passed them all;
+    test_a_free_shift_below_zero_tells_a_poison_constant_that_is_too_small is the CPU proof).  Here the right image is
+    columns of 0 and 255 and the left one the same a column on: the shift -1 would cost 0, and with D = 1 the one real
+    shift costs 255 at every tap, n^2 255 in all.  32 columns (even, so that the stripes meet across the wrap) by n + 2
+    rows are one tile of every kernel; three of a lane group's four column residues have a position below 0."""
+    w, h = xp.FREE_SHIFT_SHAPE[0], sw + xp.FREE_SHIFT_SHAPE[1]
+    left, right = xp.gray_pattern(xp.FREE_SHIFT_BELOW_ZERO, w, h)
+    ob, ow = oracle.cost_hot_path(left, right, 1, sw, mode, "sad")
+    assert (ow == 1).all()
+    if mode == "toroidal":
+        assert (ob == sw * sw * 255).all()
+    sets = [dict(cost_kernel=0, cost_workgroup_waves=wv) for wv in (1, 2, 4)] + [dict(cost_kernel=1)]
+    bad = []
+    for opts in sets:
+        best, web = cost_batch(hip, left[None], right[None], 1, sw, mode, "sad", opts)
+        bad += [f"{opts}: {b}" for b in differences(["stripes"], web, ow[None], "web") +
+                differences(["stripes"], best, ob[None], "best")]
+    assert not bad, "\n".join([f"sad {mode} n={sw} D=1", *bad])

@@ -122,3 +122,35 @@ def test_check_definition_on_hand_built_maps():
     u = (np.arange(13)[None, :] + webr - 1) % 13
     agree = np.take_along_axis(wrr, u, axis=1) == webr
     assert rej == (~agree).sum() and np.array_equal(out, np.where(agree, webr, 0))
+
+
+def test_wide_differences_tell_a_32_bit_subtraction_and_the_older_maps_do_not():
+    """(the mutation audit's L2: a check that takes web_right(u) - web(x) modulo 2^32 passed tests/test_lr_gpu.py)"""
+    from tests import lr_patterns as lp
+    mistake = lp.MISTAKES[0]
+    for w in (8, 7):
+        web, right = lp.wide_difference_maps(w)
+        for max_diff, mode in lp.WIDE_CHECKS:
+            want, nrej = lr.lr_check(web, right, max_diff, mode)
+            got, nmis = lp.lr_check_with(web, right, max_diff, mode, mistake)
+            assert not np.array_equal(want, got) and nrej > nmis, (w, max_diff, mode)       # the mistake keeps too many
+            assert (want[got != want] == 0).all()
+        # both outcomes occur, so a check that rejects everything fails as well
+        want, nrej = lr.lr_check(web, right, 2, "toroidal")
+        assert 0 < nrej < web.size
+    # the maps of test_check_of_values_no_match_produces (every int32 extreme among them) cannot tell
+    w, h = 37, 5
+    rng = np.random.default_rng(9)
+    web = rng.integers(-3 * w, 3 * w, (h, w)).astype(np.int32)
+    web[0, :4] = [0, -1, 2**31 - 1, -2**31]
+    right = rng.integers(-3 * w, 3 * w, (h, w)).astype(np.int32)
+    for mode in ("toroidal", "ghost"):
+        a, b = lr.lr_check(web, right, 2, mode), lp.lr_check_with(web, right, 2, mode, mistake)
+        assert np.array_equal(a[0], b[0]) and a[1] == b[1], mode
+    # nor maps of shifts 1 .. D, whatever max_diff (test_check_against_the_definition)
+    web = rng.integers(1, 201, (9, 128)).astype(np.int32)
+    right = rng.integers(1, 201, (9, 128)).astype(np.int32)
+    for mode in ("toroidal", "ghost"):
+        for max_diff in (0, 1, 3, 1000):
+            a, b = lr.lr_check(web, right, max_diff, mode), lp.lr_check_with(web, right, max_diff, mode, mistake)
+            assert np.array_equal(a[0], b[0]) and a[1] == b[1], (mode, max_diff)

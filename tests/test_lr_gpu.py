@@ -136,6 +136,25 @@ def test_check_of_values_no_match_produces(hip):
         plan.close()
 
 
+@pytest.mark.parametrize("w", [8, 7])
+def test_check_of_differences_past_32_bits(hip, w):
+    """web_right(u) - web(x) is a 33-bit number and is compared as one (the mutation audit's L2: a subtraction modulo
+    2^32 passed every other test here; tests/lr_patterns.py, with the CPU proof in tests/test_lr_cpu.py).  Pairs of
+    values 2^32 - 2 and 2^32 - 1 apart are rejected at max_diff = 2 although modulo 2^32 they differ by 2 and 1, and a
+    partner 2^31 + 1 .. 2^31 + 3 away is rejected at max_diff = 2^31 - 1, the largest there is, in both border modes.
+    Two rows of 8 columns take the four-pixel lanes, of 7 the one-pixel lanes; 7 is the least width whose row holds the
+    three planted pixels and their partners apart."""
+    from tests import lr_patterns as lp
+    web, right = lp.wide_difference_maps(w)
+    for max_diff, mode in lp.WIDE_CHECKS:
+        plan = hip.StereoPlan(w, lp.WIDE_H, 4, 1, mode)
+        out, rejected = plan.lr_check(dev(web[None]), dev(right[None]), max_diff)
+        want, nrej = lr.lr_check(web, right, max_diff, mode)
+        assert np.array_equal(host(out)[0], want), (max_diff, mode)
+        assert int(rejected[0]) == nrej, (max_diff, mode)
+        plan.close()
+
+
 # ---------------------------------------------------------------------------
 # sm_run_lr at full size, every pixel
 # ---------------------------------------------------------------------------

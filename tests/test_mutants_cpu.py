@@ -28,6 +28,24 @@ AROUND_OWN = {"G": "tests/test_wls_gpu.py", "I": "tests/test_interp_gpu.py", "F"
 # the two newer mutants with a second group: the row scan's carry needs more than 64 chunks, which only the module of
 # the loops' second turns has; and C1 mutates the one text of two kernels (sm_near_tile_body.h), each with its module
 SECOND_GROUP = {"I2": {"turns": ["tests/test_second_turns_gpu.py"]}, "C1": {"near": ["tests/test_near_gpu.py"]}}
+# the third audit: the matchers of the cost modes (general / strip, prefix-chain, quad-SAD, matrix-core), census, SGM, the
+# left-right check, the reprojection and step 3 -- the least each unit gets, and the GPU files its groups may name.  A
+# group of these is a list of pytest node ids (single tests of a long module), which tools/mutants.py passes on as they are
+MATCHERS = ({f"K{i}" for i in range(1, 11)} | {f"S{i}" for i in range(1, 9)} | {f"Q{i}" for i in range(1, 5)}
+            | {f"M{i}" for i in range(1, 11)} | {f"T{i}" for i in range(1, 11)} | {f"H{i}" for i in range(1, 11)}
+            | {f"L{i}" for i in range(1, 9)} | {f"J{i}" for i in range(1, 11)} | {f"Z{i}" for i in range(1, 7)})
+COST_FILES = {"tests/test_extremes_gpu.py", "tests/test_hip_gpu.py"}
+MATCHERS_FILES = {"K": COST_FILES, "S": COST_FILES, "Q": COST_FILES, "M": COST_FILES,
+                  "T": {"tests/test_census_gpu.py", "tests/test_census_extremes_gpu.py"},
+                  "H": {"tests/test_sgm_gpu.py", "tests/test_census_extremes_gpu.py"},
+                  "L": {"tests/test_lr_gpu.py", "tests/test_lr_sweep_gpu.py", "tests/test_cost_lr_gpu.py"},
+                  "J": {"tests/test_reproject_gpu.py"}, "Z": {"tests/test_step3_gpu.py", "tests/test_hip_gpu.py"}}
+# full-size tests no group may name (and so no group may name their whole module)
+TOO_LONG = {"tests/test_hip_gpu.py", "tests/test_extremes_gpu.py", "tests/test_step3_gpu.py"}
+
+
+def third(m):
+    return re.fullmatch(r"[KSQMTHLJZ]\d+", m["id"]) is not None
 
 
 @pytest.fixture(scope="module")
@@ -48,8 +66,9 @@ def survivors_recorded():
 
 def test_the_manifest_names_each_mutant_once_and_the_ones_asked_for():
     assert len(IDS) == len(set(IDS))
-    assert RECORDED | NEWEST | AROUND <= set(IDS)
-    assert len(AROUND) == 39
+    assert RECORDED | NEWEST | AROUND | MATCHERS <= set(IDS)
+    assert len(AROUND) == 39 and len(MATCHERS) == 76
+    assert sum(1 for m in MANIFEST if third(m) and m["run"]) >= 60, "the third audit runs at least 60 mutants"
     patches = {p.stem for p in mt.MUTDIR.glob("*.patch")}
     assert patches == set(IDS), "a patch without an entry, or an entry without a patch"
 
@@ -76,6 +95,12 @@ def test_every_entry_is_complete(m):
         assert m["groups"][name] == files
     if m["id"] in AROUND:
         assert m["groups"]["own"] == [AROUND_OWN[m["id"][0]]], "a mutant of the second audit runs against its unit's module"
+    if third(m):
+        files = {f.split("::")[0] for f in m["groups"]["own"]}
+        assert files <= MATCHERS_FILES[m["id"][0]], "a mutant of the third audit runs against its unit's modules"
+        for f in m["groups"]["own"]:
+            assert "::" in f or f.split("::")[0] not in TOO_LONG, f"{f}: name single tests of this module"
+            assert not f.endswith("test_cost_mode_4k_full_image_vs_own_oracle"), "the 4K test is no part of a group"
 
 
 def test_a_value_that_can_reach_an_address_is_never_run():
@@ -114,9 +139,14 @@ def test_every_group_is_gpu_test_files(m):
     for files in m["groups"].values():
         assert files
         for f in files:
-            path = ROOT / f
-            assert re.fullmatch(r"tests/test_\w+_gpu\.py", f) and path.is_file(), f
+            # a GPU test file, or one test of it as a pytest node id (third audit)
+            name, _, test = f.partition("::")
+            path = ROOT / name
+            assert re.fullmatch(r"tests/test_\w+_gpu\.py", name) and path.is_file(), f
             assert re.search(r"^pytestmark = pytest\.mark\.gpu|^@pytest\.mark\.gpu", path.read_text(), re.M), f
+            if "::" in f:
+                assert third(m) and re.fullmatch(r"test_\w+", test), f
+                assert re.search(rf"^def {test}\(", path.read_text(), re.M), f"{f}: no such test"
 
 
 def test_the_recorded_run_has_a_verdict_for_exactly_the_mutants_that_may_run(results):

@@ -210,6 +210,49 @@ def test_z_gate_keeps_both_bounds():
         ref.reproject(m, np.where(np.arange(16) == 5, np.inf, q))
 
 
+def _same_projection(a, b):
+    """(Xf, Yf, Zf, kept) twice: the same kept mask, and the same float bits at every kept pixel"""
+    return np.array_equal(a[3], b[3]) and all(np.array_equal(bits(a[i])[a[3]], bits(b[i])[b[3]]) for i in range(3))
+
+
+# which of the audit's cases tells which mistake (matrix of pp.edge_matrices, gate)
+EDGE_TELLS = {"z_min excluded": ("z_is_d", pp.EDGE_GATE), "z_max excluded": ("z_is_d", pp.EDGE_GATE),
+              "X not tested": ("x_overflows", None), "row 0 fused": ("fused_tie", None)}
+
+
+@pytest.mark.parametrize("mistake", pp.MISTAKES)
+def test_the_edge_cases_tell_each_mistake_and_the_older_inputs_do_not(mistake):
+    """(the mutation audit's J1, J2, J3, J5: a gate that drops a pixel exactly on a bound, a kept pixel whose X is no
+    float32, and a row of Q formed with fused multiply-adds all passed tests/test_reproject_gpu.py)"""
+    name, gate = EDGE_TELLS[mistake]
+    q = pp.edge_matrices()[name]
+    for dtype in pp.DTYPES.values():
+        for w in (pp.EDGE_W, pp.EDGE_W - 1):
+            m = pp.edge_map(2, w, pp.EDGE_H, dtype)
+            right, wrong = ref.project(m, q, gate), pp.project_with(m, q, gate, mistake)
+            assert not _same_projection(right, wrong), (mistake, dtype, w)
+            # and it shows in what the entry point stores: the kept count (a gate, X) or a kept pixel's X (fused)
+            if mistake == "row 0 fused":
+                assert right[3][:, 1, 3].all() and (right[0][:, 1, 3] == np.float32(1.0 + 2.0 ** -23)).all()
+                assert (wrong[0][:, 1, 3] == np.float32(1.0)).all()
+            else:
+                assert int(right[3].sum()) != int(wrong[3].sum())
+    # the cases where the gate's bounds are met are there: Z = 2 and Z = 40 exactly, in every pair
+    z = ref.project(pp.edge_map(2, pp.EDGE_W, pp.EDGE_H, np.int32), pp.edge_matrices()["z_is_d"], pp.EDGE_GATE)[2]
+    assert all((z[p] == lim).any() for p in range(2) for lim in pp.EDGE_GATE)
+    # the inputs of test_reproject_every_pattern_matrix_missing_and_gate: every matrix, pattern and gate at its two sizes
+    for (w, h) in ((66, 7), (64, 9)):
+        for qn, q in pp.matrices(w, h).items():
+            if mistake == "row 0 fused" and (w, h) == (64, 9) and qn != "dense":
+                continue            # (exact rationals per pixel: the dense matrix, where every product rounds, at both sizes)
+            for k, pattern in enumerate(pp.PATTERNS):
+                for dtype in pp.DTYPES.values():
+                    m = pp.make_map(pattern, 2, w, h, dtype, seed=k)
+                    for gate in pp.Z_GATES:
+                        assert _same_projection(ref.project(m, q, gate), pp.project_with(m, q, gate, mistake)), \
+                            (mistake, w, h, qn, pattern, gate)
+
+
 def test_point_cloud_is_the_kept_pixels_of_the_dense_map_in_raster_order():
     for (w, h) in ((37, 5), (64, 9), (41, 25)):
         for name, q in pp.matrices(w, h).items():

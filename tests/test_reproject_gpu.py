@@ -138,6 +138,27 @@ def test_reproject_every_pattern_matrix_missing_and_gate(hip, dtype, size):
         plan.close()
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_gate_bounds_an_x_that_is_no_float_and_the_rounding_of_a_row(hip, dtype):
+    """What the mutation audit's J1, J2, J3 and J5 changed decides a pixel only here (tests/reproject_patterns.py
+    edge_matrices; the CPU proof is test_the_edge_cases_tell_each_mistake_and_the_older_inputs_do_not): Z = d exactly, so
+    the pixels with d = 2 and d = 40 sit ON the gate's bounds and must be kept; X = 1e300 x is no float32 from column 1
+    on while Y and Z are finite, so isfinite(X) alone drops the pixel; and at (3, 1) of `fused_tie` X rounds to
+    1 + 2^-23 only if a x is rounded before b y is added.  8 x 3 is the smallest map with (3, 1) in a lane of four
+    pixels (V = 4) and with both bounds in every pair (the even disparities 0 .. 46); 7 x 3 (0 .. 40) takes the
+    one-pixel lanes.  Dense maps, counts and the cloud, both gates."""
+    for w in (pp.EDGE_W, pp.EDGE_W - 1):
+        m = pp.edge_map(2, w, pp.EDGE_H, dtype)
+        plan = plan_for(hip, w, pp.EDGE_H, 2)
+        try:
+            for name, q in pp.edge_matrices().items():
+                for gate in (None, pp.EDGE_GATE):
+                    check_dense(plan, m, q, -1.0, gate, (True, True), True, (w, name, gate))
+                    check_cloud(plan, m, q, None, gate, w * pp.EDGE_H, True, (w, name, gate))
+        finally:
+            plan.close()
+
+
 def test_caller_buffers_and_larger_batches(hip):
     w, h = 64, 9
     plan = plan_for(hip, w, h, 3)

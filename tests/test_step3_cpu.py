@@ -157,6 +157,26 @@ def test_generators_reach_what_they_are_named_for():
     assert 0.05 < (web == 0).mean() < 0.6 and (web[1:-1, 0] == 0).any() and (web[1:-1, -1] == 0).any()
 
 
+def test_a_map_without_a_positive_value_tells_a_maximum_that_starts_at_zero():
+    """(the mutation audit's Z4: k_minmax_zero with its running maximum started at 0 passed tests/test_step3_gpu.py)"""
+    mistake = sp.MISTAKES[0]
+    for w, h in sp.NO_POSITIVE_SHAPES:
+        web = sp.no_positive(w, h, seed=w)
+        assert (web < 0).all()
+        assert sp.min_max_with(web, mistake) != (int(web.min()), int(web.max()))
+        # and the contour depends on it: the interval (max - min) / lines differs
+        lo, hi = int(web.min()), int(web.max())
+        assert (hi - lo) // 10 != (0 - lo) // 10, (w, h)
+    # every map the GPU module gave the reductions before holds a value >= 0 in every pair: a fixture's own map and
+    # filled map, their offset copies (the sign is kept, zeros stay) and the hole-free copy; 100 .. 5000 elsewhere
+    for name in sp.CASES:
+        z = fixture(name)
+        for m in (z["web"], z["filled_tor"]):
+            assert int(m.max()) >= 0, name
+            assert sp.min_max_with(m, mistake) == (int(m.min()), int(m.max())), name
+            assert (m > 0).any() or (m == 0).any(), name
+
+
 @pytest.mark.skipif(not (oracle.step3_ref_available() and oracle.step3_ref_available(asan=True)),
                     reason="oracle/_ref/step3-ref* not built: the reference's sources are not on this machine "
                            "(the fixtures pin it instead)")

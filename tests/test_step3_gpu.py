@@ -223,6 +223,21 @@ def test_lone_minimum_maximum_and_zero_over_many_workgroups(hip, shape):
     plan.close()
 
 
+@pytest.mark.parametrize("w,h", sp.NO_POSITIVE_SHAPES)
+def test_minimum_and_maximum_of_maps_without_a_positive_value(hip, w, h):
+    """Every other map of this module holds a value >= 0 in every pair, so a running maximum started at 0 instead of
+    INT_MIN reported the right number (the mutation audit's Z4; the CPU proof is in tests/test_step3_cpu.py).  Here every
+    value is negative: the maximum is -11, and the contour interval follows from it (98, not 100).  37 x 5 ends in
+    k_minmax_zero's scalar tail and bases its second pair off 16 bytes (scalar loop); 64 x 4 is 16-byte loads alone.
+    No map has a zero, so filling is the identity on both routes."""
+    webs = [sp.no_positive(w, h, seed=w), sp.no_positive(w, h, seed=w + 1) - 5]
+    wants = [expect(x, 2, 10) for x in webs]
+    assert all(int(f.max()) < 0 and c is not None for f, c in wants)
+    plan = hip.StereoPlan(w, h, 16, 1, max_pairs=2)         # (step 3 reads W, H and max_pairs of the plan only)
+    check_staged_and_fused(hip, plan, webs, wants, 2, 10, ("no positive value", w, h))
+    plan.close()
+
+
 # ---------------------------------------------------------------------------
 # 4: sm_step3's routes and flags
 # ---------------------------------------------------------------------------
