@@ -26,7 +26,7 @@ CFLAGS := -std=gnu11 -Wall -Wextra -pedantic -Wno-unused-parameter -Iinclude -Io
 
 HOSTDIR := stereomatching_amd/host
 CSRC    := stereomatching_amd/csrc
-KERNELS := sm_match_bs_ds8 sm_match_bs sm_match_bs_duo8 sm_match_bs_duo sm_match_bs_ds4 sm_api sm_edges sm_run sm_step3 sm_match sm_cost sm_cost_qs sm_cost_pc sm_cost_mfma sm_cost_strip sm_gather sm_lr sm_subpix sm_census sm_census_near sm_sgm sm_sgm_near sm_sgm_both sm_unique sm_filter sm_wmedian sm_wls sm_pyramid sm_interp sm_rectify sm_reproject
+KERNELS := sm_match_bs_ds8 sm_match_bs sm_match_bs_duo8 sm_match_bs_duo sm_match_bs_ds4 sm_api sm_edges sm_run sm_step3 sm_match sm_cost sm_cost_qs sm_cost_pc sm_cost_mfma sm_cost_strip sm_gather sm_lr sm_subpix sm_census sm_census_near sm_sgm sm_sgm_near sm_sgm_both sm_cross sm_unique sm_filter sm_wmedian sm_wls sm_pyramid sm_interp sm_rectify sm_reproject
 DEVOBJ  := $(addprefix stereomatching_amd/obj/product/,$(addsuffix .o,$(KERNELS)))
 # (the same flags, in the same order, as HIPCC_FLAGS of stereomatching_amd/build.py: the two share
 #  stereomatching_amd/obj/product and its flags.txt stamp, so neither rebuilds what the other built)

@@ -642,6 +642,55 @@ int sm_sgm_near_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_g
 /* adds: allocates the banded SGM workspace (and the census workspace) now; idempotent */
 int sm_plan_reserve_sgm_near(sm_plan *plan);
 
+/* ---- cross-based adaptive support over the census cost: PARITY UNPINNED ---- *
+ * New work (no reference counterpart; the cross-based aggregation of Zhang et al. 2009, the aggregation
+ * step of AD-Census).  Every other matcher sums its cost over a square box, so its disparity edges lie up to half a
+ * window beside the object edges.  Here a pixel's support is a union of horizontal segments whose extents ("arms")
+ * stop where the REFERENCE image changes: a support never straddles an intensity edge, and flat regions still get up
+ * to 31 x 31 taps.  Arguments: census_width c in {3, 5, 7}, tau in 0 .. 255, arm L in 0 .. 15.  The plan gives W, H, D
+ * and the border mode; ITS square_width PLAYS NO PART.  Definition (tests/cross_reference.py in numpy):
+ *   arms a_dir(p) of a gray image I, dir in left, right, up, down: the largest l in 0 .. L such that every k = 1 .. l
+ *     has p + k dir inside the image and |I(p + k dir) - I(p)| <= tau.  Arms never leave the image, in either border
+ *     mode (the choice of SGM's paths).  Packed: uint16 = l | r << 4 | u << 8 | d << 12.
+ *   support size N(x, y) = sum over y' = y - u(x, y) .. y + d(x, y) of l(x, y') + r(x, y') + 1; N <= 961.
+ *   cost c_d(x, y) = sm_census_wta's: popcount(C_L(x, y) XOR C_R(x + d, y)); toroidal: x + d mod W; ghost: C_R = 0 for
+ *     x + d >= W.  With the arms of the LEFT image:
+ *     H_d(x, y) = sum over x' = x - l(x, y) .. x + r(x, y) of c_d(x', y),
+ *     E_d(x, y) = sum over y' = y - u(x, y) .. y + d(x, y) of H_d(x, y');  E <= 48 * 961 = 46128.
+ *   best = min_d E_d, web = 1 + the FIRST d reaching it.  The support does not depend on d, so this is the arg-min of
+ *     the normalised costs E_d / N as well.
+ *   subpixel: sm_cost_refine's SM_COST_SAD (equiangular) formula and edge rules on E(s-2), E(s-1), E(s).
+ *   right reference: (best_right, web_right) = mirror(cross(mirror(R), mirror(L))), mirror(a)(x) = a(W-1-x): the arms
+ *     of the RIGHT image.  The check is sm_lr_check's (section 10); in sm_cross_lr d_sub is 0 where it rejected.
+ * arm = 0 gives sm_census_wta at a 1 x 1 window; in ghost mode tau = 255 gives sm_census_wta's web and best at the
+ * window 2 L + 1 (L <= 12).  At most 512 shifts.  Arguments are checked before any device call; a refusal names the
+ * function: a NULL plan or required pointer, max_diff < 0, census_width, tau, arm, pairs, the shift limit, result maps
+ * that overlap each other, and an output that overlaps an input image.  Workspace: the census workspace
+ * (sm_plan_reserve_census) and the packed arms of both images of max_pairs pairs, 4 * max_pairs * W * H bytes (33 MB
+ * per 4K pair); nothing grows with D.  Allocated by sm_plan_reserve_cross or, without it, by the first call that
+ * needs it (a hipMalloc, which synchronises the device), counted in sm_plan_workspace_bytes from then on, freed by
+ * sm_plan_destroy.  All calls run in `stream` order and use nothing the pipelined lanes use.  STREAM CAPTURE: once
+ * sm_plan_reserve_cross has been called; before, a matching call is refused with SM_ERR_ARG, a message naming it,
+ * and the capture valid.                                                                                          */
+/* adds: the packed arms of `images` consecutive gray images (images <= 2 * max_pairs) into d_arms, one uint16 per
+ * pixel, and, d_support non-NULL, N as int32; needs no workspace                                                  */
+int sm_cross_arms(sm_plan *plan, const uint8_t *d_gray, int tau, int arm, int images, uint16_t *d_arms,
+                  int32_t *d_support, void *stream);
+/* adds: the cross-based arg-min -> d_web (and, non-NULL, d_best = the costs E, d_sub int16 in 1/16 of a shift) */
+int sm_cross_wta(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width, int tau,
+                 int arm, int pairs, int32_t *d_web, int32_t *d_best, int16_t *d_sub, void *stream);
+/* adds: the right-reference map (and, d_best_right non-NULL, its costs), natural order */
+int sm_cross_wta_right(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width,
+                       int tau, int arm, int pairs, int32_t *d_web_right, int32_t *d_best_right, void *stream);
+/* adds: descriptors and arms once, left and right arg-min and the check (tolerance max_diff >= 0): d_web = checked
+ * map (0 = rejected), d_best = the left costs, d_sub = the left subpixel map with 0 where rejected; d_best /
+ * d_web_right / d_rejected (one int32 per pair) / d_sub may be NULL                                               */
+int sm_cross_lr(sm_plan *plan, const uint8_t *d_gray_left, const uint8_t *d_gray_right, int census_width, int tau,
+                int arm, int pairs, int max_diff, int32_t *d_web, int32_t *d_best, int32_t *d_web_right,
+                int32_t *d_rejected, int16_t *d_sub, void *stream);
+/* adds: allocates the workspace of the calls above (and the census workspace) now; idempotent */
+int sm_plan_reserve_cross(sm_plan *plan);
+
 /* ---- match uniqueness: runner-up, ratio filter, confidence: PARITY UNPINNED -- *
  * New work (no reference counterpart; the uniquenessRatio test of OpenCV's StereoBM / SGBM).  Every
  * matcher returns how good its winner is, not by how much it won; the left-right check finds occlusions, not the

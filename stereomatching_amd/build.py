@@ -21,7 +21,7 @@ LIB = PKG / "libstereo_hip.so"
 # compile side by side (one unit: ~2 min; four beside the rest: ~50 s on 8 cores)
 SOURCES = ["sm_match_bs_ds8.hip", "sm_match_bs.hip", "sm_match_bs_duo8.hip", "sm_match_bs_duo.hip", "sm_match_bs_ds4.hip",
            "sm_api.hip", "sm_edges.hip", "sm_run.hip", "sm_step3.hip", "sm_match.hip", "sm_cost.hip", "sm_cost_qs.hip", "sm_cost_pc.hip", "sm_cost_mfma.hip", "sm_cost_strip.hip", "sm_gather.hip", "sm_lr.hip",
-           "sm_subpix.hip", "sm_census.hip", "sm_census_near.hip", "sm_sgm.hip", "sm_sgm_near.hip", "sm_sgm_both.hip", "sm_unique.hip", "sm_filter.hip", "sm_wmedian.hip", "sm_wls.hip", "sm_pyramid.hip", "sm_interp.hip",
+           "sm_subpix.hip", "sm_census.hip", "sm_census_near.hip", "sm_sgm.hip", "sm_sgm_near.hip", "sm_sgm_both.hip", "sm_cross.hip", "sm_unique.hip", "sm_filter.hip", "sm_wmedian.hip", "sm_wls.hip", "sm_pyramid.hip", "sm_interp.hip",
            "sm_rectify.hip", "sm_reproject.hip"]
 HEADERS = [CSRC / "sm_internal.h", CSRC / "sm_entry.h", CSRC / "sm_match_bs_kernel.h", CSRC / "sm_bs_network.h", CSRC / "sm_bs_ops.h", CSRC / "sm_cost.h", CSRC / "sm_census.h", CSRC / "sm_census_wta_body.h", CSRC / "sm_sgm_path_body.h", CSRC / "sm_near_tile_body.h", CSRC / "sm_device.h", CSRC / "sm_geom.h", CSRC / "sm_plan_model.h", ROOT / "include" / "stereo_hip.h"]
 OBJDIR = PKG / "obj"

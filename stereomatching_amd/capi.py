@@ -194,6 +194,11 @@ _SIGNATURES = {
     "sm_weighted_median": (_int, [_vp, _vp, _int, _vp, _int, _u16p, _int, _int, _int, _vp, _vp, _vp]),
     "sm_wls_filter": (_int, [_vp, _vp, _int, _vp, _vp, _u16p, _dbl, _int, _int, _int, _vp, _int, _vp, _vp, _vp]),
     "sm_plan_reserve_wls": (_int, [_vp]),
+    "sm_cross_arms": (_int, [_vp, _vp, _int, _int, _int, _vp, _vp, _vp]),
+    "sm_cross_wta": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp]),
+    "sm_cross_wta_right": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp]),
+    "sm_cross_lr": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sm_plan_reserve_cross": (_int, [_vp]),
     "sm_reduce_half": (_int, [_vp, _vp, _int, _int, _vp, _vp]),
     "sm_upsample_double": (_int, [_vp, _vp, _int, _vp, _vp, _u16p, _int, _int, _vp, _vp]),
     "sm_occlusion_classify": (_int, [_vp, _vp, _vp, _int, _vp, _vp]),

@@ -301,6 +301,10 @@ static size_t ws_wls_bytes(const sm_plan *plan)         // N, M and cp: a double
 {
     return (size_t)3 * plan->max_pairs * plan->width * plan->height * sizeof(double);
 }
+static size_t ws_cross_bytes(const sm_plan *plan)       // the packed arms of both images of max_pairs pairs
+{
+    return (size_t)2 * plan->max_pairs * plan->width * plan->height * sizeof(uint16_t);
+}
 
 static const struct {
     size_t member;                          // offsetof(sm_plan, the pointer)
@@ -320,6 +324,7 @@ static const struct {
     /* SM_WS_CLOUD   */ {offsetof(sm_plan, d_cloud), sm_cloud_bytes, false, "tile counts of the point cloud"},
     /* SM_WS_SGM_NEAR */ {offsetof(sm_plan, d_sgm_near), sm_sgm_near_volume_bytes, false, "banded SGM volumes"},
     /* SM_WS_WLS     */ {offsetof(sm_plan, d_wls), ws_wls_bytes, false, "planes of the edge-aware smoother"},
+    /* SM_WS_CROSS   */ {offsetof(sm_plan, d_cross), ws_cross_bytes, false, "arms of the cross-based mode"},
 };
 
 static void *&ws_ptr(const sm_plan *plan, int r) { return *(void **)((char *)plan + ws_rows[r].member); }

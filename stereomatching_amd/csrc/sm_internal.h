@@ -78,6 +78,7 @@ struct sm_plan {
     i32 *d_cloud;        // sm_reproject.hip, sm_point_cloud: kept pixels per tile of 1024 pixels, then their offsets: [max_pairs][tiles]
     void *d_sgm_near;    // sm_sgm_near.hip: one pair's banded volumes: A_b [H][W][16] u16, then S_b [H][W][16] i32 (slot innermost)
     double *d_wls;       // sm_wls.hip: three double planes, N, M and cp, each [max_pairs][H][W]
+    uint16_t *d_cross;   // sm_cross.hip: packed arms [side: 0 = left, 1 = right][max_pairs][H][W], l | r << 4 | u << 8 | d << 12
     int cost_lds_raised; // sm_cost_wta: the LDS limit of this plan's four-wave SAD kernel is raised (on `device`)
     char describe[512];
 };
@@ -139,7 +140,7 @@ void sm_step3_resolve_kernels(void);              // sm_step3.hip
 // adds a member, a row and a set, and nothing else.  A row of 0 bytes is never allocated and never missing.
 // ---------------------------------------------------------------------------
 enum { SM_WS_NARROW, SM_WS_EXT_LR, SM_WS_WEB_LR, SM_WS_GRAY_LR, SM_WS_CENSUS, SM_WS_SGM, SM_WS_FILTER, SM_WS_INTERP,
-       SM_WS_CLOUD, SM_WS_SGM_NEAR, SM_WS_WLS, SM_WS_ROWS };
+       SM_WS_CLOUD, SM_WS_SGM_NEAR, SM_WS_WLS, SM_WS_CROSS, SM_WS_ROWS };
 struct sm_ws_set {
     unsigned rows;             // bit r = row r
     const char *what;          // "the workspace of <what> is not allocated"
@@ -156,6 +157,7 @@ static const sm_ws_set SM_WS_SET_INTERP = {1u << SM_WS_INTERP, "the interpolatio
 static const sm_ws_set SM_WS_SET_SGM_NEAR = {1u << SM_WS_SGM_NEAR, "banded SGM", "sm_plan_reserve_sgm_near", &SM_WS_SET_CENSUS};
 static const sm_ws_set SM_WS_SET_CLOUD = {1u << SM_WS_CLOUD, "the point cloud", "sm_plan_reserve_cloud", nullptr};
 static const sm_ws_set SM_WS_SET_WLS = {1u << SM_WS_WLS, "the edge-aware smoother", "sm_plan_reserve_wls", nullptr};
+static const sm_ws_set SM_WS_SET_CROSS = {1u << SM_WS_CROSS, "the cross-based mode", "sm_plan_reserve_cross", &SM_WS_SET_CENSUS};
 // all or nothing: on a failure every buffer this call allocated is freed and the plan is as before (but `first` stays)
 int sm_ws_reserve(sm_plan *plan, const sm_ws_set &set, const char *me);
 // from an entry point: nothing if present; SM_ERR_ARG naming set.reserve if `st` is capturing; otherwise reserve

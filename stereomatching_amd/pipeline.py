@@ -564,6 +564,53 @@ class StereoPlan:
             lib.sm_sgm_lr_single, lambda pairs: (int(census), int(p1), int(p2), int(paths), pairs), left, right, max_diff,
             want_right, want_best, web, web_right, best, want_sub=want_sub, sub=sub))
 
+    # ---- cross-based adaptive support over the census cost ---------------------
+    def reserve_cross(self):
+        """The cross-based mode's workspace (the census workspace, and the packed arms of both images of max_pairs
+        pairs), allocated now: keeps the allocation out of timed paths and out of stream captures."""
+        check(lib.sm_plan_reserve_cross(self._h))
+
+    def cross_arms(self, images, tau=20, arm=10, want_support=False, out=None):
+        """The support arms of uint8 gray images (sm_cross_arms) -> (arms, support): arms uint16 l | r << 4 | u << 8 |
+        d << 12, how far the pixel's support reaches left, right, up and down (at most `arm` pixels, never past a
+        pixel that differs from it by more than tau, never outside the image); support int32, the number of pixels of
+        the support, or None."""
+        images = self._images(images, torch.uint8, "images")
+        n = images.shape[0]
+        if out is None:
+            out = self._new(n, torch.uint16)
+        else:
+            out = self._images(out, torch.uint16, "out")
+            if out.shape[0] < n:
+                raise ValueError(f"out: room for {out.shape[0]} images, {n} given")
+        support = self._new(n, torch.int32) if want_support else None
+        check(lib.sm_cross_arms(self._h, _ptr(images), int(tau), int(arm), n, _ptr(out), _ptr(support), self._stream()))
+        return out, support
+
+    def cross_wta(self, left, right, census=7, tau=20, arm=10, want_best=True, want_sub=False, web=None, best=None,
+                  sub=None):
+        """Cross-based matcher (sm_cross_wta, parity unpinned) -> (web, best, sub): the census Hamming cost summed over
+        each left pixel's own support (cross_arms of the left image; the plan's window plays no part), arg-min over
+        the shifts, first shift wins; best = the minimum sum, sub int16 in 1/16 of a shift (equiangular fit).  Outputs
+        not wanted are None."""
+        return self._match_one(lib.sm_cross_wta, lambda pairs: (int(census), int(tau), int(arm), pairs), left, right, "",
+                               want_best, web, best, want_sub=want_sub, sub=sub)
+
+    def cross_wta_right(self, left, right, census=7, tau=20, arm=10, want_best=True, web_right=None, best_right=None):
+        """The cross-based right-reference map (sm_cross_wta_right) -> (web_right, best_right), over the supports of
+        the right image: web_right(u, y) = s' means right pixel u matched left pixel u - (s' - 1)."""
+        return self._match_one(lib.sm_cross_wta_right, lambda pairs: (int(census), int(tau), int(arm), pairs), left,
+                               right, "_right", want_best, web_right, best_right)
+
+    def cross_lr(self, left, right, census=7, tau=20, arm=10, max_diff=0, want_right=False, want_best=False,
+                 want_sub=False, web=None, web_right=None, best=None, sub=None) -> SGMLRResult:
+        """Both cross-based passes and the check in one call (sm_cross_lr) -> SGMLRResult(web, rejected, web_right,
+        best, sub); web is the checked map (0 = rejected), best the left minima, sub the left subpixel map with 0 where
+        rejected."""
+        return SGMLRResult(*self._match_lr(
+            lib.sm_cross_lr, lambda pairs: (int(census), int(tau), int(arm), pairs), left, right, max_diff, want_right,
+            want_best, web, web_right, best, want_sub=want_sub, sub=sub))
+
     # ---- banded SGM: aggregation within +-radius of a prior map -----------------
     def reserve_sgm_near(self):
         """The banded SGM workspace (the census workspace, and one pair's banded volumes, 96 bytes a pixel), allocated
