@@ -32,19 +32,12 @@ def P(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def regions(w, h, n, seed):
-    """n images of flat-ish blocks (5 x 3 pixels, four levels 50 apart) under a fine texture of 0 .. 11: gray
-    differences at, below and above every tau of the tests, so arms of every length"""
-    rng = np.random.default_rng(seed)
-    blocks = np.kron(rng.integers(0, 4, (n, (h + 2) // 3, (w + 4) // 5)), np.ones((3, 5), np.int64))[:, :h, :w]
-    return (50 * blocks + rng.integers(0, 12, (n, h, w))).astype(np.uint8)
+regions = cp.regions
 
 
 @functools.lru_cache(maxsize=None)
 def expected(w, h, d, census, tau, arm, mode, md, pairs, seed):
-    left, right = regions(w, h, pairs, seed), regions(w, h, pairs, seed + 1)
-    # (the right images are related to the left ones in half of the rows: real minima beside noise)
-    right[:, ::2] = np.roll(left, 2, axis=2)[:, ::2]
+    left, right = cp.related_pairs(w, h, pairs, seed)
     rows = [x.expected(left[q], right[q], d, census, tau, arm, mode, md) for q in range(pairs)]
     return left, right, {k: np.stack([np.asarray(r[k]) for r in rows]) for k in rows[0]}
 
@@ -72,10 +65,7 @@ def test_arms_and_support_are_exact(hip, w, h):
         plan.close()
 
 
-# (w, h, D, arm, tau): D in {1, 12, 130, 200} and D > W, both sizes (several tiles each way, ragged edges), every arm
-# and tau of the lists
-CASES = [(70, 45, 1, 3, 8), (70, 45, 12, 15, 255), (130, 37, 130, 0, 255), (130, 37, 200, 3, 40), (70, 45, 200, 15, 40),
-         (130, 37, 12, 15, 8)]
+CASES = cp.CASES
 
 
 @pytest.mark.parametrize("census", [3, 5, 7])
@@ -124,24 +114,38 @@ def test_ghost_without_a_threshold_is_the_gpus_box_matcher(hip, arm):
         plan.close()
 
 
-@pytest.mark.parametrize("name,d", [("anti_0", 1), ("anti_D", 5), ("rows_anti", 20)])
-def test_extreme_pairs(hip, name, d):
-    """the bounds of the u16 fields, of the prefix sums and of the keys: E = 48 * 961 at every pixel with a full support,
-    the same value just past the range, and an all-tie map above 2^15"""
+EXTREMES = [("anti_0", 1), ("anti_D", 5), ("rows_anti", 20)]
+
+
+# (the three cases of census 7, toroidal keep their ids; the others are the kernel's other instances: NW = 1, GHOST)
+@pytest.mark.parametrize("name,d,census,mode",
+                         [pytest.param(n, d, 7, "toroidal", id=f"{n}-{d}") for n, d in EXTREMES]
+                         + [pytest.param(n, d, c, m, id=f"{n}-{d}-{c}-{m}") for c, m in ((5, "toroidal"), (7, "ghost"),
+                                                                                         (5, "ghost")) for n, d in EXTREMES])
+def test_extreme_pairs(hip, name, d, census, mode):
+    """the bounds of the u16 fields, of the prefix sums and of the keys: E = (c^2 - 1) * 961 (48 * 961 at c = 7) at every
+    pixel with a full support, the same value just past the range, and an all-tie map (above 2^15 at c = 7).  Ghost: what
+    the definition gives, nothing more"""
     w, h = cp.EXTREME_W, cp.EXTREME_H
     left, right = {"anti_0": lambda: cp.anti(w, h, 0), "anti_D": lambda: cp.anti(w, h, d),
                    "rows_anti": lambda: cp.rows_anti(w, h)}[name]()
-    e = x.expected(left, right, d, 7, 255, 15, "toroidal", 0)
-    if name == "anti_0":
-        assert int((e["best"] == cp.E_MAX).sum()) == cp.EXTREME_INTERIOR
-    if name == "rows_anti":
-        assert (e["web"] == 1).all() and e["best"].max() > 2 ** 15
-    plan = hip.StereoPlan(w, h, d, 1, "toroidal")
+    e = x.expected(left, right, d, census, 255, 15, mode, 0)
+    if mode == "toroidal":
+        if name == "anti_0":
+            assert int((e["best"] == (census * census - 1) * 961).sum()) == cp.EXTREME_INTERIOR
+        if name == "rows_anti":
+            assert (e["web"] == 1).all() and e["best"].max() == (census * census - census) * 961
+            assert census != 7 or e["best"].max() > 2 ** 15
+    plan = hip.StereoPlan(w, h, d, 1, mode)
     try:
-        res = plan.cross_lr(dev(left), dev(right), 7, 255, 15, max_diff=0, want_right=True, want_best=True, want_sub=True)
-        web, best, _ = plan.cross_wta(dev(left), dev(right), 7, 255, 15)
+        res = plan.cross_lr(dev(left), dev(right), census, 255, 15, max_diff=0, want_right=True, want_best=True,
+                            want_sub=True)
+        web, best, sub = plan.cross_wta(dev(left), dev(right), census, 255, 15, want_sub=True)
+        web_right, best_right = plan.cross_wta_right(dev(left), dev(right), census, 255, 15)
         torch.cuda.synchronize()
         assert np.array_equal(host(web)[0], e["web"]) and np.array_equal(host(best)[0], e["best"])
+        assert np.array_equal(host(sub)[0], e["sub"])
+        assert np.array_equal(host(web_right)[0], e["web_right"]) and np.array_equal(host(best_right)[0], e["best_right"])
         assert np.array_equal(host(res.web)[0], e["checked"]) and np.array_equal(host(res.best)[0], e["best"])
         assert np.array_equal(host(res.web_right)[0], e["web_right"])
         assert np.array_equal(host(res.sub)[0], e["sub_checked"]) and int(res.rejected[0]) == e["rejected"]

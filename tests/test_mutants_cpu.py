@@ -40,12 +40,21 @@ MATCHERS_FILES = {"K": COST_FILES, "S": COST_FILES, "Q": COST_FILES, "M": COST_F
                   "H": {"tests/test_sgm_gpu.py", "tests/test_census_extremes_gpu.py"},
                   "L": {"tests/test_lr_gpu.py", "tests/test_lr_sweep_gpu.py", "tests/test_cost_lr_gpu.py"},
                   "J": {"tests/test_reproject_gpu.py"}, "Z": {"tests/test_step3_gpu.py", "tests/test_hip_gpu.py"}}
+# the fourth audit: the cross-based matcher (sm_cross.hip) -- the least each of its three kernels gets (A: k_cross_arms,
+# E: k_cross_wta, Y: k_cross_refine), and the GPU files its groups may name, as whole modules or as node ids
+CROSS = {f"A{i}" for i in range(1, 8)} | {f"E{i}" for i in range(1, 15)} | {f"Y{i}" for i in range(1, 6)}
+CROSS_KERNEL = {"A": "k_cross_arms", "E": "k_cross_wta", "Y": "k_cross_refine"}
+CROSS_FILES = {"tests/test_cross_gpu.py", "tests/test_cross_shapes_gpu.py"}
 # full-size tests no group may name (and so no group may name their whole module)
 TOO_LONG = {"tests/test_hip_gpu.py", "tests/test_extremes_gpu.py", "tests/test_step3_gpu.py"}
 
 
 def third(m):
     return re.fullmatch(r"[KSQMTHLJZ]\d+", m["id"]) is not None
+
+
+def fourth(m):
+    return re.fullmatch(r"[AEY]\d+", m["id"]) is not None
 
 
 @pytest.fixture(scope="module")
@@ -66,9 +75,11 @@ def survivors_recorded():
 
 def test_the_manifest_names_each_mutant_once_and_the_ones_asked_for():
     assert len(IDS) == len(set(IDS))
-    assert RECORDED | NEWEST | AROUND | MATCHERS <= set(IDS)
-    assert len(AROUND) == 39 and len(MATCHERS) == 76
+    assert RECORDED | NEWEST | AROUND | MATCHERS | CROSS <= set(IDS)
+    assert len(AROUND) == 39 and len(MATCHERS) == 76 and len(CROSS) == 26
     assert sum(1 for m in MANIFEST if third(m) and m["run"]) >= 60, "the third audit runs at least 60 mutants"
+    assert sum(1 for m in MANIFEST if fourth(m)) >= 28, "the fourth audit has at least 28 mutants"
+    assert sum(1 for m in MANIFEST if fourth(m) and m["run"]) >= 24, "the fourth audit runs at least 24 mutants"
     patches = {p.stem for p in mt.MUTDIR.glob("*.patch")}
     assert patches == set(IDS), "a patch without an entry, or an entry without a patch"
 
@@ -101,6 +112,10 @@ def test_every_entry_is_complete(m):
         for f in m["groups"]["own"]:
             assert "::" in f or f.split("::")[0] not in TOO_LONG, f"{f}: name single tests of this module"
             assert not f.endswith("test_cost_mode_4k_full_image_vs_own_oracle"), "the 4K test is no part of a group"
+    if fourth(m):
+        assert m["file"] == "sm_cross.hip" and m["kernel"] == CROSS_KERNEL[m["id"][0]]
+        files = {f.split("::")[0] for f in m["groups"]["own"]}
+        assert files and files <= CROSS_FILES, "a mutant of the fourth audit runs against the cross matcher's modules"
 
 
 def test_a_value_that_can_reach_an_address_is_never_run():
@@ -139,13 +154,13 @@ def test_every_group_is_gpu_test_files(m):
     for files in m["groups"].values():
         assert files
         for f in files:
-            # a GPU test file, or one test of it as a pytest node id (third audit)
+            # a GPU test file, or one test of it as a pytest node id (third and fourth audit)
             name, _, test = f.partition("::")
             path = ROOT / name
             assert re.fullmatch(r"tests/test_\w+_gpu\.py", name) and path.is_file(), f
             assert re.search(r"^pytestmark = pytest\.mark\.gpu|^@pytest\.mark\.gpu", path.read_text(), re.M), f
             if "::" in f:
-                assert third(m) and re.fullmatch(r"test_\w+", test), f
+                assert (third(m) or fourth(m)) and re.fullmatch(r"test_\w+", test), f
                 assert re.search(rf"^def {test}\(", path.read_text(), re.M), f"{f}: no such test"
 
 
